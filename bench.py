@@ -8,6 +8,11 @@ A "step" is one NGP training step of BASELINE.json configs[1] on synthetic Lego-
   GradScaler), `update_extra_state` every 16 steps.  Ray batches and targets are resident in HBM before timing.
 `value` = real marched samples (sum of step_counter[:,0] over the timed steps and over ranks) / wall time.
 
+A plain run sets up, warms up, times `--steps` steps and prints the JSON line (plus `--dump-outputs DIR`: the last timed step's
+results as .npy files).  Everything else — the secondary 64-step figure, per-kernel timings and rooflines, the render, the
+PSNR comparisons with the CPU oracle and the long-run convergence study, the Seal and TensoRF sections, the CPU baseline, the
+data-parallel all-reduce timing — runs only under `--full` (each still subject to its own `--no_*` switch).
+
 Multi-GPU (`python -m torch.distributed.run ... bench.py --gpus N`): weak scaling, every rank trains on its own
 4,096-ray batches; one gradient all-reduce (RCCL) per step over the optimizer's flat fp16 buffer, recorded INSIDE the step's
 HIP graph when the process group supports capture (two graphs with an eager collective between them otherwise).
@@ -46,6 +51,9 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=16)
+    ap.add_argument("--full", action="store_true", help="also run every figure and check beyond the headline line (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (loss, sample counter, model state) to DIR/<name>.npy")
     ap.add_argument("--num_rays", type=int, default=4096)
     ap.add_argument("--pretrain", type=int, default=384, help="untimed setup steps that converge the occupancy grid")
     ap.add_argument("--net", choices=["ff", "seal"], default="ff", help="ff: nerf/network_ff (configs[1]); seal: two-encoder nn.Linear net")
@@ -54,7 +62,7 @@ def parse():
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--no_render", action="store_true")
     ap.add_argument("--save_model", default=None, help="write the trained model's state_dict here after the timed region "
-                    "(tools/profile_render.sh renders THIS model under rocprofv3)")
+                    "(and after --full's extra training passes; tools/profile_render.sh renders THIS model under rocprofv3)")
     ap.add_argument("--infer_batch_scale", type=int, default=4, help="inference samples/ray/iteration multiplier (1 = reference heuristic)")
     ap.add_argument("--cpu_steps", type=int, default=5, help="timed CPU-baseline steps (median), after --cpu_warmup warm-ups (BASELINE.md §3: 2 + 5)")
     ap.add_argument("--cpu_warmup", type=int, default=2)
@@ -768,6 +776,35 @@ def long_run_quality(args, dev, R, scene_bits, boxes, steps=3000, note=lambda m:
     return out
 
 
+# ----------------------------------------------------------------------------- outputs of the timed path
+DUMP_FULL_MAX = 1 << 21  # elements: larger tensors are dumped as a fixed, seeded sample of DUMP_SAMPLE elements
+DUMP_SAMPLE = 1 << 20
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, loss, model):
+    """What the last timed step handed its caller: the loss train_step() returned, the step's counter row (marched samples,
+    rays) and the model state the step left (every state_dict entry: parameters after the optimizer step, occupancy grid).
+    Floating-point tensors as float32 (float64 kept), integer ones as float64; a flattened tensor of more than DUMP_FULL_MAX
+    elements as DUMP_SAMPLE elements at indices drawn from a generator seeded with 0 (the same indices for every build)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(()),
+              "step_counter_last": model.step_counter[(model.local_step - 1) % 16]}
+    arrays.update({f"state.{k}": v for k, v in model.state_dict().items()})
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_FULL_MAX:
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0))
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 or not np.issubdtype(a.dtype, np.floating) else np.float32)
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB at {name}")
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 # ----------------------------------------------------------------------------- main
 def main():
     args = parse()
@@ -842,7 +879,7 @@ def main():
         timers.install(grid_meta, queue_ahead)
         rt.install(lambda n, a: 0, queue_ahead)
         ft.install(lambda n, a: a[2] if n == "ffmlp_forward" else (a[3] if n == "ngp_pair_inference" else a[4]), queue_ahead)
-    if not graphed:
+    if not graphed and args.full:
         install_timers()
 
     # density-grid maintenance (every 16 steps, inside the timed region like in the reference's train loop): event pair per call
@@ -870,7 +907,7 @@ def main():
     # the bookkeeping is not part of the reference's step either)
     ring_from = model.local_step % 16
     for i in range(args.steps):
-        step(i)
+        loss = step(i)
         if model.local_step % 16 == 0 or trainer.global_step % trainer.update_extra_interval == 0:
             samples_dev += model.step_counter[ring_from:(model.local_step - 1) % 16 + 1, 0].sum()
             ring_from = 0 if trainer.global_step % trainer.update_extra_interval == 0 else model.local_step % 16
@@ -883,45 +920,48 @@ def main():
     elapsed = time.perf_counter() - t0
     trainer._maybe_update_extra_state = ues_inner
     ues_ms = [a.elapsed_time(b) for a, b in ues_events]
-    # secondary figure over (at least) 64 steps = four whole occupancy-update periods: `ms_per_step` of a short timed region moves
-    # by +-5 % with where the 16-step boundary falls (one 0.5 ms update inside 20 steps is 5 % of them)
-    long_steps = max(64, (args.steps + 15) // 16 * 16)
-    s64 = torch.zeros(1, dtype=torch.int64, device=dev)
-    torch.cuda.synchronize()
-    t64 = time.perf_counter()
-    ring_from = model.local_step % 16
-    for i in range(long_steps):
-        step(args.steps + i)
-        if model.local_step % 16 == 0 or trainer.global_step % trainer.update_extra_interval == 0:
-            s64 += model.step_counter[ring_from:(model.local_step - 1) % 16 + 1, 0].sum()
-            ring_from = 0 if trainer.global_step % trainer.update_extra_interval == 0 else model.local_step % 16
-    if model.local_step % 16 != ring_from:
-        s64 += model.step_counter[ring_from:model.local_step % 16, 0].sum()
-    torch.cuda.synchronize()
-    t64 = time.perf_counter() - t64
-    long_run = {"steps": long_steps, "ms_per_step": t64 / long_steps * 1e3, "samples_per_s_this_rank": float(s64.item()) / t64}
-    timer_steps = args.steps
-    if graphed:
-        # HIP events cannot be recorded inside a graph replay: time the individual kernels in an eager pass of the
-        # SAME step on the same state, immediately after the timed region (not part of `value`)
-        eager = Trainer(model, lr=1e-2, fp16=True, update_extra_interval=10 ** 9, dist=None, optimizer=trainer.optimizer,
-                        scaler=trainer.scaler)
-        eager.global_step = 1
-        install_timers(queue_ahead=True)
-        timer_steps = 32
-        for i in range(-2, timer_steps):
-            if i == 0:  # (the first step of either kind pays first-use allocations: not kept)
-                torch.cuda.synchronize()
-                for t in (timers, rt, ft):
-                    t.reset()
-            ro, rd, gt = batches[i % n_pool]
-            # (half of the pass with the table's update as its own launch: the plain scatter + accumulate pair stays measured,
-            #  `roofline_grid_backward_plain`, next to the product's in-backward update)
-            eager.fuse_table_updates = trainer.fuse_table_updates and i % 2 == 0
-            eager.train_step(ro, rd, gt)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, model)
+    long_run, timer_steps = None, args.steps
+    if args.full:
+        # secondary figure over (at least) 64 steps = four whole occupancy-update periods: `ms_per_step` of a short timed region
+        # moves by +-5 % with where the 16-step boundary falls (one 0.5 ms update inside 20 steps is 5 % of them)
+        long_steps = max(64, (args.steps + 15) // 16 * 16)
+        s64 = torch.zeros(1, dtype=torch.int64, device=dev)
         torch.cuda.synchronize()
-    for t in (timers, rt, ft):
-        t.remove()
+        t64 = time.perf_counter()
+        ring_from = model.local_step % 16
+        for i in range(long_steps):
+            step(args.steps + i)
+            if model.local_step % 16 == 0 or trainer.global_step % trainer.update_extra_interval == 0:
+                s64 += model.step_counter[ring_from:(model.local_step - 1) % 16 + 1, 0].sum()
+                ring_from = 0 if trainer.global_step % trainer.update_extra_interval == 0 else model.local_step % 16
+        if model.local_step % 16 != ring_from:
+            s64 += model.step_counter[ring_from:model.local_step % 16, 0].sum()
+        torch.cuda.synchronize()
+        t64 = time.perf_counter() - t64
+        long_run = {"steps": long_steps, "ms_per_step": t64 / long_steps * 1e3, "samples_per_s_this_rank": float(s64.item()) / t64}
+        if graphed:
+            # HIP events cannot be recorded inside a graph replay: time the individual kernels in an eager pass of the
+            # SAME step on the same state, immediately after the timed region (not part of `value`)
+            eager = Trainer(model, lr=1e-2, fp16=True, update_extra_interval=10 ** 9, dist=None, optimizer=trainer.optimizer,
+                            scaler=trainer.scaler)
+            eager.global_step = 1
+            install_timers(queue_ahead=True)
+            timer_steps = 32
+            for i in range(-2, timer_steps):
+                if i == 0:  # (the first step of either kind pays first-use allocations: not kept)
+                    torch.cuda.synchronize()
+                    for t in (timers, rt, ft):
+                        t.reset()
+                ro, rd, gt = batches[i % n_pool]
+                # (half of the pass with the table's update as its own launch: the plain scatter + accumulate pair stays
+                #  measured, `roofline_grid_backward_plain`, next to the product's in-backward update)
+                eager.fuse_table_updates = trainer.fuse_table_updates and i % 2 == 0
+                eager.train_step(ro, rd, gt)
+            torch.cuda.synchronize()
+        for t in (timers, rt, ft):
+            t.remove()
 
     samples = float(samples_dev.item())
     if world > 1:
@@ -937,24 +977,26 @@ def main():
     if dp is not None:
         seen = torch.ones(1, device=dev)
         dist.all_reduce(seen)
-        for _ in range(3):
-            dp.allreduce_grads()
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a0.record()
-        for _ in range(10):
-            dp.allreduce_grads()
-        a1.record()
-        torch.cuda.synchronize()
-        mine = torch.tensor([a0.elapsed_time(a1) / 10], dtype=torch.float32, device=dev)
-        per_rank = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(per_rank, mine)
-        nbytes = sum(h.numel() * h.element_size() for h in dp.half_grads) + (dp.flat.numel() * 4 if dp.flat is not None else 0)
-        dp_info = {"n_ranks_seen": int(seen.item()), "allreduce_ms_per_rank": [round(float(t.item()), 4) for t in per_rank],
-                   "gradient_bytes": int(nbytes), "collectives_in_graph": bool(getattr(trainer, "collectives_in_graph", False)),
-                   "reduce_op": "avg (in the collective)" if dp.fused_avg() else "sum + divide"}
+        dp_info = {"n_ranks_seen": int(seen.item())}
+        if args.full:
+            for _ in range(3):
+                dp.allreduce_grads()
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+            a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a0.record()
+            for _ in range(10):
+                dp.allreduce_grads()
+            a1.record()
+            torch.cuda.synchronize()
+            mine = torch.tensor([a0.elapsed_time(a1) / 10], dtype=torch.float32, device=dev)
+            per_rank = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(per_rank, mine)
+            nbytes = sum(h.numel() * h.element_size() for h in dp.half_grads) + (dp.flat.numel() * 4 if dp.flat is not None else 0)
+            dp_info.update({"allreduce_ms_per_rank": [round(float(t.item()), 4) for t in per_rank], "gradient_bytes": int(nbytes)})
+        dp_info.update({"collectives_in_graph": bool(getattr(trainer, "collectives_in_graph", False)),
+                        "reduce_op": "avg (in the collective)" if dp.fused_avg() else "sum + divide"})
         if dp_info["n_ranks_seen"] != args.gpus:
             sys.exit(f"bench.py: {dp_info['n_ranks_seen']} ranks took part in the gradient all-reduce, --gpus {args.gpus}")
     if rank != 0:
@@ -963,71 +1005,73 @@ def main():
         return
 
     # --- roofline of the dominant hot kernel
-    ksum = {}
-    for t in (timers, rt, ft):
-        ksum.update(t.summary())
-    s = 2  # fp16 tables under -O
-    bytes_pt = 12 + 16 * 8 * 2 * s + 16 * 2 * s  # 588 B / point / encoder
-    # (per launch: a step has one of grid_encode_backward / grid_encode_backward_adam; the eager timing pass alternates them)
-    dom = max(("grid_encode_forward", "grid_encode_backward", "grid_encode_backward_adam"), key=lambda n: ksum.get(n, {}).get("avg_us", 0))
-    kd = ksum[dom]
-    n_params = sum(p.numel() for p in model.parameters() if p.dim() == 2 and p.shape[1] == 2 and p.shape[0] > 100000)
-    # the in-backward update moves the optimizer's 30 B per parameter (p, m, v read and written in fp32, fp16 copy written,
-    # gradient written + read + cleared) as part of the op: VERDICT r5 #4's bookkeeping
-    op_bytes = kd["units"] * bytes_pt + (30.0 * n_params if dom == "grid_encode_backward_adam" else 0.0)
-    achieved = op_bytes / (kd["avg_us"] * 1e-6) / 1e9
-    traffic, traffic_src = profile_traffic(dom)
-    roofline = {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src, "avg_us": kd["avg_us"], "points_per_launch": kd["units"],
-                "algorithmic_bytes_per_point": bytes_pt, "algorithmic_bytes_per_launch": op_bytes,
-                "algorithmic_bytes_note": ("588 B x points + 30 B x table parameters (the Adam update rides in the accumulate kernel)"
-                                           if dom == "grid_encode_backward_adam" else "588 B x points"),
-                "kernels_ms_per_step": {k: v["total_ms"] / timer_steps for k, v in ksum.items()},
-                "kernel_calls_in_timing_pass": {k: v["calls"] for k, v in ksum.items()},
-                "timing": "HIP events around each native call on the launch stream; " +
-                          ("eager pass of 32 identical steps (2 more discarded) right after the graph-replayed timed region, each call queued behind "
-                           "a short GPU spin so that its kernels run back to back as in the graph" if graphed
-                           else "inside the timed region")}
+    roofline, extra = None, {}
+    if args.full:
+        ksum = {}
+        for t in (timers, rt, ft):
+            ksum.update(t.summary())
+        s = 2  # fp16 tables under -O
+        bytes_pt = 12 + 16 * 8 * 2 * s + 16 * 2 * s  # 588 B / point / encoder
+        # (per launch: a step has one of grid_encode_backward / grid_encode_backward_adam; the eager timing pass alternates them)
+        dom = max(("grid_encode_forward", "grid_encode_backward", "grid_encode_backward_adam"), key=lambda n: ksum.get(n, {}).get("avg_us", 0))
+        kd = ksum[dom]
+        n_params = sum(p.numel() for p in model.parameters() if p.dim() == 2 and p.shape[1] == 2 and p.shape[0] > 100000)
+        # the in-backward update moves the optimizer's 30 B per parameter (p, m, v read and written in fp32, fp16 copy written,
+        # gradient written + read + cleared) as part of the op: VERDICT r5 #4's bookkeeping
+        op_bytes = kd["units"] * bytes_pt + (30.0 * n_params if dom == "grid_encode_backward_adam" else 0.0)
+        achieved = op_bytes / (kd["avg_us"] * 1e-6) / 1e9
+        traffic, traffic_src = profile_traffic(dom)
+        roofline = {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src, "avg_us": kd["avg_us"], "points_per_launch": kd["units"],
+                    "algorithmic_bytes_per_point": bytes_pt, "algorithmic_bytes_per_launch": op_bytes,
+                    "algorithmic_bytes_note": ("588 B x points + 30 B x table parameters (the Adam update rides in the accumulate kernel)"
+                                               if dom == "grid_encode_backward_adam" else "588 B x points"),
+                    "kernels_ms_per_step": {k: v["total_ms"] / timer_steps for k, v in ksum.items()},
+                    "kernel_calls_in_timing_pass": {k: v["calls"] for k, v in ksum.items()},
+                    "timing": "HIP events around each native call on the launch stream; " +
+                              ("eager pass of 32 identical steps (2 more discarded) right after the graph-replayed timed region, each call queued behind "
+                               "a short GPU spin so that its kernels run back to back as in the graph" if graphed
+                               else "inside the timed region")}
 
-    if "grid_encode_backward" in ksum:  # the plain scatter + accumulate pair (gradient table written), as rounds 3 - 5 reported it
-        kb = ksum["grid_encode_backward"]
-        ach_b = kb["units"] * bytes_pt / (kb["avg_us"] * 1e-6) / 1e9
-        roofline["grid_backward_plain"] = {"kernel": "grid_encode_backward (k_bin_scatter6 + k_bin_accumulate6, update separate)",
-                                           "achieved": ach_b, "frac": ach_b / HBM_PEAK_GBS, "avg_us": kb["avg_us"],
-                                           "points_per_launch": kb["units"], "algorithmic_bytes_per_point": bytes_pt}
-    # --- matrix-core roofline of the fused MLPs (north_star: MFMA utilisation on ffmlp against chip peak; SURVEY §8d: the
-    # bound is min(MFMA peak, arithmetic intensity x HBM peak)).  Both ffmlp nets of this config are 32-64-64-16 (3 matmuls,
-    # 7,168 MAC per sample forward); the training forward stores no activations (the fused backward re-computes them), so the
-    # forward moves 2*32 + 2*16 bytes per sample and the backward 2*32 (input) + 2*16 (output grad) + 2*32 (input grad).
-    # Backward flops: re-computed forward + data gradient + weight gradient = 3x the forward's.
-    mfma_peak = 2500.0  # TFLOP/s dense fp16, MI355X_MICROARCH.md
-    roofline_ffmlp = {}
-    def mlp_macs(net):  # MAC per sample of an FFMLP: in x W + (layers - 1) x W x W + W x 16 (padded output)
-        return net.input_dim * net.hidden_dim + (net.num_layers - 1) * net.hidden_dim ** 2 + net.hidden_dim * 16
-    nets = [n for n in (getattr(model, "sigma_net", None), getattr(model, "color_net", None)) if hasattr(n, "num_layers")]
-    # (the timers average over the launches of both networks: density net 32-64-64-16 = 7,168 MAC, colour net 32-64-64-64-16 =
-    #  11,264 MAC per sample; rounds 1-3 priced both at 7,168)
-    macs = sum(mlp_macs(n) for n in nets) / len(nets) if nets else 7168
-    # (round 4: the training forward of both networks is ONE launch, `ngp_pair_inference` = k_ffmlp_ngp_pair: both networks'
-    #  flops; 64 B encoder features + 12 B directions in, 64 B colour-net input + 4 + 2 + 12 B out per sample)
-    for name, flops, byts in (("ffmlp_forward", 2 * macs, 96), ("ngp_pair_inference", 2 * macs * len(nets), 158),
-                              ("ffmlp_backward", 6 * macs, 160)):
-        k = ksum.get(name)
-        if not k or not k["units"]:
-            continue
-        ach = k["units"] * flops / (k["avg_us"] * 1e-6) / 1e12
-        bound = min(mfma_peak, flops / byts * HBM_PEAK_GBS / 1e3)
-        roofline_ffmlp[name] = {"achieved": ach, "unit": "TFLOP/s", "bound": bound, "bound_is": "mfma" if bound == mfma_peak else "AI x hbm",
-                                "frac_of_bound": ach / bound, "frac_of_mfma_peak": ach / mfma_peak, "avg_us": k["avg_us"],
-                                "samples_per_launch": k["units"], "flop_per_sample": flops, "algorithmic_bytes_per_sample": byts}
-    if roofline_ffmlp:
-        import glob as _glob
-        _tr = sorted(f for f in _glob.glob(os.path.join(REPO, "profiles", "r*_timed_region.md")) if re.match(r"r\d+_timed_region\.md$", os.path.basename(f)))
-        roofline_ffmlp["counters"] = ((f"profiles/{os.path.basename(_tr[-1])}" if _tr else "no committed profile") +
-                                      ", section 'Matrix cores' (SQ_INSTS_VALU_MFMA_MOPS_F16, SQ_VALU_MFMA_BUSY_CYCLES per kernel); issued MFMA "
-                                      "work = 1.14x / 1.09x the algorithmic work of the density / colour net (16-row output layer on a 32-row tile)")
+        if "grid_encode_backward" in ksum:  # the plain scatter + accumulate pair (gradient table written), as rounds 3 - 5 reported it
+            kb = ksum["grid_encode_backward"]
+            ach_b = kb["units"] * bytes_pt / (kb["avg_us"] * 1e-6) / 1e9
+            roofline["grid_backward_plain"] = {"kernel": "grid_encode_backward (k_bin_scatter6 + k_bin_accumulate6, update separate)",
+                                               "achieved": ach_b, "frac": ach_b / HBM_PEAK_GBS, "avg_us": kb["avg_us"],
+                                               "points_per_launch": kb["units"], "algorithmic_bytes_per_point": bytes_pt}
+        # --- matrix-core roofline of the fused MLPs (north_star: MFMA utilisation on ffmlp against chip peak; SURVEY §8d: the
+        # bound is min(MFMA peak, arithmetic intensity x HBM peak)).  Both ffmlp nets of this config are 32-64-64-16 (3 matmuls,
+        # 7,168 MAC per sample forward); the training forward stores no activations (the fused backward re-computes them), so the
+        # forward moves 2*32 + 2*16 bytes per sample and the backward 2*32 (input) + 2*16 (output grad) + 2*32 (input grad).
+        # Backward flops: re-computed forward + data gradient + weight gradient = 3x the forward's.
+        mfma_peak = 2500.0  # TFLOP/s dense fp16, MI355X_MICROARCH.md
+        roofline_ffmlp = {}
+        def mlp_macs(net):  # MAC per sample of an FFMLP: in x W + (layers - 1) x W x W + W x 16 (padded output)
+            return net.input_dim * net.hidden_dim + (net.num_layers - 1) * net.hidden_dim ** 2 + net.hidden_dim * 16
+        nets = [n for n in (getattr(model, "sigma_net", None), getattr(model, "color_net", None)) if hasattr(n, "num_layers")]
+        # (the timers average over the launches of both networks: density net 32-64-64-16 = 7,168 MAC, colour net 32-64-64-64-16 =
+        #  11,264 MAC per sample; rounds 1-3 priced both at 7,168)
+        macs = sum(mlp_macs(n) for n in nets) / len(nets) if nets else 7168
+        # (round 4: the training forward of both networks is ONE launch, `ngp_pair_inference` = k_ffmlp_ngp_pair: both networks'
+        #  flops; 64 B encoder features + 12 B directions in, 64 B colour-net input + 4 + 2 + 12 B out per sample)
+        for name, flops, byts in (("ffmlp_forward", 2 * macs, 96), ("ngp_pair_inference", 2 * macs * len(nets), 158),
+                                  ("ffmlp_backward", 6 * macs, 160)):
+            k = ksum.get(name)
+            if not k or not k["units"]:
+                continue
+            ach = k["units"] * flops / (k["avg_us"] * 1e-6) / 1e12
+            bound = min(mfma_peak, flops / byts * HBM_PEAK_GBS / 1e3)
+            roofline_ffmlp[name] = {"achieved": ach, "unit": "TFLOP/s", "bound": bound, "bound_is": "mfma" if bound == mfma_peak else "AI x hbm",
+                                    "frac_of_bound": ach / bound, "frac_of_mfma_peak": ach / mfma_peak, "avg_us": k["avg_us"],
+                                    "samples_per_launch": k["units"], "flop_per_sample": flops, "algorithmic_bytes_per_sample": byts}
+        if roofline_ffmlp:
+            import glob as _glob
+            _tr = sorted(f for f in _glob.glob(os.path.join(REPO, "profiles", "r*_timed_region.md")) if re.match(r"r\d+_timed_region\.md$", os.path.basename(f)))
+            roofline_ffmlp["counters"] = ((f"profiles/{os.path.basename(_tr[-1])}" if _tr else "no committed profile") +
+                                          ", section 'Matrix cores' (SQ_INSTS_VALU_MFMA_MOPS_F16, SQ_VALU_MFMA_BUSY_CYCLES per kernel); issued MFMA "
+                                          "work = 1.14x / 1.09x the algorithmic work of the density / colour net (16-row output layer on a 32-row tile)")
 
-    extra = {"roofline_ffmlp": roofline_ffmlp, "samples_per_s_64steps": long_run}
+        extra = {"roofline_ffmlp": roofline_ffmlp, "samples_per_s_64steps": long_run}
     collectives_in_graph = bool(getattr(trainer, "collectives_in_graph", False))  # (the Seal section below drops `trainer`)
     if graphed:
         extra["graph_captures_in_timed_region"] = trainer.n_captures - captures0
@@ -1036,7 +1080,7 @@ def main():
                                        "ms_per_step_amortised": sum(ues_ms) / args.steps}
     if args.save_model and rank == 0:
         torch.save(model.state_dict(), args.save_model)
-    if not args.no_render:
+    if args.full and not args.no_render:
         # full 800x800 frame renders (inference loop) + PSNR against the analytic scene
         model.infer_batch_scale = args.infer_batch_scale
         r = syn.get_rays(poses[:1].to(dev), syn.lego_intrinsics(), 800, 800)
@@ -1082,11 +1126,11 @@ def main():
 
     def note(msg):
         print(f"[bench] {msg}", file=sys.stderr, flush=True)
-    if world == 1 and not args.no_render:
+    if args.full and world == 1 and not args.no_render:
         note("psnr vs oracle render")
         extra["psnr"] = psnr_vs_oracle(model, lambda: Net(bound=1, cuda_ray=True, density_scale=1, min_near=0.2, density_thresh=10),
                                        poses, scene_bits, boxes, dev, R)
-    if world == 1 and not args.no_long_run and args.net == "ff":
+    if args.full and world == 1 and not args.no_long_run and args.net == "ff":
         lr_ = long_run_quality(args, dev, R, scene_bits, boxes, steps=args.long_run_steps, note=note, seeds=args.long_run_seeds,
                                n_views=args.long_run_views, hw=400)
         # the committed many-seed study of the same comparison (tools/psnr_seeds.py): what settles "within 0.1 dB"
@@ -1107,7 +1151,7 @@ def main():
             extra["psnr"]["vs_reference_path"] = {"delta_db": ms["delta_db"], "ci95": ms["delta_db_ci95"], "seeds": ms["seeds"],
                                                   "within_0p1_db_with_95pct_confidence": ms["ci95_inside_0p1_db"], "source": ms["file"],
                                                   "this_run": {"seeds": lr_["seeds"], "delta_db": lr_["delta_db"], "ci95": lr_["delta_db_ci95"]}}
-    if not args.no_seal and args.net == "ff":
+    if args.full and not args.no_seal and args.net == "ff":
         # configs[2] on one GPU; under `--gpus N` (or --force_dp) configs[3]: the same section data-parallel over the ranks
         note("seal section")
         del trainer
@@ -1120,7 +1164,7 @@ def main():
             # the headline line of an N-rank run must not be lost to a failure of this optional section (every rank runs the
             # same code on the same shapes: a Python-level failure is raised on all of them)
             extra["seal"] = {"error": f"{type(e).__name__}: {e}"[:400]}
-    if world == 1 and not args.no_tensorf and args.net == "ff":
+    if args.full and world == 1 and not args.no_tensorf and args.net == "ff":
         note("tensorf section")
         extra["tensorf"] = tensorf_section(args, dev, batches, note)
         if not args.no_seal:
@@ -1129,7 +1173,7 @@ def main():
             except Exception as e:  # (a reported gap, not a lost bench line)
                 extra["tensorf"]["seal"] = {"error": f"{type(e).__name__}: {e}"[:400]}
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         note("cpu baseline")
         cpu = cpu_baseline(args, args.cpu_rays)
 

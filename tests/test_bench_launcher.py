@@ -106,7 +106,7 @@ def test_force_dp_runs_the_seal_section_through_a_one_rank_rccl_group():
     """`bench.py --force_dp` on one GPU: the plain step AND the Seal section (configs[3]'s code path: sharded pretraining,
     per-rank proxy targets, fine-tuning with both tables' gradients in the all-reduce) run through a 1-rank RCCL process
     group, collectives issued for real."""
-    argv = ["--force_dp", "--steps", "4", "--warmup", "2", "--pretrain", "64", "--no_cpu_baseline", "--no_render",
+    argv = ["--full", "--force_dp", "--steps", "4", "--warmup", "2", "--pretrain", "64", "--no_cpu_baseline", "--no_render",
             "--no_long_run", "--no_tensorf", "--seal_teacher_steps", "48"]
     r = _run(argv)
     if r.returncode != 0:
