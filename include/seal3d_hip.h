@@ -552,6 +552,28 @@ int s3d_seal_bbox_map(const float* points, const float* dirs, uint32_t M, const 
 int s3d_seal_map_color(const void* rgbs, const uint8_t* mask, uint32_t M, int dtype, const float* hsv, const float* rgb_target,
                        float light_offset, void* out, void* stats, const int32_t* n_valid /* or NULL */, s3d_stream_t stream);
 
+/* Seal proxy mapper, brush tool — SealNeRF/seal_utils.py:282-453 (map_to_origin :408-453) with :132-153 (map_mask) and
+ * :630-685 (inside test, ray direction = the UNnormalised normal_expand).  points / out_points DEVICE [M,3] f32, mask DEVICE
+ * [M] u8.  triangles DEVICE [n_tris,3,3] (12 per stroke), bounds DEVICE [n_bounds,2,3] (min,max; one per stroke), border
+ * DEVICE [n_border,3] (projected border points of all strokes; may be NULL when linear == 0).  normal_expand, center: HOST [3]
+ * (of the last stroke).  linear != 0: masked p -> (p - n) + (|att - d| / att) n where att > d, d = distance of p's projection
+ * on the plane (center, n) to the nearest border point; linear == 0 (`dry`): p unchanged.  Unmasked rows are copied; the
+ * view directions are not touched (the reference returns them unchanged). */
+int s3d_seal_brush_map(const float* points, uint32_t M, const float* triangles, uint32_t n_tris, const float* bounds,
+                       uint32_t n_bounds, const float* border, uint32_t n_border, const float* normal_expand, const float* center,
+                       float attenuation_distance, int linear, float* out_points, uint8_t* mask,
+                       const int32_t* n_valid /* or NULL */, s3d_stream_t stream);
+
+/* Seal proxy mapper, anchor tool — SealNeRF/seal_utils.py:456-570 (map_to_origin :514-570).  points / out_points DEVICE
+ * [M,3] f32, mask DEVICE [M] u8, triangles DEVICE [n_tris,3,3]; bounds HOST [2,3]; params HOST [14] = v_anchor[3],
+ * v_offset[3], v_h[3], len_h, radius, scale[3].  As in the reference the decision is batch-wide: if no row passes the map
+ * mask (AABB, all coordinates != 0, inside test along the fixed axis) every row is copied with mask 0; otherwise EVERY row
+ * goes through the cone / plane-side map and mask = cone AND side.  flag: DEVICE 4 bytes of scratch that carries that
+ * decision between the call's kernels (cleared by the call), so no host synchronisation is needed. */
+int s3d_seal_anchor_map(const float* points, uint32_t M, const float* triangles, uint32_t n_tris, const float* bounds,
+                        const float* params, float* out_points, uint8_t* mask, void* flag,
+                        const int32_t* n_valid /* or NULL */, s3d_stream_t stream);
+
 /* ------------------------------------------------------------------ parameter update
  * The reference's update is torch.optim.Adam(betas=(0.9, 0.99), eps=1e-15) under torch.cuda.amp.GradScaler
  * (nerf/utils.py:356-361, 495-537; main_SealNeRF.py:283-288).  These three calls are that update taken directly

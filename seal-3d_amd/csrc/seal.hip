@@ -27,8 +27,10 @@ struct SealMap {
 // do the rays (o, d) AND (o, -d) each hit a triangle?  seal_utils.py:630-665, expression by expression, for both rays inside one
 // walk over the triangles: the kernel is a chain of scalar loads (the triangles live in the kernel arguments) and ~40
 // dependent flops per triangle and ray — one walk instead of two, four triangles' loads in flight (19.7 -> 16 us per teacher
-// sample batch)
-__device__ __forceinline__ bool hit_both(const SealMap& m, float ox, float oy, float oz, float dx, float dy, float dz) {
+// sample batch).  `tri(f, k, d)` = coordinate d of vertex k of triangle f (kernel arguments for the bbox tool, a device
+// buffer for the brush / anchor tools).
+template <class Tri>
+__device__ __forceinline__ bool hit_both(const Tri& tri, uint32_t n_tris, float ox, float oy, float oz, float dx, float dy, float dz) {
     bool hit_p = false, hit_n = false;
     auto test = [&](float dx_, float dy_, float dz_, float e1x, float e1y, float e1z, float e2x, float e2y, float e2z, float nx, float ny,
                     float nz, float ax, float ay, float az) {
@@ -40,17 +42,25 @@ __device__ __forceinline__ bool hit_both(const SealMap& m, float ox, float oy, f
         return (t >= 0.0f) && (u >= 0.0f) && (v >= 0.0f) && ((u + v) <= 1.0f);
     };
 #pragma unroll 4
-    for (uint32_t f = 0; f < m.n_tris; f++) {
-        const float* v0 = m.tri[f][0];
-        const float e1x = m.tri[f][1][0] - v0[0], e1y = m.tri[f][1][1] - v0[1], e1z = m.tri[f][1][2] - v0[2];
-        const float e2x = m.tri[f][2][0] - v0[0], e2y = m.tri[f][2][1] - v0[1], e2z = m.tri[f][2][2] - v0[2];
+    for (uint32_t f = 0; f < n_tris; f++) {
+        const float v0x = tri(f, 0, 0), v0y = tri(f, 0, 1), v0z = tri(f, 0, 2);
+        const float e1x = tri(f, 1, 0) - v0x, e1y = tri(f, 1, 1) - v0y, e1z = tri(f, 1, 2) - v0z;
+        const float e2x = tri(f, 2, 0) - v0x, e2y = tri(f, 2, 1) - v0y, e2z = tri(f, 2, 2) - v0z;
         const float nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
-        const float ax = ox - v0[0], ay = oy - v0[1], az = oz - v0[2];
+        const float ax = ox - v0x, ay = oy - v0y, az = oz - v0z;
         hit_p |= test(dx, dy, dz, e1x, e1y, e1z, e2x, e2y, e2z, nx, ny, nz, ax, ay, az);
         hit_n |= test(-dx, -dy, -dz, e1x, e1y, e1z, e2x, e2y, e2z, nx, ny, nz, ax, ay, az);
     }
     return hit_p && hit_n;
 }
+struct ArgTris {  // the bbox tool's triangles, kernel arguments
+    const SealMap& m;
+    __device__ __forceinline__ float operator()(uint32_t f, int k, int d) const { return m.tri[f][k][d]; }
+};
+struct BufTris {  // [n, 3, 3] in device memory, read at wave-uniform addresses
+    const float* __restrict__ t;
+    __device__ __forceinline__ float operator()(uint32_t f, int k, int d) const { return t[f * 9 + k * 3 + d]; }
+};
 
 __global__ void __launch_bounds__(256) k_seal_map(const float* __restrict__ points, const float* __restrict__ dirs, uint32_t M,
                                                   SealMap m, float* __restrict__ out_p, float* __restrict__ out_d,
@@ -66,7 +76,7 @@ __global__ void __launch_bounds__(256) k_seal_map(const float* __restrict__ poin
     in = in && (px != 0.0f) && (py != 0.0f) && (pz != 0.0f);  // `points.all(1)` of the reference (seal_utils.py:141)
     if (in) {
         const float tx = 0.4395064455f, ty = 0.617598629942f, tz = 0.652231566745f;  // seal_utils.py:676-678
-        in = hit_both(m, px, py, pz, tx, ty, tz);
+        in = hit_both(ArgTris{m}, m.n_tris, px, py, pz, tx, ty, tz);
     }
     float ox = px, oy = py, oz = pz;
     if (m.has_source && (m.empty_hi[0] > px) && (px > m.empty_lo[0]) && (m.empty_hi[1] > py) && (py > m.empty_lo[1]) &&
@@ -96,6 +106,158 @@ __global__ void __launch_bounds__(256) k_seal_map(const float* __restrict__ poin
     }
 }
 
+
+// ---- brush tool (seal_utils.py:282-453): map_mask with the UNnormalised `normal_expand` as the ray direction of the inside
+// test, then for masked points p' = (p - n) + (|att - d| / att) n  where att > d, d = distance of p's projection on the stroke
+// plane to the nearest border point (`linear`), or p' = p (`dry`).  The reference gathers the masked points (host sync), runs
+// the [2m x F] einsum inside test and an [m x B] torch.cdist; here one lane per point, the border points staged through LDS in
+// per-wave tiles and read at one address across the wave (broadcast).  A wave whose lanes are all outside skips the border walk.
+struct SealBrush {
+    float ne[3], center[3], att;
+    uint32_t n_tris, n_bounds, n_border, linear;
+};
+constexpr uint32_t kBrushTile = 256;  // border points per wave and tile (4 KB of LDS per wave)
+
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ void __launch_bounds__(256) k_seal_brush_map(const float* __restrict__ points, uint32_t M, SealBrush b,
+                                                        const float* __restrict__ tris, const float* __restrict__ bounds,
+                                                        const float* __restrict__ border, float* __restrict__ out_p,
+                                                        uint8_t* __restrict__ mask, const int32_t* __restrict__ n_valid) {
+    __shared__ float4 tile[4][kBrushTile];
+    const uint32_t Mv = valid_rows(M, n_valid);
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    // (the loop bound is uniform per wave, so the wave stays together for the tile walk)
+    for (uint32_t base = blockIdx.x * 256 + w * 64; base < Mv; base += gridDim.x * 256) {
+        const uint32_t i = base + lane;
+        const bool live = i < Mv;
+        float px = 0.0f, py = 0.0f, pz = 0.0f;
+        if (live) { px = points[(size_t)i * 3]; py = points[(size_t)i * 3 + 1]; pz = points[(size_t)i * 3 + 2]; }
+        bool in = false;
+        for (uint32_t s = 0; s < b.n_bounds; s++) {
+            const float* lo = bounds + s * 6;
+            const float* hi = lo + 3;
+            in |= (hi[0] > px) && (px > lo[0]) && (hi[1] > py) && (py > lo[1]) && (hi[2] > pz) && (pz > lo[2]);
+        }
+        in = live && in && (px != 0.0f) && (py != 0.0f) && (pz != 0.0f);  // `points.all(1)` (seal_utils.py:141)
+        if (in) in = hit_both(BufTris{tris}, b.n_tris, px, py, pz, b.ne[0], b.ne[1], b.ne[2]);
+        float ox = px, oy = py, oz = pz;
+        if (b.linear && __ballot(in) != 0ull) {
+            // project_points(n, c, p) = p - ((p - c) . n) / (n . n) * n   (seal_utils.py:728-736, same order)
+            const float nn = b.ne[0] * b.ne[0] + b.ne[1] * b.ne[1] + b.ne[2] * b.ne[2];
+            const float s = ((px - b.center[0]) * b.ne[0] + (py - b.center[1]) * b.ne[1] + (pz - b.center[2]) * b.ne[2]) / nn;
+            const float qx = px - s * b.ne[0], qy = py - s * b.ne[1], qz = pz - s * b.ne[2];
+            float best = INFINITY;
+            for (uint32_t t0 = 0; t0 < b.n_border; t0 += kBrushTile) {
+                const uint32_t nt = min(kBrushTile, b.n_border - t0);
+                wave_sync();  // (the previous tile has been read)
+                for (uint32_t k = lane; k < nt; k += 64) {
+                    const float* q = border + (size_t)(t0 + k) * 3;
+                    tile[w][k] = make_float4(q[0], q[1], q[2], 0.0f);
+                }
+                wave_sync();
+                if (in) {
+                    // four independent running minima (a minimum is exact in any order): four LDS reads in flight per step
+                    float m4[4] = {best, INFINITY, INFINITY, INFINITY};
+                    uint32_t k = 0;
+                    for (; k + 4 <= nt; k += 4) {
+#pragma unroll
+                        for (int u = 0; u < 4; u++) {
+                            const float4 c = tile[w][k + u];
+                            const float dx = qx - c.x, dy = qy - c.y, dz = qz - c.z;
+                            m4[u] = fminf(m4[u], dx * dx + dy * dy + dz * dz);
+                        }
+                    }
+                    for (; k < nt; k++) {
+                        const float4 c = tile[w][k];
+                        const float dx = qx - c.x, dy = qy - c.y, dz = qz - c.z;
+                        m4[0] = fminf(m4[0], dx * dx + dy * dy + dz * dz);
+                    }
+                    best = fminf(fminf(m4[0], m4[1]), fminf(m4[2], m4[3]));
+                }
+            }
+            if (in) {
+                const float d = sqrtf(best);
+                ox = px - b.ne[0]; oy = py - b.ne[1]; oz = pz - b.ne[2];
+                if (b.att > d) {
+                    const float f = fabsf(b.att - d) / b.att;
+                    ox = ox + f * b.ne[0]; oy = oy + f * b.ne[1]; oz = oz + f * b.ne[2];
+                }
+            }
+        }
+        if (live) {
+            out_p[(size_t)i * 3] = ox; out_p[(size_t)i * 3 + 1] = oy; out_p[(size_t)i * 3 + 2] = oz;
+            mask[i] = in ? 1 : 0;
+        }
+    }
+}
+
+// ---- anchor tool (seal_utils.py:456-570).  Its map_to_origin decides on the WHOLE batch: when no point passes the map mask
+// the batch comes back unchanged with an all-false mask, otherwise the cone / plane-side mapping applies to every point and
+// its mask is cone AND side.  That decision stays on the device (a graph-capturable call): k_seal_word_zero clears a word,
+// k_seal_anchor_flag sets it if any row passes the map mask, k_seal_anchor_map reads it.
+struct SealAnchor {
+    float lo[3], hi[3];
+    float anchor[3], offset[3], h[3], len_h, radius, scale[3];
+    uint32_t n_tris;
+};
+__global__ void k_seal_word_zero(uint32_t* w) { if (threadIdx.x == 0) w[0] = 0u; }
+
+__global__ void __launch_bounds__(256) k_seal_anchor_flag(const float* __restrict__ points, uint32_t M, SealAnchor a,
+                                                          const float* __restrict__ tris, uint32_t* __restrict__ flag,
+                                                          const int32_t* __restrict__ n_valid) {
+    const uint32_t Mv = valid_rows(M, n_valid);
+    bool any = false;
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < Mv; i += gridDim.x * 256) {
+        const float px = points[(size_t)i * 3], py = points[(size_t)i * 3 + 1], pz = points[(size_t)i * 3 + 2];
+        bool in = (a.hi[0] > px) && (px > a.lo[0]) && (a.hi[1] > py) && (py > a.lo[1]) && (a.hi[2] > pz) && (pz > a.lo[2]) &&
+                  (px != 0.0f) && (py != 0.0f) && (pz != 0.0f);
+        if (in) in = hit_both(BufTris{tris}, a.n_tris, px, py, pz, 0.4395064455f, 0.617598629942f, 0.652231566745f);
+        any |= in;
+    }
+    if (__ballot(any) != 0ull && (threadIdx.x & 63) == 0) *flag = 1u;
+}
+
+__global__ void __launch_bounds__(256) k_seal_anchor_map(const float* __restrict__ points, uint32_t M, SealAnchor a,
+                                                         const uint32_t* __restrict__ flag, float* __restrict__ out_p,
+                                                         uint8_t* __restrict__ mask, const int32_t* __restrict__ n_valid) {
+    const uint32_t Mv = valid_rows(M, n_valid);
+    const bool apply = *flag != 0u;
+    const float hh = a.h[0] * a.h[0] + a.h[1] * a.h[1] + a.h[2] * a.h[2];
+    const float slope = a.len_h / a.radius * 1.1f;
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < Mv; i += gridDim.x * 256) {
+        const float px = points[(size_t)i * 3], py = points[(size_t)i * 3 + 1], pz = points[(size_t)i * 3 + 2];
+        float ox = px, oy = py, oz = pz;
+        bool valid = false;
+        if (apply) {
+            // projected = project_points(v_h, v_anchor, p); to_plane = projected - p
+            const float s = ((px - a.anchor[0]) * a.h[0] + (py - a.anchor[1]) * a.h[1] + (pz - a.anchor[2]) * a.h[2]) / hh;
+            const float jx = px - s * a.h[0], jy = py - s * a.h[1], jz = pz - s * a.h[2];
+            const float tx = jx - px, ty = jy - py, tz = jz - pz;
+            const float dist = sqrtf(tx * tx + ty * ty + tz * tz);
+            const float os = dist / a.len_h;
+            const float qx = jx - os * a.offset[0], qy = jy - os * a.offset[1], qz = jz - os * a.offset[2];
+            const float ax = qx - a.anchor[0], ay = qy - a.anchor[1], az = qz - a.anchor[2];
+            const float ad = sqrtf(ax * ax + ay * ay + az * az);
+            const bool cone = (ad <= a.radius) && (dist / (a.radius - ad) < slope);
+            const bool side = (tx * a.h[0] + ty * a.h[1] + tz * a.h[2]) > 0.0f;
+            valid = cone && side;
+            if (valid) {
+                const float g = -((a.len_h - dist) / 10.0f);
+                const float mx = qx - (g * a.h[0]) / a.len_h, my = qy - (g * a.h[1]) / a.len_h, mz = qz - (g * a.h[2]) / a.len_h;
+                ox = (mx - a.anchor[0]) * a.scale[0] + a.anchor[0];
+                oy = (my - a.anchor[1]) * a.scale[1] + a.anchor[1];
+                oz = (mz - a.anchor[2]) * a.scale[2] + a.anchor[2];
+            }
+        }
+        out_p[(size_t)i * 3] = ox; out_p[(size_t)i * 3 + 1] = oy; out_p[(size_t)i * 3 + 2] = oz;
+        mask[i] = valid ? 1 : 0;
+    }
+}
 
 // ---- colour edit of the bbox tool (seal_utils.py:48-58 map_color, :739-769 modify_hsv / modify_rgb, color_utils.py:33-66) ----
 // The renderers re-colour only the samples the proxy moved: `rgbs[mask] = map_color(.., rgbs[mask])` (SealNeRF/renderer.py:316,
@@ -272,4 +434,44 @@ S3D_EXPORT int s3d_seal_map_color(const void* rgbs, const uint8_t* mask, uint32_
     if (dtype == S3D_F32) hipLaunchKernelGGL(k_seal_color_apply<float>, grid, block, 0, st, (const float*)rgbs, mask, M, c, n_valid, sw, (float*)out);
     else hipLaunchKernelGGL(k_seal_color_apply<_Float16>, grid, block, 0, st, (const _Float16*)rgbs, mask, M, c, n_valid, sw, (_Float16*)out);
     return check_launch("seal_map_color");
+}
+
+S3D_EXPORT int s3d_seal_brush_map(const float* points, uint32_t M, const float* triangles, uint32_t n_tris, const float* bounds,
+                                  uint32_t n_bounds, const float* border, uint32_t n_border, const float* normal_expand,
+                                  const float* center, float attenuation_distance, int linear, float* out_points, uint8_t* mask,
+                                  const int32_t* n_valid, s3d_stream_t stream) {
+    if (M == 0) return S3D_OK;
+    S3D_REQUIRE(points && triangles && bounds && normal_expand && center && out_points && mask, "seal_brush_map: null pointer");
+    S3D_REQUIRE(n_tris >= 1 && n_bounds >= 1, "seal_brush_map: no stroke");
+    S3D_REQUIRE(!linear || (border && n_border >= 1), "seal_brush_map: the linear attenuation needs border points");
+    SealBrush b;
+    memset(&b, 0, sizeof(b));
+    for (int d = 0; d < 3; d++) { b.ne[d] = normal_expand[d]; b.center[d] = center[d]; }  // HOST [3] each
+    b.att = attenuation_distance;
+    b.n_tris = n_tris; b.n_bounds = n_bounds; b.n_border = linear ? n_border : 0u; b.linear = linear ? 1u : 0u;
+    hipLaunchKernelGGL(k_seal_brush_map, dim3(std::min<uint32_t>(div_up<uint32_t>(M, 256), 2048u)), dim3(256), 0, as_stream(stream),
+                       points, M, b, triangles, bounds, border, out_points, mask, n_valid);
+    return check_launch("seal_brush_map");
+}
+
+S3D_EXPORT int s3d_seal_anchor_map(const float* points, uint32_t M, const float* triangles, uint32_t n_tris, const float* bounds,
+                                   const float* params, float* out_points, uint8_t* mask, void* flag, const int32_t* n_valid,
+                                   s3d_stream_t stream) {
+    if (M == 0) return S3D_OK;
+    S3D_REQUIRE(points && triangles && bounds && params && out_points && mask && flag, "seal_anchor_map: null pointer");
+    S3D_REQUIRE(n_tris >= 1, "seal_anchor_map: no triangles");
+    SealAnchor a;
+    memset(&a, 0, sizeof(a));
+    for (int d = 0; d < 3; d++) {  // HOST: bounds [2,3]; params [v_anchor 3 | v_offset 3 | v_h 3 | len_h | radius | scale 3]
+        a.lo[d] = bounds[d]; a.hi[d] = bounds[3 + d];
+        a.anchor[d] = params[d]; a.offset[d] = params[3 + d]; a.h[d] = params[6 + d]; a.scale[d] = params[11 + d];
+    }
+    a.len_h = params[9]; a.radius = params[10]; a.n_tris = n_tris;
+    hipStream_t st = as_stream(stream);
+    const dim3 grid(std::min<uint32_t>(div_up<uint32_t>(M, 256), 2048u)), block(256);
+    auto* fw = reinterpret_cast<uint32_t*>(flag);
+    hipLaunchKernelGGL(k_seal_word_zero, dim3(1), dim3(64), 0, st, fw);  // (a kernel, not a memset node: see tensorf.hip's bins)
+    hipLaunchKernelGGL(k_seal_anchor_flag, grid, block, 0, st, points, M, a, triangles, fw, n_valid);
+    hipLaunchKernelGGL(k_seal_anchor_map, grid, block, 0, st, points, M, a, fw, out_points, mask, n_valid);
+    return check_launch("seal_anchor_map");
 }

@@ -42,7 +42,7 @@ EXPORTS = [
     "s3d_grads_nonfinite", "s3d_adam_step", "s3d_adam_step_multi", "s3d_adam_advance", "s3d_scaler_update", "s3d_step_ring_push", "s3d_step_epilogue",
     "s3d_ngp_mid_forward", "s3d_ngp_mid_backward", "s3d_ngp_mid2_forward", "s3d_ngp_mid2_backward", "s3d_ngp_rgb_forward", "s3d_ngp_rgb_backward",
     "s3d_bg_mse_forward", "s3d_bg_mse_backward", "s3d_bg_targets", "s3d_l1_pair_workspace_size", "s3d_l1_pair_loss",
-    "s3d_seal_bbox_map", "s3d_seal_map_color", "s3d_grid_encode_backward_adam", "s3d_vm_features_forward",
+    "s3d_seal_bbox_map", "s3d_seal_map_color", "s3d_seal_brush_map", "s3d_seal_anchor_map", "s3d_grid_encode_backward_adam", "s3d_vm_features_forward",
     "s3d_aabb_normalize", "s3d_weighted_abs_sum_workspace_size", "s3d_weighted_abs_sum", "s3d_pack_linear_chain", "s3d_unpack_linear_chain",
     "s3d_vm_backward_max_bins", "s3d_vm_backward_keys", "s3d_vm_backward_bins_workspace_size", "s3d_vm_backward_bins",
     "s3d_vm_backward_stage_bytes", "s3d_vm_transpose_factors",
@@ -1006,7 +1006,7 @@ class NgpHeadBackend:
 
 
 class SealBackend:
-    """csrc/seal.hip — Seal-3D's bbox proxy mapper (SealNeRF/seal_utils.py:132-279, 630-685) on the device"""
+    """csrc/seal.hip — Seal-3D's proxy mappers (SealNeRF/seal_utils.py:132-570, 630-685: bbox, brush, anchor) on the device"""
 
     @staticmethod
     def bbox_map(points, dirs, host, out_points, out_dirs, mask, n_valid=None):
@@ -1030,6 +1030,40 @@ class SealBackend:
                                        _u(keep[1][0].shape[0]), ptr[2], ptr[3], ptr[4], ptr[5], ptr[6], ptr[7], _p(out_points),
                                        _p(out_dirs), _p(mask), _nv(n_valid), _stream()), "seal_bbox_map")
 
+
+    @staticmethod
+    def brush_map(points, dev, out_points, mask, n_valid=None):
+        """brush tool (include/seal3d_hip.h: s3d_seal_brush_map); `dev`: the mapper's device constants (triangles, bounds,
+        border as fp32 GPU tensors with their counts, normal_expand / center as 3 host floats, attenuation_distance, linear)"""
+        import numpy as np
+        _need(points, torch.float32, "points")
+        if mask.dtype != torch.uint8:
+            raise RuntimeError("mask must be uint8")
+        ne = np.ascontiguousarray(dev["normal_expand"], dtype=np.float32)
+        ce = np.ascontiguousarray(dev["center"], dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        border = dev["border"] if dev["n_border"] else None
+        _check(lib().s3d_seal_brush_map(_p(points), _u(points.shape[0]), _p(dev["triangles"]), _u(dev["n_tris"]), _p(dev["bounds"]),
+                                        _u(dev["n_bounds"]), _p(border), _u(dev["n_border"]), ne.ctypes.data_as(fp),
+                                        ce.ctypes.data_as(fp), C.c_float(dev["attenuation_distance"]), C.c_int(1 if dev["linear"] else 0),
+                                        _p(out_points), _p(mask), _nv(n_valid), _stream()), "seal_brush_map")
+
+    @staticmethod
+    def anchor_map(points, dev, out_points, mask, flag, n_valid=None):
+        """anchor tool (include/seal3d_hip.h: s3d_seal_anchor_map); `dev`: triangles (fp32 GPU tensor) + n_tris, bounds [2,3]
+        and params [14] as host float32 arrays; `flag`: a 4-byte GPU scratch tensor"""
+        import numpy as np
+        _need(points, torch.float32, "points")
+        if mask.dtype != torch.uint8:
+            raise RuntimeError("mask must be uint8")
+        bo = np.ascontiguousarray(dev["bounds"], dtype=np.float32)
+        pa = np.ascontiguousarray(dev["params"], dtype=np.float32)
+        if bo.size != 6 or pa.size != 14:
+            raise RuntimeError("anchor_map: bounds [2,3] and params [14]")
+        fp = C.POINTER(C.c_float)
+        _check(lib().s3d_seal_anchor_map(_p(points), _u(points.shape[0]), _p(dev["triangles"]), _u(dev["n_tris"]), bo.ctypes.data_as(fp),
+                                         pa.ctypes.data_as(fp), _p(out_points), _p(mask), _p(flag), _nv(n_valid), _stream()),
+               "seal_anchor_map")
 
     @staticmethod
     def map_color(rgbs, mask, hsv, rgb_target, light_offset, out, stats=None, n_valid=None):

@@ -1,11 +1,14 @@
 """Seal proxy functions (SealNeRF/seal_utils.py): map edited-space points back to the source space.
 
-Only the bounding-box tool of BASELINE configs 3/4 is implemented (`SealBBoxMapper`, seal_utils.py:155-279):
-config keys `type: bbox`, `raw` (points spanning the source box), `transform` (4x4 source->target), `scale` (3),
-`boundType` ('to' | 'from' | 'both'), optional `mapSource`.  No trimesh / pytorch3d: the box meshes are built
-directly (12 triangles per box) and the inside test is the reference's two-ray Moller-Trumbore parity test
-(seal_utils.py:630-685) in plain torch.  Colour remapping: the bbox tool's `hsv` / `rgb` options (seal_utils.py:48-58,
-739-769, color_utils.py:33-66); the brush tool's image remap is not part of the bbox configuration.
+Three tools, each a `SealMapper` with a torch op sequence and device kernels (csrc/seal.hip):
+  bbox    (`SealBBoxMapper`, seal_utils.py:155-279): `raw` (points spanning the source box), `transform` (4x4 source->target),
+          `scale` (3), `boundType` ('to' | 'from' | 'both'), optional `mapSource`;
+  brush   (`SealBrushMapper`, :282-453): `line` strokes pushed / pulled along their plane normal, `linear` or `dry`;
+  anchor  (`SealAnchorMapper`, :456-570): a control point dragged by `translation`, its cone of influence carried along.
+No trimesh / pytorch3d / skspatial: the box meshes are built directly (12 triangles per box), the plane fit and the uv-sphere
+vertex set are restated, and the inside test is the reference's two-ray Moller-Trumbore parity test (seal_utils.py:630-685)
+in plain torch.  Colour remapping: the `hsv` / `rgb` options (seal_utils.py:48-58, 739-769, color_utils.py:33-66) of every
+tool; the brush tool's image remap (`imageConfig`), `curve` strokes and the `ease-in` / `ease-out` attenuation are refused.
 """
 import json
 
@@ -24,7 +27,7 @@ def _box_vertices(lo, hi):
 
 def _min_area_rect(p2):
     """minimum-area enclosing rectangle of 2-D points: (area, angle of the rectangle's first axis); one side of the optimum
-    is collinear with a hull edge, so the hull edges are the only candidates"""
+    is collinear with a hull edge, so the hull edges are the only candidates, and the extents are those of the hull's vertices"""
     from scipy.spatial import ConvexHull
     hull = p2[ConvexHull(p2).vertices]
     best = (np.inf, 0.0)
@@ -34,7 +37,7 @@ def _min_area_rect(p2):
         if n < 1e-12:
             continue
         e = e / n
-        q = p2 @ np.stack([e, [-e[1], e[0]]], axis=1)
+        q = hull @ np.stack([e, [-e[1], e[0]]], axis=1)
         area = np.prod(q.max(0) - q.min(0))
         if area < best[0]:
             best = (area, np.arctan2(e[1], e[0]))
@@ -63,7 +66,7 @@ def oriented_box_vertices(points, snap=1e-9):
         n = eq[:3] / np.linalg.norm(eq[:3])
         if n[np.argmax(np.abs(n))] < 0:
             n = -n  # a normal and its opposite give the same box
-        if any(abs(abs(n @ m) - 1) < 1e-12 for m in seen):
+        if seen and np.any(np.abs(np.abs(np.array(seen) @ n) - 1) < 1e-12):
             continue
         seen.append(n)
         ref = np.eye(3)[np.argmin(np.abs(n))]
@@ -107,9 +110,12 @@ def moller_trumbore_any(ray_o, ray_d, tris, eps=1e-8):
     return ((t >= 0.0) & (u >= 0.0) & (v >= 0.0) & ((u + v) <= 1.0)).any(1)
 
 
-def points_in_mesh(points, triangles):
-    """a point is inside iff rays in BOTH directions of the test axis hit the mesh (seal_utils.py:668-685)"""
-    d = torch.tensor([_TEST_DIR], device=points.device, dtype=points.dtype).repeat(points.shape[0], 1)
+def points_in_mesh(points, triangles, rays_d=None):
+    """a point is inside iff rays in BOTH directions of the test axis hit the mesh (seal_utils.py:668-685); `rays_d` [1, 3]
+    replaces the fixed axis (the brush tool tests along its unnormalised `normal_expand`, seal_utils.py:379)"""
+    if rays_d is None:
+        rays_d = torch.tensor([_TEST_DIR], device=points.device, dtype=points.dtype)
+    d = rays_d.repeat(points.shape[0], 1)
     hit = moller_trumbore_any(torch.cat([points, points]), torch.cat([d, -d]), triangles)
     return hit[:points.shape[0]] & hit[points.shape[0]:]
 
@@ -167,7 +173,82 @@ def modify_rgb(rgb, modification, light_offset=0):
     return hsv_to_rgb(out)
 
 
-class SealBBoxMapper:
+class SealMapper:
+    """what every tool shares (seal_utils.py:18-153): the constants in `map_data` (float32 tensors) and `map_triangles`, their
+    device, the `hsv` / `rgb` colour edit of the moved samples and the AABB + mesh `map_mask`.  `native = True`: GPU tensors go
+    through the tool's device kernels (csrc/seal.hip); False = the reference's torch op sequence."""
+    native = True
+    map_test_dir = None  # [1, 3] ray direction of the inside test; None = the fixed axis
+
+    def _color_options(self, seal_config):
+        if "hsv" in seal_config:  # seal_utils.py:226-230, 389-393, 497-501
+            self.map_data["hsv"] = torch.tensor(seal_config["hsv"], dtype=torch.float32)
+        if "rgb" in seal_config:
+            self.map_data["rgb"] = torch.tensor(seal_config["rgb"], dtype=torch.float32)
+            self.map_data["rgb_light_offset"] = float(seal_config.get("rgbLightOffset", 0))
+
+    def to(self, device):
+        if device != self.device:
+            self.map_data = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in self.map_data.items()}
+            self.map_triangles = self.map_triangles.to(device)
+            if self.map_test_dir is not None:
+                self.map_test_dir = self.map_test_dir.to(device)
+            self.device = device
+        return self
+
+    def map_mask(self, points):
+        """AABB pre-test (incl. the reference's `points.all(1)` term) then the mesh inside test — seal_utils.py:132-153"""
+        bounds = self.map_data["map_bound"]
+        if bounds.ndim == 2:
+            bounds = bounds[None]
+        mask = None
+        for i in range(bounds.shape[0]):
+            cur = points.all(1) & ((bounds[i][1] > points) & (points > bounds[i][0])).all(1)
+            mask = cur if mask is None else (mask | cur)
+        if not mask.any():
+            return mask
+        inside = points_in_mesh(points[mask], self.map_triangles, self.map_test_dir)
+        mask[mask.clone()] = inside
+        return mask
+
+    def map_color(self, points, dirs, colors):
+        """seal_utils.py:48-81 (`hsv` / `rgb` of seal.json, :226-230, 389-393, 497-501): hue / saturation / value offsets, then
+        re-colouring towards a target RGB that keeps each sample's brightness offset from the batch mean.  The brush tool's
+        image remap (`imageConfig`) is not supported (get_seal_mapper refuses it)."""
+        if "hsv" in self.map_data:
+            colors = modify_hsv(colors, self.map_data["hsv"])
+        if "rgb" in self.map_data:
+            colors = modify_rgb(colors, self.map_data["rgb"], self.map_data.get("rgb_light_offset", 0))
+        return colors
+
+    def map_color_masked(self, points, dirs, colors, mask):
+        """the renderers' use of map_color (SealNeRF/renderer.py:316, 396-399): `colors[mask] = map_color(points[mask],
+        dirs[mask], colors[mask])` — returns a new tensor, `colors` is left alone"""
+        md = self.map_data
+        if (self.native and colors.is_cuda and mask is not None and colors.dtype in (torch.float32, torch.float16) and colors.dim() == 2
+                and colors.shape[1] == 3 and "image" not in md and ("hsv" in md or "rgb" in md)):
+            # one or two passes on the device (csrc/seal.hip: s3d_seal_map_color) instead of a boolean gather (host sync), ~40
+            # masked elementwise launches and a scatter back; the batch mean of the `rgb` edit is an order-independent sum
+            import s3d_hip
+            src = colors.contiguous()
+            out = torch.empty_like(src)
+            hsv = md["hsv"].tolist() if "hsv" in md else None
+            tgt = md["rgb"].tolist() if "rgb" in md else None
+            s3d_hip.SealBackend.map_color(src, mask.view(torch.uint8), hsv, tgt, md.get("rgb_light_offset", 0) if tgt is not None else 0.0,
+                                          out, n_valid=s3d_hip.active_row_limit(src.shape[0]))
+            return out
+        out = colors.clone()
+        if mask is None:
+            return self.map_color(points, dirs, out)
+        sel = colors[mask]
+        if sel.shape[0]:
+            out[mask] = self.map_color(points[mask] if points is not None else None, dirs[mask] if dirs is not None else None,
+                                       sel.float()).to(colors.dtype)
+        return out
+
+
+
+class SealBBoxMapper(SealMapper):
     def __init__(self, seal_config):
         self.config = seal_config
         T = np.array(seal_config["transform"], dtype=np.float64)
@@ -202,11 +283,7 @@ class SealBBoxMapper:
             "scale": torch.tensor(1.0 / scale, dtype=torch.float32),
             "center": torch.tensor(center, dtype=torch.float32),
         }
-        if "hsv" in seal_config:  # seal_utils.py:226-230
-            self.map_data["hsv"] = torch.tensor(seal_config["hsv"], dtype=torch.float32)
-        if "rgb" in seal_config:
-            self.map_data["rgb"] = torch.tensor(seal_config["rgb"], dtype=torch.float32)
-            self.map_data["rgb_light_offset"] = float(seal_config.get("rgbLightOffset", 0))
+        self._color_options(seal_config)
         if seal_config.get("mapSource"):
             self.map_data["empty_bound"] = torch.tensor(from_b, dtype=torch.float32)
             self.map_data["map_source"] = torch.tensor(seal_config["mapSource"], dtype=torch.float32)
@@ -221,30 +298,6 @@ class SealBBoxMapper:
         if "map_source" in md:
             self._host["empty_bound"] = md["empty_bound"].numpy().copy()
             self._host["map_source"] = md["map_source"].numpy().copy()
-
-    def to(self, device):
-        if device != self.device:
-            self.map_data = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in self.map_data.items()}
-            self.map_triangles = self.map_triangles.to(device)
-            self.device = device
-        return self
-
-    def map_mask(self, points):
-        """AABB pre-test (incl. the reference's `points.all(1)` term) then the mesh inside test — seal_utils.py:132-153"""
-        bounds = self.map_data["map_bound"]
-        if bounds.ndim == 2:
-            bounds = bounds[None]
-        mask = None
-        for i in range(bounds.shape[0]):
-            cur = points.all(1) & ((bounds[i][1] > points) & (points > bounds[i][0])).all(1)
-            mask = cur if mask is None else (mask | cur)
-        if not mask.any():
-            return mask
-        inside = points_in_mesh(points[mask], self.map_triangles)
-        mask[mask.clone()] = inside
-        return mask
-
-    native = True  # GPU tensors go through the one-pass device kernel; False = the reference's torch op sequence
 
     def _map_native(self, points, dirs):
         import s3d_hip
@@ -282,41 +335,241 @@ class SealBBoxMapper:
             out_d[mask] = torch.matmul(self.map_data["rotation"], dirs[mask].T).T
         return out_p, out_d, mask
 
-    def map_color(self, points, dirs, colors):
-        """seal_utils.py:48-81 for the bbox tool (`hsv` / `rgb` of seal.json, :226-230): hue / saturation / value offsets, then
-        re-colouring towards a target RGB that keeps each sample's brightness offset from the batch mean.  The image remap
-        (`image`) belongs to the brush tool and is not part of the bbox configuration."""
-        if "hsv" in self.map_data:
-            colors = modify_hsv(colors, self.map_data["hsv"])
-        if "rgb" in self.map_data:
-            colors = modify_rgb(colors, self.map_data["rgb"], self.map_data.get("rgb_light_offset", 0))
-        return colors
+
+def fit_plane(points):
+    """skspatial's `Plane.best_fit` (what seal_utils.py:311, 476 call): the centroid, and the left singular vector of the
+    centred points with the smallest singular value as the normal; collinear points raise as there"""
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    centroid = pts.mean(0)
+    centered = pts - centroid
+    if np.linalg.matrix_rank(centered) <= 1:
+        raise ValueError("The points must not be collinear.")
+    u, _, _ = np.linalg.svd(centered.T, full_matrices=False)
+    return u[:, 2].copy(), centroid
 
 
-    def map_color_masked(self, points, dirs, colors, mask):
-        """the renderers' use of map_color (SealNeRF/renderer.py:316, 396-399): `colors[mask] = map_color(points[mask],
-        dirs[mask], colors[mask])` — returns a new tensor, `colors` is left alone"""
+def project_points(plane_norm, plane_point, target_points):
+    """seal_utils.py:728-736: project points onto the plane (normal need not be unit)"""
+    v = target_points - plane_point
+    return target_points - (v @ plane_norm).unsqueeze(1) / (plane_norm @ plane_norm) * plane_norm
+
+
+def mesh_surface_points_mask(triangles, points, offset=1e-4):
+    """seal_utils.py:712-725: a point is on the border when one of its six +-offset neighbours is outside the mesh"""
+    o = torch.tensor([[0, 0, offset], [0, 0, -offset], [0, offset, 0], [0, -offset, 0], [offset, 0, 0], [-offset, 0, 0]],
+                     dtype=torch.float64).to(points.device, points.dtype)
+    return torch.sum(torch.stack([~points_in_mesh(points + o[i], triangles) for i in range(6)]), 0) > 0
+
+
+def uv_sphere_vertices(radius, count=(32, 32)):
+    """the vertex set of `trimesh.creation.uv_sphere(radius)` (what seal_utils.py:485 builds the anchor box around), restated:
+    count -> (c0 + c0 % 2, 2 (c1 + c1 % 2)) = (32, 64); theta_i = i pi / 31 (i = 0..31), phi_j = 2 pi j / 64 (j = 0..63);
+    vertex = radius (sin theta_i cos phi_j, sin theta_i sin phi_j, cos theta_i), the poles once each.  Only the convex hull of
+    the set matters here (the oriented box is built around it)."""
+    c0 = count[0] + count[0] % 2
+    c1 = 2 * (count[1] + count[1] % 2)
+    theta = np.linspace(0.0, np.pi, c0)[1:-1]
+    phi = np.linspace(0.0, 2.0 * np.pi, c1 + 1)[:-1]
+    t, p = np.meshgrid(theta, phi, indexing="ij")
+    ring = np.stack([np.sin(t) * np.cos(p), np.sin(t) * np.sin(p), np.cos(t)], -1).reshape(-1, 3)
+    return np.concatenate([[[0.0, 0.0, 1.0]], ring, [[0.0, 0.0, -1.0]]]) * radius
+
+
+class SealBrushMapper(SealMapper):
+    """brush tool (seal_utils.py:282-453): push (brushPressure > 0) or pull the surface under one or more `line` strokes along
+    the strokes' plane normal.  Config keys: `raw` (one stroke [N, 3] or a list of strokes), `normal` (which side of the plane
+    is positive), `brushType` ('line', or a list with one entry per stroke), `brushDepth`, `brushPressure`,
+    `attenuationDistance`, `attenuationMode` ('linear' | 'dry'), optional `hsv` / `rgb` / `rgbLightOffset`.
+    Each stroke's edit region is the oriented box of its points lifted by 2 * normal_expand and sunk by brushDepth *
+    normal_expand (12 triangles); a sample inside is moved back by normal_expand, less the part that attenuates linearly with
+    the distance of its projection on the plane to the nearest border point of the strokes."""
+
+    def __init__(self, seal_config):
+        self.config = seal_config
+        strokes = seal_config["raw"]
+        if np.asarray(strokes[0]).ndim == 1:
+            strokes = [strokes]
+        brush_type = seal_config["brushType"]
+        if isinstance(brush_type, str):
+            brush_type = [brush_type] * len(strokes)
+        pressure, depth = seal_config["brushPressure"], seal_config["brushDepth"]
+        tris, bounds, border = [], [], []
+        for i, stroke in enumerate(strokes):
+            pts = np.asarray(stroke, dtype=np.float64)
+            normal, point = fit_plane(pts)
+            if "normal" in seal_config and normal @ np.asarray(seal_config["normal"], dtype=np.float64) < 0:
+                normal = -normal
+            normal_expand = normal * pressure
+            projected = project_points(torch.from_numpy(normal), torch.from_numpy(point), torch.from_numpy(pts))
+            if brush_type[i] != "line":
+                raise NotImplementedError(f"brushType `{brush_type[i]}`: only `line` strokes (a `curve` stroke's mesh needs open3d's "
+                                          "vertex clustering, seal_utils.py:606-624)")
+            verts = oriented_box_vertices(np.vstack([pts + 2 * normal_expand, pts - depth * normal_expand]))
+            t = verts[_BOX_FACES]
+            tris.append(t)
+            bounds.append(np.stack([verts.min(0), verts.max(0)]))
+            # (the reference runs this test in the mapper's float32)
+            on_border = mesh_surface_points_mask(torch.from_numpy(t).float(), projected.float())
+            border.append(projected[on_border])
+        mode = seal_config["attenuationMode"]
+        if mode not in ("linear", "dry"):
+            raise NotImplementedError(f"attenuationMode `{mode}`: the reference implements `linear` and `dry` only")
+        bounds = np.stack(bounds)
+        self.map_data = {
+            "force_fill_bound": torch.tensor(bounds, dtype=torch.float32),
+            "map_bound": torch.tensor(bounds, dtype=torch.float32),
+            "normal_expand": torch.tensor(normal_expand, dtype=torch.float32),  # (of the LAST stroke, as in the reference)
+            "center": torch.tensor(point, dtype=torch.float32),
+            "border_points": torch.cat(border).float(),  # (of ALL strokes)
+            "attenuation_distance": torch.tensor(float(seal_config["attenuationDistance"]), dtype=torch.float32),
+            "attenuation_mode": mode,
+        }
+        self._color_options(seal_config)
+        self.map_triangles = torch.tensor(np.concatenate(tris), dtype=torch.float32)
+        self.map_test_dir = self.map_data["normal_expand"][None].clone()  # the UNnormalised ray direction of the inside test
+        self.device = torch.device("cpu")
+        self._dev = {}
+
+    def _device_constants(self, device):
+        """triangles / bounds / border points as one device buffer per device (uploaded on the first native call there; a
+        caller that edits map_data / map_triangles in place clears `_dev`)"""
+        c = self._dev.get(device)
+        if c is None:
+            md = self.map_data
+            parts = [self.map_triangles.reshape(-1), md["map_bound"].reshape(-1), md["border_points"].reshape(-1)]
+            buf = torch.cat([x.detach().cpu().float() for x in parts]).to(device)
+            n = [x.numel() for x in parts]
+            c = {"triangles": buf[:n[0]], "bounds": buf[n[0]:n[0] + n[1]], "border": buf[n[0] + n[1]:],
+                 "n_tris": n[0] // 9, "n_bounds": n[1] // 6, "n_border": n[2] // 3,
+                 "normal_expand": md["normal_expand"].detach().cpu().numpy().astype(np.float32),
+                 "center": md["center"].detach().cpu().numpy().astype(np.float32),
+                 "attenuation_distance": float(md["attenuation_distance"]), "linear": md["attenuation_mode"] == "linear"}
+            self._dev[device] = c
+        return c
+
+    def _map_native(self, points, dirs):
+        import s3d_hip
+        lead = points.shape
+        p = points.reshape(-1, 3).contiguous()
+        out_p = torch.empty_like(p)
+        mask = torch.empty(p.shape[0], dtype=torch.bool, device=p.device)
+        s3d_hip.SealBackend.brush_map(p, self._device_constants(p.device), out_p, mask.view(torch.uint8),
+                                      s3d_hip.active_row_limit(p.shape[0]))
+        return out_p.view(lead), dirs, mask
+
+    @torch.autocast("cuda", enabled=False)
+    def map_to_origin(self, points, dirs=None):
+        """seal_utils.py:408-453; `dirs` come back unchanged"""
+        if self.native and points.is_cuda and points.dtype == torch.float32 and points.shape[-1] == 3 and points.numel() > 0:
+            return self._map_native(points, dirs)
+        self.to(points.device)
         md = self.map_data
-        if (self.native and colors.is_cuda and mask is not None and colors.dtype in (torch.float32, torch.float16) and colors.dim() == 2
-                and colors.shape[1] == 3 and "image" not in md and ("hsv" in md or "rgb" in md)):
-            # one or two passes on the device (csrc/seal.hip: s3d_seal_map_color) instead of a boolean gather (host sync), ~40
-            # masked elementwise launches and a scatter back; the batch mean of the `rgb` edit is an order-independent sum
-            import s3d_hip
-            src = colors.contiguous()
-            out = torch.empty_like(src)
-            hsv = md["hsv"].tolist() if "hsv" in md else None
-            tgt = md["rgb"].tolist() if "rgb" in md else None
-            s3d_hip.SealBackend.map_color(src, mask.view(torch.uint8), hsv, tgt, md.get("rgb_light_offset", 0) if tgt is not None else 0.0,
-                                          out, n_valid=s3d_hip.active_row_limit(src.shape[0]))
-            return out
-        out = colors.clone()
-        if mask is None:
-            return self.map_color(points, dirs, out)
-        sel = colors[mask]
-        if sel.shape[0]:
-            out[mask] = self.map_color(points[mask] if points is not None else None, dirs[mask] if dirs is not None else None,
-                                       sel.float()).to(colors.dtype)
-        return out
+        mask = self.map_mask(points)
+        if not mask.any():
+            return points, dirs, mask
+        inner = points[mask]
+        if md["attenuation_mode"] == "linear":
+            ne, att = md["normal_expand"], md["attenuation_distance"]
+            projected = project_points(ne, md["center"], inner)
+            dist = torch.cdist(projected, md["border_points"]).min(1)[0]
+            mapped = inner - ne
+            near = att > dist
+            mapped[near] += (torch.abs(att - dist[near]) / att)[None].T @ ne[None]
+        else:  # dry: no space mapping
+            mapped = inner
+        out_p = points.clone()
+        out_p[mask] = mapped
+        return out_p, dirs, mask
+
+
+class SealAnchorMapper(SealMapper):
+    """control point (anchor) tool (seal_utils.py:456-570): drag the surface around `mean(raw)` by `translation`; the samples in
+    a cone from the anchor disc (`radius`) to the moved anchor are carried back towards the plane of `raw`, then scaled by
+    `scale` about the anchor.  Config keys: `raw`, `translation`, `radius`, `scale`, optional `hsv` / `rgb` / `rgbLightOffset`.
+    The edit region is the oriented box of a uv-sphere of 1.1 radius around the anchor, swept by -0.1 translation, and the
+    moved anchor (1.1 translation)."""
+
+    def __init__(self, seal_config):
+        self.config = seal_config
+        t = np.asarray(seal_config["translation"], dtype=np.float64)
+        raw = np.asarray(seal_config["raw"], dtype=np.float64)
+        anchor = raw.mean(0)
+        radius = float(seal_config["radius"])
+        normal, point = fit_plane(raw)
+        moved = anchor + t
+        projected_moved = moved + ((point - moved) @ normal) / (normal @ normal) * normal  # skspatial Plane.project_point
+        v_offset = projected_moved - anchor
+        v_h = projected_moved - moved
+        sphere = uv_sphere_vertices(radius * 1.1) + anchor
+        verts = oriented_box_vertices(np.vstack([sphere, anchor + 1.1 * t, sphere - 0.1 * t]))
+        bounds = np.stack([verts.min(0), verts.max(0)])
+        self.map_data = {
+            "force_fill_bound": torch.tensor(bounds, dtype=torch.float32),
+            "map_bound": torch.tensor(bounds, dtype=torch.float32),
+            "pose_center": torch.tensor(verts.mean(0), dtype=torch.float32),
+            "pose_radius": float(np.linalg.norm(t) * 10),
+            "v_anchor": torch.tensor(anchor, dtype=torch.float32),
+            "v_offset": torch.tensor(v_offset, dtype=torch.float32),
+            "v_h": torch.tensor(v_h, dtype=torch.float32),
+            "len_h": torch.tensor(float(np.linalg.norm(v_h)), dtype=torch.float32),
+            "radius": torch.tensor(radius, dtype=torch.float32),
+            "scale": torch.tensor(np.asarray(seal_config["scale"], dtype=np.float64) * np.ones(3), dtype=torch.float32),
+        }
+        self._color_options(seal_config)
+        # keep every point of the local pretraining lattice (seal_utils.py:493-494); a flag here, unlike the bbox tool's point
+        self.map_data["map_source"] = True
+        self.map_triangles = torch.tensor(verts[_BOX_FACES], dtype=torch.float32)
+        self.device = torch.device("cpu")
+        self._dev = {}
+
+    def _device_constants(self, device):
+        c = self._dev.get(device)
+        if c is None:
+            md = self.map_data
+            f32 = lambda k: md[k].detach().cpu().numpy().astype(np.float32).reshape(-1)
+            c = {"triangles": self.map_triangles.detach().reshape(-1).float().to(device), "n_tris": self.map_triangles.shape[0],
+                 "bounds": f32("map_bound"),
+                 # [v_anchor 3 | v_offset 3 | v_h 3 | len_h | radius | scale 3]
+                 "params": np.concatenate([f32("v_anchor"), f32("v_offset"), f32("v_h"), f32("len_h"), f32("radius"), f32("scale")])}
+            self._dev[device] = c
+        return c
+
+    def _map_native(self, points, dirs):
+        import s3d_hip
+        lead = points.shape
+        p = points.reshape(-1, 3).contiguous()
+        out_p = torch.empty_like(p)
+        mask = torch.empty(p.shape[0], dtype=torch.bool, device=p.device)
+        flag = torch.empty(1, dtype=torch.int32, device=p.device)
+        s3d_hip.SealBackend.anchor_map(p, self._device_constants(p.device), out_p, mask.view(torch.uint8), flag,
+                                       s3d_hip.active_row_limit(p.shape[0]))
+        return out_p.view(lead), dirs, mask
+
+    @torch.autocast("cuda", enabled=False)
+    def map_to_origin(self, points, dirs=None):
+        """seal_utils.py:514-570, with its two quirks: when no point of the batch passes the map mask the batch comes back
+        unchanged with that (all-false) mask; otherwise the cone mapping applies to EVERY point of the batch and the returned
+        mask is cone AND plane side, not intersected with the box mask.  `dirs` come back unchanged."""
+        if self.native and points.is_cuda and points.dtype == torch.float32 and points.shape[-1] == 3 and points.numel() > 0:
+            return self._map_native(points, dirs)
+        self.to(points.device)
+        md = self.map_data
+        mask = self.map_mask(points)
+        if not mask.any():
+            return points, dirs, mask
+        v_h, anchor, len_h, radius = md["v_h"], md["v_anchor"], md["len_h"], md["radius"]
+        projected = project_points(v_h, anchor, points)
+        to_plane = projected - points
+        plane_dist = torch.norm(to_plane, 2, 1)
+        offset_points = projected - plane_dist.unsqueeze(1) / len_h * md["v_offset"]
+        anchor_dist = torch.norm(offset_points - anchor, 2, 1)
+        in_cone = torch.logical_and(anchor_dist <= radius, plane_dist / (radius - anchor_dist) < len_h / radius * 1.1)
+        valid = torch.logical_and(in_cone, to_plane @ v_h > 0)
+        v_map = -((len_h - plane_dist[valid]) / 10)[None].T @ v_h[None] / len_h
+        mapped = (offset_points[valid] - v_map - anchor) * md["scale"] + anchor
+        out_p = points.clone()
+        out_p[valid] = mapped
+        return out_p, dirs, valid
 
 
 def get_seal_mapper(config_dict=None, config_file=None):
@@ -324,6 +577,13 @@ def get_seal_mapper(config_dict=None, config_file=None):
     if config_dict is None:
         with open(config_file) as f:
             config_dict = json.load(f)
-    if config_dict["type"] == "bbox":
+    kind = config_dict["type"]
+    if "imageConfig" in config_dict:
+        raise NotImplementedError("imageConfig: the texture remap (seal_utils.py:394-416) needs cv2 and an image file")
+    if kind == "bbox":
         return SealBBoxMapper(config_dict)
-    raise NotImplementedError(f"seal tool `{config_dict['type']}` is outside the BASELINE configs (bbox only)")
+    if kind == "brush":
+        return SealBrushMapper(config_dict)
+    if kind == "anchor":
+        return SealAnchorMapper(config_dict)
+    raise NotImplementedError(f"unknown seal tool `{kind}` (bbox, brush, anchor)")
