@@ -492,6 +492,17 @@ int s3d_ngp_mid_backward(const uint16_t* grad_color_in, const float* grad_sigma 
  * [16][B][2] fp16, the grid kernels' own layout. */
 int s3d_ngp_mid2_forward(const uint16_t* h, const float* dirs, const uint16_t* enc_color, uint32_t B, float* sigma,
                          uint16_t* color_in, const int32_t* n_valid, s3d_stream_t stream);
+/* Build extension — s3d_composite_rays_train_loss with a PER-RAY background: bg [N,3] (device, fp32) replaces the 3 host floats,
+ * and grad_bg [N,3] = d loss / d bg = (d loss / d pixel) * (1 - weights_sum) is written as well — the input of
+ * s3d_background_backward (nerf/renderer.py:316 with `bg_color = self.background(sph, rays_d)`, :159-161).  Same launches, same
+ * expressions as the constant form. */
+int s3d_composite_rays_train_loss_bg(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
+                                     uint32_t M, uint32_t N, float T_thresh, const float* gt, const float* bg,
+                                     const float* grad_loss, const float* gt_depth, float depth_weight,
+                                     float* weights_sum, float* depth, float* image, float* grad_sigmas, float* grad_rgbs,
+                                     float* grad_image, float* grad_weights_sum, float* grad_bg, float* loss, float* workspace,
+                                     s3d_stream_t stream);
+
 int s3d_ngp_mid2_backward(const uint16_t* grad_color_in, const float* grad_sigma /* or NULL */, const uint16_t* h,
                           uint32_t h_stride /* 16: h is the density network's [B, 16] output; 1: its first column [B] alone */,
                           uint32_t B, uint16_t* grad_h, uint16_t* grad_enc_color /* or NULL */, const int32_t* n_valid,
@@ -516,6 +527,30 @@ int s3d_bg_mse_backward(const float* image, const float* weights_sum, const floa
  * +-inf -> +-FLT_MAX as torch.nan_to_num(nan=0.); bg_rgb = 3 HOST floats. */
 int s3d_bg_targets(const float* image, const float* weights_sum, const float* depth, const float* bg_rgb, uint32_t N,
                    float* out_rgb, float* out_depth, s3d_stream_t stream);
+/* Build extension — s3d_bg_targets with a per-ray background bg [N,3] (device, fp32): the teacher's background model. */
+int s3d_bg_targets_rays(const float* image, const float* weights_sum, const float* depth, const float* bg, uint32_t N,
+                        float* out_rgb, float* out_depth, s3d_stream_t stream);
+/* Build extension — the NGP background model, nerf/network.py:149-163 `background(x, d)` of the reference (modules built at
+ * :74-96): rgb [N,3] = sigmoid(W1 relu(W0 [SH_4(dirs) | grid(sph)])), grid = `encoder_bg`, a 4-level 2D hash grid with 2
+ * features per level (GridEncoder.forward with bound = 1), W0 [64,24] and W1 [3,64] fp32 (the parameters; rounded to fp16 as they are read).  One launch: grid lookup (the
+ * expressions of s3d_grid_encode_forward, D = 2: the features are bit for bit its outputs), SH degree 4, both layers (fp32
+ * accumulation, fp16 rounding of each layer's output), sigmoid in fp32 rounded to fp16 (rgb holds fp16 values in fp32).
+ * sph [N,2] in [-1,1] (s3d_sph_from_ray), dirs [N,3]; table [offsets[4], 2] of `dtype`; offsets [5] (device); S = log2 of the
+ * per-level scale, H = base resolution; features [4,N,2] of `dtype` (optional): the grid features, level-major. */
+int s3d_background_forward(const float* sph, const float* dirs, const void* table, const int32_t* offsets, uint32_t N,
+                           float S, uint32_t H, int dtype, const float* w0, const float* w1, float* rgb, void* features,
+                           s3d_stream_t stream);
+/* Backward of s3d_background_forward from grad_rgb [N,3] (fp32) and the forward's rgb: the hidden layer is recomputed, the feature
+ * gradient (fp16-rounded, like the reference's autocast backward) is ADDED into grad_table [table_rows, 2] of `dtype` (NULL: a
+ * frozen table, no scatter) with the
+ * grid backward's direct atomics, grad_w0 [64,24] / grad_w1 [3,64] (fp32) are overwritten.  Two launches: the per-ray pass filing
+ * per-wave weight-gradient partials in `workspace` (s3d_background_backward_workspace_size(N) bytes), and their sum in wave order
+ * (deterministic).  found_inf (optional): set to 1 when a weight gradient or an entry of grad_table is not finite. */
+size_t s3d_background_backward_workspace_size(uint32_t N);
+int s3d_background_backward(const float* grad_rgb, const float* rgb, const float* sph, const float* dirs, const void* table,
+                            const int32_t* offsets, uint32_t table_rows, uint32_t N, float S, uint32_t H, int dtype,
+                            const float* w0, const float* w1, void* grad_table, float* grad_w0, float* grad_w1,
+                            float* found_inf, void* workspace, size_t workspace_bytes, s3d_stream_t stream);
 /* Build extension — Seal-3D's local-pretraining loss on one point chunk (SealNeRF/trainer.py:455-469: L1Loss(sigma) +
  * L1Loss(colour), means): loss = sum|sigma - gt_sigma| / n_total + sum|color - gt_color| / (3 n_total); n_total >= n is the
  * size of the whole chunk when the call sees one rank's shard of it; sigma / color (and the gradients) hold n_rows >= n rows,

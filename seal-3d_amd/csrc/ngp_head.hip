@@ -209,10 +209,12 @@ __global__ void __launch_bounds__(1024) k_bg_mse_forward(const float* __restrict
 __device__ __forceinline__ float nan_to_num0(float v) { return v != v ? 0.0f : fminf(fmaxf(v, -3.402823466e38f), 3.402823466e38f); }
 __global__ void __launch_bounds__(256) k_bg_targets(const float* __restrict__ image, const float* __restrict__ ws,
                                                     const float* __restrict__ depth, float bg0, float bg1, float bg2, uint32_t N,
-                                                    float* __restrict__ out_rgb, float* __restrict__ out_depth) {
+                                                    float* __restrict__ out_rgb, float* __restrict__ out_depth,
+                                                    const float* __restrict__ bg_ray = nullptr) {
     const uint32_t n = blockIdx.x * 256 + threadIdx.x;
     if (n >= N) return;
-    const float bg[3] = {bg0, bg1, bg2};
+    const float bg[3] = {bg_ray ? bg_ray[(size_t)n * 3] : bg0, bg_ray ? bg_ray[(size_t)n * 3 + 1] : bg1,
+                         bg_ray ? bg_ray[(size_t)n * 3 + 2] : bg2};
     const float w = 1.0f - ws[n];
 #pragma unroll
     for (int c = 0; c < 3; c++) out_rgb[(size_t)n * 3 + c] = nan_to_num0(image[(size_t)n * 3 + c] + w * bg[c]);
@@ -323,6 +325,15 @@ S3D_EXPORT int s3d_bg_targets(const float* image, const float* weights_sum, cons
     hipLaunchKernelGGL(k_bg_targets, dim3(div_up<uint32_t>(N, 256)), dim3(256), 0, as_stream(stream), image, weights_sum, depth,
                        bg_rgb[0], bg_rgb[1], bg_rgb[2], N, out_rgb, out_depth);
     return check_launch("bg_targets");
+}
+
+S3D_EXPORT int s3d_bg_targets_rays(const float* image, const float* weights_sum, const float* depth, const float* bg, uint32_t N,
+                                   float* out_rgb, float* out_depth, s3d_stream_t stream) {
+    if (N == 0) return S3D_OK;
+    S3D_REQUIRE(image && weights_sum && bg && out_rgb && (!out_depth || depth), "bg_targets_rays: null pointer");
+    hipLaunchKernelGGL(k_bg_targets, dim3(div_up<uint32_t>(N, 256)), dim3(256), 0, as_stream(stream), image, weights_sum, depth,
+                       0.0f, 0.0f, 0.0f, N, out_rgb, out_depth, bg);
+    return check_launch("bg_targets_rays");
 }
 
 S3D_EXPORT size_t s3d_l1_pair_workspace_size(void) { return (size_t)(kL1Blocks + 2) * sizeof(float); }

@@ -1098,7 +1098,8 @@ __global__ void __launch_bounds__(256) k_composite_train_loss_wave(
     uint32_t M, uint32_t N, float T_thresh, const float* __restrict__ gt, float bg0, float bg1, float bg2,
     const float* __restrict__ grad_loss, const float* __restrict__ gt_depth, float depth_weight, float* __restrict__ weights_sum,
     float* __restrict__ depth, float* __restrict__ image, float* __restrict__ grad_sigmas, float* __restrict__ grad_rgbs,
-    float* __restrict__ grad_image, float* __restrict__ grad_ws, float* __restrict__ work) {
+    float* __restrict__ grad_image, float* __restrict__ grad_ws, float* __restrict__ work,
+    const float* __restrict__ bg_ray = nullptr, float* __restrict__ grad_bg = nullptr) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n = blockIdx.x * 4 + (threadIdx.x >> 6);
     float* sq = work;
@@ -1108,7 +1109,9 @@ __global__ void __launch_bounds__(256) k_composite_train_loss_wave(
         const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num_steps = (uint32_t)rays[n * 3 + 2];
         const RayPixel px = composite_ray_fwd_wave(sigmas, rgbs, deltas, offset, num_steps, M, T_thresh, lane);
         // ngp_head.hip:k_bg_mse_forward for this ray
-        const float bg[3] = {bg0, bg1, bg2};
+        // (per-ray background [N, 3] of a background model, s3d_composite_rays_train_loss_bg: the same expressions)
+        const float bg[3] = {bg_ray ? bg_ray[(size_t)index * 3] : bg0, bg_ray ? bg_ray[(size_t)index * 3 + 1] : bg1,
+                             bg_ray ? bg_ray[(size_t)index * 3 + 2] : bg2};
         const float pix[3] = {px.r, px.g, px.b};
         const float k = *grad_loss * (2.0f / (3.0f * (float)N));
         const float w = 1.0f - px.ws;
@@ -1132,6 +1135,9 @@ __global__ void __launch_bounds__(256) k_composite_train_loss_wave(
             if (grad_image) {
                 grad_image[(size_t)index * 3] = gd[0]; grad_image[(size_t)index * 3 + 1] = gd[1]; grad_image[(size_t)index * 3 + 2] = gd[2];
                 grad_ws[index] = gw;
+            }
+            if (grad_bg) {  // d loss / d bg = d loss / d pixel * (1 - weights_sum)
+                grad_bg[(size_t)index * 3] = gd[0] * w; grad_bg[(size_t)index * 3 + 1] = gd[1] * w; grad_bg[(size_t)index * 3 + 2] = gd[2] * w;
             }
         }
         composite_ray_bwd_wave(sigmas, rgbs, deltas, n, offset, num_steps, M, N, T_thresh, gw, gd[0], gd[1], gd[2], px.r, px.g, px.b,
@@ -1700,6 +1706,26 @@ S3D_EXPORT int s3d_composite_rays_train_loss(const float* sigmas, const float* r
     hipLaunchKernelGGL(k_bg_mse_reduce, dim3(1), dim3(1024), 0, as_stream(stream), (const float*)workspace,
                        gt_depth ? (const float*)(workspace + (size_t)3 * N) : nullptr, N, depth_weight, loss);
     return check_launch("composite_rays_train_loss");
+}
+
+S3D_EXPORT int s3d_composite_rays_train_loss_bg(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
+                                                uint32_t M, uint32_t N, float T_thresh, const float* gt, const float* bg,
+                                                const float* grad_loss, const float* gt_depth, float depth_weight,
+                                                float* weights_sum, float* depth, float* image, float* grad_sigmas, float* grad_rgbs,
+                                                float* grad_image, float* grad_weights_sum, float* grad_bg, float* loss, float* workspace,
+                                                s3d_stream_t stream) {
+    if (N == 0) return S3D_OK;
+    S3D_REQUIRE(rays && weights_sum && depth && image && gt && bg && grad_bg && grad_loss && loss && workspace,
+                "composite_rays_train_loss_bg: null pointer");
+    S3D_REQUIRE(M == 0 || (sigmas && rgbs && deltas && grad_sigmas && grad_rgbs), "composite_rays_train_loss_bg: null sample buffer");
+    S3D_REQUIRE((grad_image == nullptr) == (grad_weights_sum == nullptr), "composite_rays_train_loss_bg: grad_image and "
+                "grad_weights_sum come together");
+    hipLaunchKernelGGL(k_composite_train_loss_wave, dim3(div_up<uint32_t>(N, 4)), dim3(256), 0, as_stream(stream), sigmas, rgbs, deltas,
+                       rays, M, N, T_thresh, gt, 0.0f, 0.0f, 0.0f, grad_loss, gt_depth, depth_weight, weights_sum, depth,
+                       image, grad_sigmas, grad_rgbs, grad_image, grad_weights_sum, workspace, bg, grad_bg);
+    hipLaunchKernelGGL(k_bg_mse_reduce, dim3(1), dim3(1024), 0, as_stream(stream), (const float*)workspace,
+                       gt_depth ? (const float*)(workspace + (size_t)3 * N) : nullptr, N, depth_weight, loss);
+    return check_launch("composite_rays_train_loss_bg");
 }
 
 S3D_EXPORT int s3d_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t* rays_alive, const float* rays_t,

@@ -2,6 +2,7 @@
 degree-4 SH on the view direction, bias-free nn.Linear MLPs, `trunc_exp` density, sigmoid colour."""
 import os
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -115,6 +116,52 @@ class _SealPair(Function):
                 ref.param._s3d_grad_touched = True
         return ((g_e0 if ctx.need[0] else None), g_e1, (None if stash_s is not None else gw_s),
                 (None if stash_c is not None else gw_c)) + (None,) * 6
+
+
+class _Background(Function):
+    """`background(x, d)` of nerf/network.py:149-163 (reference) on the fused kernels (csrc/background.hip): grid lookup, SH_4(d),
+    24 -> 64 -> 3 MLP and sigmoid as ONE forward launch; backward = one launch (table gradient + per-wave weight-gradient
+    partials, the hidden layer recomputed) + one small reduce.  The table gradient goes where the other GridEncoder tables put
+    theirs: the optimizer's fp16 hand-over buffer when adopted (nerf/optim.py), else autograd."""
+
+    @staticmethod
+    def forward(ctx, sph, dirs, table_param, w0, w1, enc):
+        from gridencoder.grid import _table_for_kernels
+        sph, dirs = sph.float().contiguous(), dirs.float().contiguous()
+        table = _table_for_kernels(table_param, not torch.is_grad_enabled())
+        S = float(np.log2(enc.per_level_scale))
+        rgb = torch.empty(sph.shape[0], 3, dtype=torch.float32, device=sph.device)
+        _head.background_forward(sph, dirs, table, enc.offsets, S, enc.base_resolution, w0.detach().contiguous(),
+                                 w1.detach().contiguous(), rgb)
+        ctx.save_for_backward(sph, dirs, table, w0, w1, rgb)
+        ctx.meta = (enc.offsets, S, enc.base_resolution)
+        ctx.param = table_param
+        return rgb
+
+    @staticmethod
+    def backward(ctx, g_rgb):
+        sph, dirs, table, w0, w1, rgb = ctx.saved_tensors
+        offsets, S, H = ctx.meta
+        param = ctx.param
+        stash = getattr(param, "_s3d_grad", None)
+        found_inf = None
+        if stash is not None and stash.dtype == table.dtype and stash.shape == table.shape and ctx.needs_input_grad[2]:
+            grad_table = stash
+            param._s3d_grad_touched = True
+            found_inf = getattr(param, "_s3d_found_inf", None)
+            param.__dict__.pop("_s3d_fused_arm", None)  # (no in-backward Adam here: the optimizer's step updates this table)
+        else:
+            stash = None
+            grad_table = torch.zeros_like(table) if ctx.needs_input_grad[2] else None  # (frozen table: no scatter)
+        gw0 = torch.empty(64, 24, dtype=torch.float32, device=rgb.device)
+        gw1 = torch.empty(3, 64, dtype=torch.float32, device=rgb.device)
+        _head.background_backward(g_rgb.float().contiguous(), rgb, sph, dirs, table, offsets, S, H, w0.detach().contiguous(),
+                                  w1.detach().contiguous(), grad_table, gw0, gw1, found_inf)
+        if found_inf is not None:  # (the reduce launch checked the weight gradients against the scaler's flag)
+            for w in (w0, w1):
+                w._s3d_grad_checked = found_inf
+        return (None, None, (grad_table if stash is None and ctx.needs_input_grad[2] else None),
+                gw0 if ctx.needs_input_grad[3] else None, gw1 if ctx.needs_input_grad[4] else None, None)
 
 
 class PackedWeights:
@@ -243,7 +290,8 @@ def _run_mlp(layers, h):
 
 class NeRFNetwork(NeRFRenderer):
     def __init__(self, encoding="hashgrid", encoding_dir="sphere_harmonics", num_layers=2, hidden_dim=64, geo_feat_dim=15,
-                 num_layers_color=3, hidden_dim_color=64, bound=1, log2_hashmap_size=19, **kwargs):
+                 num_layers_color=3, hidden_dim_color=64, bound=1, log2_hashmap_size=19, encoding_bg="hashgrid", num_layers_bg=2,
+                 hidden_dim_bg=64, **kwargs):
         super().__init__(bound, **kwargs)
         self.num_layers, self.hidden_dim, self.geo_feat_dim = num_layers, hidden_dim, geo_feat_dim
         self.encoder, self.in_dim = get_encoder(encoding, desired_resolution=2048 * bound,
@@ -257,7 +305,11 @@ class NeRFNetwork(NeRFRenderer):
         self.color_net = _mlp([self.in_dim_dir + geo_feat_dim + self.in_dim_color]
                               + [hidden_dim_color] * (num_layers_color - 1) + [3])
         if self.bg_radius > 0:
-            raise NotImplementedError("background model (bg_radius > 0) is outside the BASELINE configs")
+            # background model (nerf/network.py:74-96): a much smaller 2D hash grid on the ray's sphere coordinates + SH_4(d)
+            self.num_layers_bg, self.hidden_dim_bg = num_layers_bg, hidden_dim_bg
+            self.encoder_bg, self.in_dim_bg = get_encoder(encoding_bg, input_dim=2, num_levels=4, log2_hashmap_size=19,
+                                                          desired_resolution=2048)
+            self.bg_net = _mlp([self.in_dim_bg + self.in_dim_dir] + [hidden_dim_bg] * (num_layers_bg - 1) + [3])
         self.register_buffer("_eye_hidden", torch.eye(hidden_dim), persistent=False)  # (not a checkpoint key)
         self._packs = None
         if (num_layers == 2 and hidden_dim == 64 and geo_feat_dim == 15 and self.in_dim == 32 and num_layers_color == 3
@@ -377,6 +429,26 @@ class NeRFNetwork(NeRFRenderer):
             rgbs[mask] = self._rgb(x[mask], d[mask], geo_feat[mask]).to(rgbs.dtype)
         return rgbs
 
+    fused_background = os.environ.get("S3D_FUSED_BG", "1") != "0"  # tests / A-B runs: False = the reference's op sequence
+
+    def _can_fuse_bg(self, x):
+        enc = self.encoder_bg
+        return (self.fused_mlp and self.fused_background and x.is_cuda and x.dim() == 2 and x.shape[1] == 2 and x.shape[0] > 0
+                and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.float16
+                and self.num_layers_bg == 2 and self.hidden_dim_bg == 64 and getattr(self.encoder_dir, "degree", None) == 4
+                and getattr(enc, "input_dim", 0) == 2 and getattr(enc, "num_levels", 0) == 4 and getattr(enc, "level_dim", 0) == 2
+                and getattr(enc, "gridtype", None) == "hash" and not getattr(enc, "align_corners", True)
+                and getattr(enc, "interpolation", None) == "linear")
+
+    def background(self, x, d):
+        """x [N, 2]: the ray's sphere coordinates in [-1, 1] (raymarching.sph_from_ray), d [N, 3] -> rgb [N, 3]"""
+        if self._can_fuse_bg(x):
+            return _Background.apply(x, d, self.encoder_bg.embeddings, self.bg_net[0].weight, self.bg_net[1].weight, self.encoder_bg)
+        h = torch.cat([self.encoder_dir(d), self.encoder_bg(x)], dim=-1)
+        return torch.sigmoid(_run_mlp(self.bg_net, h))
+
     def get_params(self, lr):
         groups = [self.encoder, self.sigma_net, self.encoder_color, self.encoder_dir, self.color_net]
+        if self.bg_radius > 0:
+            groups += [self.encoder_bg, self.bg_net]
         return [{"params": g.parameters(), "lr": lr} for g in groups]

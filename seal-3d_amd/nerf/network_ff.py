@@ -64,6 +64,8 @@ class NeRFNetwork(NeRFRenderer):
     def __init__(self, encoding="hashgrid", encoding_dir="sphere_harmonics", num_layers=2, hidden_dim=64, geo_feat_dim=15,
                  num_layers_color=3, hidden_dim_color=64, bound=1, **kwargs):
         super().__init__(bound, **kwargs)
+        if self.bg_radius > 0:  # (main_nerf.py:86 of the reference: the FFMLP network has no background model)
+            raise NotImplementedError("network_ff: background model (bg_radius > 0) is not supported")
         self.num_layers, self.hidden_dim, self.geo_feat_dim = num_layers, hidden_dim, geo_feat_dim
         self.encoder, self.in_dim = get_encoder(encoding, desired_resolution=2048 * bound)
         self.sigma_net = FFMLP(input_dim=self.in_dim, output_dim=1 + geo_feat_dim, hidden_dim=hidden_dim,

@@ -196,7 +196,16 @@ class NeRFRenderer(nn.Module):
             if self.density_scale != 1:  # (x1 is the identity: skip the pass over [M])
                 sigmas = self.density_scale * sigmas
             fused = kwargs.get("fused_loss")  # (nerf/trainer.py: the criterion and its gradient inside the compositing launch)
-            if (fused is not None and kwargs.get("defer_background", False) and not torch.is_tensor(bg_color)
+            # a background model's per-ray colours [N, 3] take the same launch in its per-ray form, which also hands out their
+            # gradient (raymarching.composite_rays_train_loss_bg)
+            bg_model = (self.bg_radius > 0 and torch.is_tensor(bg_color) and bg_color.shape == (N, 3)
+                        and hasattr(raymarching.raymarching._backend, "composite_rays_train_loss_bg"))
+            if (fused is not None and kwargs.get("defer_background", False) and bg_model and sigmas.is_cuda
+                    and fused.get("expected_grad") is not None and getattr(raymarching.raymarching._backend, "_composite_path", 0) == 0):
+                results["loss"], weights_sum, depth, image = raymarching.composite_rays_train_loss_bg(
+                    sigmas, rgbs, deltas, rays, T_thresh, fused["gt"], bg_color, fused["expected_grad"], fused.get("workspace"),
+                    fused.get("gt_depth"), fused.get("depth_weight", 1.0), not lean)
+            elif (fused is not None and kwargs.get("defer_background", False) and not torch.is_tensor(bg_color)
                     and sigmas.is_cuda and fused.get("expected_grad") is not None
                     # (the one-launch composite + criterion exists on the product's composite path only: an A/B run on
                     #  another path takes the unfused sequence below instead of failing)
@@ -209,8 +218,9 @@ class NeRFRenderer(nn.Module):
             else:
                 weights_sum, depth, image = raymarching.composite_rays_train(sigmas, rgbs, deltas, rays, T_thresh,
                                                                              *(() if not lean else (False,)))
-            if kwargs.get("defer_background", False) and not torch.is_tensor(bg_color):
-                # the caller composites the background inside its fused loss kernel (nerf/trainer.py:bg_mse_loss)
+            if kwargs.get("defer_background", False) and (not torch.is_tensor(bg_color) or bg_model):
+                # the caller composites the background inside its fused loss kernel (nerf/trainer.py:bg_mse_loss; a background
+                # model's per-ray colours: the loss launch above, or the per-ray target kernel of sealnerf/trainer.py)
                 results["premultiplied"] = True
                 results["bg_color"] = bg_color
             else:

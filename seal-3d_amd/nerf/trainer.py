@@ -58,7 +58,9 @@ def render_loss(out, gt_rgb, expected_grad=None, gt_depth=None, depth_weight=1.0
     kernel when the renderer deferred the background (`expected_grad`: see _BgMse.forward)"""
     if "loss" in out:  # the renderer's compositing launch formed the criterion itself (Trainer._fused_loss -> render(fused_loss=...))
         return out["loss"]
-    if out.get("premultiplied", False):
+    if out.get("premultiplied", False) and torch.is_tensor(out["bg_color"]):  # (a background model's colours, unfused criterion)
+        out = dict(out, image=out["image"] + (1 - out["weights_sum"]).unsqueeze(-1) * out["bg_color"].view(out["image"].shape))
+    elif out.get("premultiplied", False):
         bg = out["bg_color"]
         bg = (float(bg),) * 3 if not isinstance(bg, (tuple, list)) else tuple(float(v) for v in bg)
         if gt_depth is not None:
@@ -214,6 +216,8 @@ class Trainer:
         starts, so their update can be applied there.  (Seal's nn.Linear `.grad`s without a pack, TensoRF's factors, data
         parallelism: the separate update as before.)"""
         opt, sc = self.optimizer, self.scaler
+        if getattr(self.model, "bg_radius", 0) > 0:
+            return 0  # (the background model's backward is not ordered behind the tables': their updates stay in step())
         if not (self.fuse_table_updates and self.native_optim and self.dist is None and hasattr(opt, "arm_fused_tables")
                 and hasattr(sc, "_checked_at_source")):
             return 0

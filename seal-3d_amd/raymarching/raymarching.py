@@ -27,7 +27,7 @@ def _zeros_332(M, dtype, device):
     return flat[:3 * M].view(M, 3), flat[3 * M:6 * M].view(M, 3), flat[6 * M:].view(M, 2)
 
 __all__ = ["near_far_from_aabb", "sph_from_ray", "morton3D", "morton3D_invert", "packbits", "march_rays_train",
-           "composite_rays_train", "composite_rays_train_loss", "march_rays", "composite_rays", "compact_rays_alive"]
+           "composite_rays_train", "composite_rays_train_loss", "composite_rays_train_loss_bg", "march_rays", "composite_rays", "compact_rays_alive"]
 
 
 def _on_device(t):
@@ -302,6 +302,74 @@ class _CompositeRaysTrainLoss(Function):
         _backend.composite_rays_train_backward(gw.contiguous(), gi.contiguous(), sigmas, rgbs, deltas, rays, weights_sum, image, M, N,
                                                T_thresh, grad_sigmas, grad_rgbs)
         return (grad_sigmas, grad_rgbs) + none
+
+
+class _CompositeRaysTrainLossBg(Function):
+    """_CompositeRaysTrainLoss with a per-ray background `bg` [N,3] — the output of a background model (nerf/renderer.py:159-161,
+    316) — that receives a gradient as well (seal3d_hip.h: s3d_composite_rays_train_loss_bg, same launches)."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, sigmas, rgbs, deltas, rays, T_thresh, gt, bg, expected_grad, workspace=None, gt_depth=None, depth_weight=1.0,
+                zero_grads=True):
+        sigmas, rgbs, deltas = sigmas.float().contiguous(), rgbs.float().contiguous(), deltas.contiguous()
+        gt = gt.float().contiguous().view(-1, 3)
+        bg = bg.float().contiguous().view(-1, 3)
+        M, N = sigmas.shape[0], rays.shape[0]
+        dev = sigmas.device
+        weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
+        depth = torch.empty(N, dtype=torch.float32, device=dev)
+        image = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        flat = (torch.zeros if zero_grads else torch.empty)(4 * M, dtype=torch.float32, device=dev)
+        grad_sigmas, grad_rgbs = flat[:M], flat[M:].view(M, 3)
+        grad_bg = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        if workspace is None:
+            workspace = torch.empty(4 * N, dtype=torch.float32, device=dev)
+        if gt_depth is not None:
+            gt_depth = gt_depth.float().contiguous().view(-1)
+        _backend.composite_rays_train_loss_bg(sigmas, rgbs, deltas, rays, M, N, T_thresh, gt, bg, expected_grad, weights_sum, depth,
+                                              image, grad_sigmas, grad_rgbs, grad_bg, loss, workspace, gt_depth=gt_depth,
+                                              depth_weight=float(depth_weight))
+        ctx.pre = (grad_sigmas, grad_rgbs, grad_bg, expected_grad.data_ptr(), expected_grad._version)
+        ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, image, gt, bg)
+        ctx.dims = (M, N, T_thresh)
+        ctx.set_materialize_grads(False)
+        return loss, weights_sum, depth, image
+
+    @staticmethod
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, g_loss, g_ws, g_depth, g_image):
+        none = (None,) * 4
+        if g_loss is None and g_ws is None and g_image is None:
+            return (None,) * 12
+        if (g_ws is None and g_image is None and g_loss is not None and g_loss.dtype == torch.float32
+                and g_loss.data_ptr() == ctx.pre[3] and g_loss._version == ctx.pre[4]):
+            return (ctx.pre[0], ctx.pre[1]) + none + (ctx.pre[2],) + (None,) * 5  # (the announced upstream gradient)
+        sigmas, rgbs, deltas, rays, weights_sum, image, gt, bg = ctx.saved_tensors
+        M, N, T_thresh = ctx.dims
+        gi, gw, gb = torch.zeros_like(image), torch.zeros_like(weights_sum), torch.zeros_like(bg)
+        if g_loss is not None:  # (the MSE's gradient, as s3d_bg_mse_backward forms it, with a per-ray background)
+            w = (1 - weights_sum).unsqueeze(-1)
+            k = g_loss.float() * (2.0 / (3.0 * N)) * ((image + w * bg) - gt)
+            gi, gw, gb = k, -(k * bg).sum(-1), k * w
+        if g_image is not None:
+            gi = gi + g_image
+        if g_ws is not None:
+            gw = gw + g_ws
+        flat = torch.zeros(4 * M, dtype=torch.float32, device=sigmas.device)
+        grad_sigmas, grad_rgbs = flat[:M], flat[M:].view(M, 3)
+        _backend.composite_rays_train_backward(gw.contiguous(), gi.contiguous(), sigmas, rgbs, deltas, rays, weights_sum, image, M, N,
+                                               T_thresh, grad_sigmas, grad_rgbs)
+        return (grad_sigmas, grad_rgbs) + none + (gb,) + (None,) * 5
+
+
+def composite_rays_train_loss_bg(sigmas, rgbs, deltas, rays, T_thresh, gt, bg, expected_grad, workspace=None, gt_depth=None,
+                                 depth_weight=1.0, zero_grads=True):
+    if not hasattr(_backend, "composite_rays_train_loss_bg"):
+        raise RuntimeError("composite_rays_train_loss_bg: the active raymarching backend has no fused loss launch")
+    return _CompositeRaysTrainLossBg.apply(sigmas, rgbs, deltas, rays, T_thresh, gt, bg, expected_grad, workspace, gt_depth,
+                                           depth_weight, zero_grads)
 
 
 def _head():

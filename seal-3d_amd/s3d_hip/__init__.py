@@ -47,6 +47,8 @@ EXPORTS = [
     "s3d_vm_backward_max_bins", "s3d_vm_backward_keys", "s3d_vm_backward_bins_workspace_size", "s3d_vm_backward_bins",
     "s3d_vm_backward_stage_bytes", "s3d_vm_transpose_factors",
     "s3d_vm_features_backward", "s3d_vm_color_forward", "s3d_vm_color_backward",
+    "s3d_composite_rays_train_loss_bg", "s3d_bg_targets_rays",
+    "s3d_background_forward", "s3d_background_backward_workspace_size", "s3d_background_backward",
 ]
 
 
@@ -76,7 +78,7 @@ def lib():
                      "s3d_ffmlp_backward_workspace_size", "s3d_grid_encode_backward_workspace_size",
                      "s3d_grid_encode_backward_control_size", "s3d_l1_pair_workspace_size",
                      "s3d_sweep_update_workspace_size", "s3d_vm_backward_bins_workspace_size", "s3d_vm_backward_stage_bytes",
-                     "s3d_weighted_abs_sum_workspace_size"):
+                     "s3d_weighted_abs_sum_workspace_size", "s3d_background_backward_workspace_size"):
             getattr(l, name).restype = C.c_size_t
         l.s3d_vm_backward_max_bins.restype = C.c_uint32
         l.s3d_grid_level_scales.restype = None
@@ -416,6 +418,32 @@ class RaymarchingBackend:
                                                    _p(grad_loss), _p(gt_depth), _f(depth_weight), _p(weights_sum), _p(depth), _p(image),
                                                    _p(grad_sigmas), _p(grad_rgbs), _p(grad_image), _p(grad_weights_sum), _p(loss),
                                                    _p(workspace), _stream()), "composite_rays_train_loss")
+
+    @staticmethod
+    def composite_rays_train_loss_bg(sigmas, rgbs, deltas, rays, M, N, T_thresh, gt, bg, grad_loss, weights_sum, depth, image,
+                                     grad_sigmas, grad_rgbs, grad_bg, loss, workspace, gt_depth=None, depth_weight=1.0,
+                                     grad_image=None, grad_weights_sum=None):
+        """composite_rays_train_loss with a per-ray background bg [N,3] (device) and its gradient grad_bg [N,3] (seal3d_hip.h)"""
+        for t, n in ((sigmas, "sigmas"), (rgbs, "rgbs"), (deltas, "deltas"), (gt, "gt"), (bg, "bg"), (grad_bg, "grad_bg"),
+                     (grad_loss, "grad_loss"), (loss, "loss"), (workspace, "workspace"), (grad_sigmas, "grad_sigmas"),
+                     (grad_rgbs, "grad_rgbs")):
+            _need(t, torch.float32, n)
+        if (gt.numel() != 3 * N or bg.numel() != 3 * N or grad_bg.numel() != 3 * N or workspace.numel() < 4 * N
+                or grad_sigmas.numel() < M or grad_rgbs.numel() < 3 * M):
+            raise RuntimeError("composite_rays_train_loss_bg: gt / bg / grad_bg [N,3], workspace >= 4N floats, grad_sigmas [M], "
+                               "grad_rgbs [M,3]")
+        if gt_depth is not None:
+            _need(gt_depth, torch.float32, "gt_depth")
+            if gt_depth.numel() != N:
+                raise RuntimeError("composite_rays_train_loss_bg: gt_depth holds one value per ray")
+        if (grad_image is None) != (grad_weights_sum is None):
+            raise RuntimeError("composite_rays_train_loss_bg: grad_image and grad_weights_sum come together")
+        if RaymarchingBackend._composite_path != 0:
+            raise RuntimeError("composite_rays_train_loss_bg: the fused launch exists for the wave-per-ray path only")
+        _check(lib().s3d_composite_rays_train_loss_bg(_p(sigmas), _p(rgbs), _p(deltas), _p(rays), _u(M), _u(N), _f(T_thresh), _p(gt),
+                                                      _p(bg), _p(grad_loss), _p(gt_depth), _f(depth_weight), _p(weights_sum), _p(depth),
+                                                      _p(image), _p(grad_sigmas), _p(grad_rgbs), _p(grad_image), _p(grad_weights_sum),
+                                                      _p(grad_bg), _p(loss), _p(workspace), _stream()), "composite_rays_train_loss_bg")
 
     zero_fills_march_rays = True  # march_rays(zero_unfilled=True): the kernel writes the zeros of the unfilled slots itself
 
@@ -968,6 +996,58 @@ class NgpHeadBackend:
         bg = (C.c_float * 3)(*[float(v) for v in bg_rgb])
         _check(lib().s3d_bg_targets(_p(image), _p(weights_sum), _p(depth if out_depth is not None else None), bg, _u(N),
                                     _p(out_rgb), _p(out_depth), _stream()), "bg_targets")
+
+    @staticmethod
+    def bg_targets_rays(image, weights_sum, depth, bg, out_rgb, out_depth=None):
+        """bg_targets with a per-ray background bg [N,3] (device)"""
+        for t, n in ((image, "image"), (weights_sum, "weights_sum"), (bg, "bg"), (out_rgb, "out_rgb")):
+            _need(t, torch.float32, n)
+        N = image.shape[0]
+        if out_rgb.numel() != 3 * N or weights_sum.numel() != N or bg.numel() != 3 * N:
+            raise RuntimeError("bg_targets_rays: image / bg / out_rgb [N,3], weights_sum [N]")
+        if out_depth is not None:
+            _need(depth, torch.float32, "depth"); _need(out_depth, torch.float32, "out_depth")
+            if depth.numel() != N or out_depth.numel() != N:
+                raise RuntimeError("bg_targets_rays: depth / out_depth [N]")
+        _check(lib().s3d_bg_targets_rays(_p(image), _p(weights_sum), _p(depth if out_depth is not None else None), _p(bg), _u(N),
+                                         _p(out_rgb), _p(out_depth), _stream()), "bg_targets_rays")
+
+    @staticmethod
+    def background_forward(sph, dirs, table, offsets, S, H, w0, w1, rgb, features=None):
+        """the background model (seal3d_hip.h: s3d_background_forward): sph [N,2], dirs [N,3] fp32, table [rows,2] fp32/fp16,
+        offsets [5] int32, w0 [64,24] / w1 [3,64] fp32 (read as fp16) -> rgb [N,3] fp32 (+ the grid features [4,N,2] of the table's dtype)"""
+        N = sph.shape[0]
+        _need(sph, torch.float32, "sph"); _need(dirs, torch.float32, "dirs"); _need(rgb, torch.float32, "rgb")
+        _need(w0, torch.float32, "w0"); _need(w1, torch.float32, "w1"); _need(offsets, torch.int32, "offsets")
+        if (sph.shape != (N, 2) or dirs.shape != (N, 3) or rgb.shape != (N, 3) or offsets.numel() != 5 or table.dim() != 2
+                or table.shape[1] != 2 or w0.shape != (64, 24) or w1.shape != (3, 64)):
+            raise RuntimeError("background_forward: sph [N,2], dirs / rgb [N,3], offsets [5], table [rows,2], w0 [64,24], w1 [3,64]")
+        if features is not None and (features.dtype != table.dtype or features.shape != (4, N, 2)):
+            raise RuntimeError("background_forward: features [4,N,2] of the table's dtype")
+        _check(lib().s3d_background_forward(_p(sph), _p(dirs), _p(table), _p(offsets), _u(N), _f(S), _u(H), C.c_int(_dt(table)),
+                                            _p(w0), _p(w1), _p(rgb), _p(features), _stream()), "background_forward")
+
+    @staticmethod
+    def background_backward(grad_rgb, rgb, sph, dirs, table, offsets, S, H, w0, w1, grad_table, grad_w0, grad_w1, found_inf=None):
+        """backward of background_forward: ADDS the table gradient into grad_table (the table's shape and dtype; None: no table
+        gradient), overwrites
+        grad_w0 [64,24] / grad_w1 [3,64] (fp32); found_inf (optional fp32 [1]) raised for a non-finite gradient"""
+        N = sph.shape[0]
+        for t, n in ((grad_rgb, "grad_rgb"), (rgb, "rgb"), (sph, "sph"), (dirs, "dirs"), (grad_w0, "grad_w0"), (grad_w1, "grad_w1")):
+            _need(t, torch.float32, n)
+        _need(w0, torch.float32, "w0"); _need(w1, torch.float32, "w1"); _need(offsets, torch.int32, "offsets")
+        if (grad_rgb.shape != (N, 3) or rgb.shape != (N, 3) or dirs.shape != (N, 3) or offsets.numel() != 5
+                or (grad_table is not None and (grad_table.shape != table.shape or grad_table.dtype != table.dtype))
+                or table.dim() != 2 or table.shape[1] != 2
+                or grad_w0.shape != (64, 24) or grad_w1.shape != (3, 64) or w0.shape != (64, 24) or w1.shape != (3, 64)):
+            raise RuntimeError("background_backward: shapes as background_forward, grad_table like table, grad_w0 [64,24], grad_w1 [3,64]")
+        if found_inf is not None:
+            _need(found_inf, torch.float32, "found_inf")
+        nb = int(lib().s3d_background_backward_workspace_size(_u(N)))
+        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=sph.device)
+        _check(lib().s3d_background_backward(_p(grad_rgb), _p(rgb), _p(sph), _p(dirs), _p(table), _p(offsets), _u(table.shape[0]), _u(N),
+                                             _f(S), _u(H), C.c_int(_dt(table)), _p(w0), _p(w1), _p(grad_table), _p(grad_w0),
+                                             _p(grad_w1), _p(found_inf), _p(ws), C.c_size_t(nb), _stream()), "background_backward")
 
     _l1_ws = {}
 

@@ -399,6 +399,12 @@ class SealSteps:
             rgb = out_rgb if out_rgb is not None else torch.empty(n, 3, device=rays_o.device)
             dep = out_depth if out_depth is not None else torch.empty(n, device=rays_o.device)
             bg = out["bg_color"]
+            if torch.is_tensor(bg):  # (the teacher's background model: per-ray colours)
+                s3d_hip.NgpHeadBackend.bg_targets_rays(out["image"].reshape(-1, 3).float().contiguous(),
+                                                       out["weights_sum"].reshape(-1).float().contiguous(),
+                                                       out["depth"].reshape(-1).float().contiguous(), bg.reshape(-1, 3).float().contiguous(),
+                                                       rgb, dep)
+                return rgb.view(out["image"].shape), dep.view(out["depth"].shape)
             bg = (float(bg),) * 3 if not isinstance(bg, (tuple, list)) else tuple(float(v) for v in bg)
             s3d_hip.NgpHeadBackend.bg_targets(out["image"].reshape(-1, 3).float().contiguous(), out["weights_sum"].reshape(-1).float().contiguous(),
                                               out["depth"].reshape(-1).float().contiguous(), bg, rgb, dep)
