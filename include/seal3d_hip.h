@@ -668,6 +668,34 @@ int s3d_step_epilogue(float* scale, int32_t* growth_tracker, float* found_inf, f
                       int32_t growth_interval, float* adam_step, const float* loss, int32_t* counter, float* loss_ring,
                       int32_t* counter_ring, int32_t* cursor, int32_t ring, int32_t loss_slots, s3d_stream_t stream);
 
+/* ------------------------------------------------------------------ training-ray sampling (build extension)
+ * nerf/utils.py:92-114 `get_rays(..., N, error_map)` on the device, for one training batch in one launch.  index [B] (device
+ * int64): the image of each batch row.  error_map [n_img, 128*128] (fp32, 16-byte aligned): weighted draw of N <= 16,384 cells
+ * per row without replacement (an exponential race: key w / -log(u), the N largest keys; winners in ascending cell order, at the
+ * threshold key the lower cell wins; when fewer than N cells are positive the rest are zero-weight cells by index, where
+ * torch.multinomial raises), each jittered to a pixel with (cell * s + u * s).long().clamp(max = H|W - 1), s = H|W / 128.
+ * error_map NULL: the reference's uniform randint pixels, shared by the rows.  poses [n_img,4,4]; intrinsics: 4 HOST floats
+ * fx, fy, cx, cy.  Outputs [B,N,*]: rays_o, rays_d (get_rays' expression), inds (int64), inds_coarse (int64, with a map), and
+ * (optional) gt [B,N,3] fp32 gathered from images [n_img,H,W,3] (images_dtype fp32 / fp16) and gt_depth [B,N] from depths
+ * [n_img,H*W].  Randomness: a counter hash of (seed, ctl[0], image, cell); ctl [2] int32 on the device = {step, 0}: the last
+ * workgroup advances ctl[0], so a captured launch draws fresh cells on every replay.  Test entry: u_keys [B,16384] in (0, 1]
+ * and u_fine [B,N,2] in [0, 1) (both, with a map) replace the hash and leave ctl alone.  out_index [B] (optional) receives a
+ * copy of index: the static index buffer a captured step's s3d_error_map_update reads. */
+int s3d_sample_train_rays(const float* error_map, const int64_t* index, uint32_t B, uint32_t N, uint32_t n_img, uint32_t H,
+                          uint32_t W, const float* poses, const float* intrinsics, const void* images, int images_dtype,
+                          const float* depths, uint32_t seed, int32_t* ctl, const float* u_keys, const float* u_fine,
+                          float* rays_o, float* rays_d, float* gt, float* gt_depth, int64_t* inds, int64_t* inds_coarse,
+                          int64_t* out_index, s3d_stream_t stream);
+/* Build extension — the error-map EMA of nerf/utils.py:506-528 after a step's loss: for ray r = (b, n) of the batch,
+ * err = mean_c((image + (1 - weights_sum) * bg - gt)^2) (+ depth_weight * mean_r |nan_to_num(depth) - gt_depth|, reduced in a
+ * fixed order inside the launch), then error_map[index[b], inds_coarse[r]] = 0.1 old + 0.9 err.  bg: 3 HOST floats bg_rgb or a
+ * per-ray bg_rays [B*N,3] (device); weights_sum NULL (and no bg): image is the composited prediction.  Rows of `index` must be
+ * distinct and every row of inds_coarse free of duplicates (as the sampler returns them): the scatter is race-free.  A
+ * non-finite err leaves the old value in place (where the reference writes it and multinomial later raises). */
+int s3d_error_map_update(float* error_map, uint32_t n_img, const int64_t* index, const int64_t* inds_coarse, uint32_t B, uint32_t N,
+                         const float* image, const float* weights_sum, const float* gt, const float* bg_rgb, const float* bg_rays,
+                         const float* depth, const float* gt_depth, float depth_weight, s3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

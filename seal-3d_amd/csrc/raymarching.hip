@@ -54,16 +54,7 @@ __device__ __forceinline__ uint32_t morton3d_invert(uint32_t x) {
 }
 
 // ---------------------------------------------------------------- small utilities
-// counter-based per-ray jitter for a graph-replayed step: u01(key, step, ray) with the step number read from device memory
-// (torch.rand inside a captured graph costs its own kernel plus two seed/offset fills before every replay)
-__device__ __forceinline__ uint32_t pcg_hash(uint32_t v) {
-    v = v * 747796405u + 2891336453u;
-    const uint32_t w = ((v >> ((v >> 28u) + 4u)) ^ v) * 277803737u;
-    return (w >> 22u) ^ w;
-}
-__device__ __forceinline__ float ray_noise(uint32_t key, uint32_t step, uint32_t n) {
-    return (float)(pcg_hash(pcg_hash(key ^ (step * 0x9E3779B9u)) + n) >> 8) * (1.0f / 16777216.0f);  // [0, 1)
-}
+// (counter-based per-ray jitter of a graph-replayed step: ray_noise, s3d_common.hpp)
 
 // Rows of a padded sample batch that no ray fills but the consumers still process (seal3d_hip.h: `n_valid` rounds the sample
 // count up to 128 rows; a ray that does not fit the budget M leaves [offset, M) empty).  The training kernels write them as

@@ -1,0 +1,334 @@
+// raysample.hip — error-map importance sampling of training rays (nerf/utils.py:102-114 `get_rays(error_map=...)`, the
+// EMA update of nerf/utils.py:506-528) for gfx950.
+//
+//  * s3d_sample_train_rays: one workgroup per batch row, 1,024 threads x 16 cells = the 128 x 128 map of that row's image.
+//    Weighted sampling without replacement as an exponential race: cell c gets key w_c / E_c, E_c = -log(u_c) ~ Exp(1), and
+//    the N largest keys win (torch.multinomial(replacement=False) draws from the same distribution).  The keys stay in
+//    VGPRs; a radix select over their bits (4 passes of 8 bits, per-wave LDS histograms) finds the N-th largest key, and one
+//    block scan emits the winners in ascending cell order — at the threshold key the lower cell index wins.  Zero-weight
+//    cells have key 0: when fewer than N cells are positive the rest is filled with zero-weight cells by index (where
+//    torch.multinomial raises).  Each winner's thread then applies the fine perturb, forms the ray (the get_rays expression
+//    and the pose rotation) and gathers its target colour / depth straight into the caller's buffers.  Without a map the
+//    same launch draws the reference's uniform randint pixels.  The step number of the counter-based hash is read from
+//    device memory and advanced by the last workgroup to finish, so a captured launch draws fresh cells on every replay.
+//  * s3d_error_map_update: one workgroup; the depth term's batch mean is reduced first in a fixed order, then every ray's
+//    error (the torch route's float expressions) is folded into its cell as 0.1 old + 0.9 err.  A non-finite error leaves the
+//    cell's old value in place.
+#include "s3d_common.hpp"
+
+#include <math.h>
+
+namespace s3d {
+namespace {
+
+constexpr uint32_t kCells = 128 * 128;
+constexpr uint32_t kSampleBlock = 1024;
+constexpr uint32_t kPerThread = kCells / kSampleBlock;  // 16
+constexpr uint32_t kWaves = kSampleBlock / 64;           // 16
+constexpr uint32_t kUpdateBlock = 1024;
+static_assert(kPerThread == 16, "16 cells per thread");
+
+// Exp(1) variate from a full 32-bit word: -log(u) for u in the lower half, -log1p(-(1 - u)) in the upper one, so that the
+// key keeps ~24 significant bits of randomness across the whole range (a 24-bit uniform would tie often among 16,384 cells)
+__device__ __forceinline__ float exp_variate(uint32_t h) {
+    if (h < 0x80000000u) return 0.0f - logf(((float)h + 0.5f) * 0x1p-32f);
+    return 0.0f - log1pf(0.0f - ((float)(0xFFFFFFFFu - h) + 0.5f) * 0x1p-32f);
+}
+
+// key bits of one cell: w / E (correctly rounded, -ffp-contract=off) as an unsigned word, monotone for keys >= 0; weights
+// that are not positive (and a NaN key) rank as 0, below every positive key
+__device__ __forceinline__ uint32_t key_bits(float w, float E) {
+    if (!(w > 0.0f)) return 0u;
+    const float k = w / E;
+    return k >= 0.0f ? __float_as_uint(k) : 0u;
+}
+
+// block-wide exclusive scan of one word per thread (1,024 threads), total in *total
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_wave, uint32_t* total) {
+    const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63u;
+    const uint32_t incl = wave_incl_scan(v);
+    if (lane == 63u) s_wave[wave] = incl;
+    __syncthreads();
+    if (t < 64) {
+        const uint32_t x = t < kWaves ? s_wave[t] : 0u;
+        const uint32_t xi = wave_incl_scan(x);
+        if (t < kWaves) s_wave[kWaves + t] = xi - x;
+        if (t == kWaves - 1) *total = xi;
+    }
+    __syncthreads();
+    return s_wave[kWaves + wave] + incl - v;
+}
+
+struct SampleArgs {
+    const float* error_map;  // [n_img, 16384] or NULL (uniform pixels)
+    const int64_t* index;    // [B] image of each batch row
+    const float* poses;      // [n_img, 4, 4]
+    const void* images;      // [n_img, H, W, 3] fp32 / fp16 or NULL
+    const float* depths;     // [n_img, H * W] or NULL
+    const float* u_keys;     // [B, 16384] or NULL (test entry: explicit uniforms of the keys)
+    const float* u_fine;     // [B, N, 2] or NULL (test entry: explicit uniforms of the fine perturb)
+    int32_t* ctl;            // {step, arrivals} or NULL (explicit uniforms)
+    float* rays_o;
+    float* rays_d;
+    float* gt;
+    float* gt_depth;
+    int64_t* inds;
+    int64_t* inds_coarse;
+    int64_t* out_index;      // [B] copy of index or NULL (the static index buffer of a captured step)
+    uint32_t N, n_img, H, W, seed, img_f16;
+    float fx, fy, cx, cy, sx, sy;
+};
+
+// the ray of pixel `pix` into row b's slot n (get_rays: pixel centre, normalised direction, cam2world rotation) + targets
+__device__ __forceinline__ void emit_ray(const SampleArgs& a, uint32_t b, uint32_t img, uint32_t n, uint32_t pix,
+                                         const float* __restrict__ pose) {
+    const size_t o = (size_t)b * a.N + n;
+    const float i = (float)(pix % a.W) + 0.5f, j = (float)(pix / a.W) + 0.5f;
+    const float x = (i - a.cx) / a.fx * 1.0f, y = (j - a.cy) / a.fy * 1.0f, z = 1.0f;
+    const float nrm = sqrtf(x * x + y * y + z * z);
+    const float dx = x / nrm, dy = y / nrm, dz = z / nrm;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        a.rays_d[o * 3 + k] = dx * pose[k * 4] + dy * pose[k * 4 + 1] + dz * pose[k * 4 + 2];
+        a.rays_o[o * 3 + k] = pose[k * 4 + 3];
+    }
+    a.inds[o] = (int64_t)pix;
+    const size_t src = (size_t)img * a.H * a.W + pix;
+    if (a.images && a.gt) {
+        if (a.img_f16) {
+            const __half* im = reinterpret_cast<const __half*>(a.images);
+#pragma unroll
+            for (int k = 0; k < 3; k++) a.gt[o * 3 + k] = __half2float(im[src * 3 + k]);
+        } else {
+            const float* im = reinterpret_cast<const float*>(a.images);
+#pragma unroll
+            for (int k = 0; k < 3; k++) a.gt[o * 3 + k] = im[src * 3 + k];
+        }
+    }
+    if (a.depths && a.gt_depth) a.gt_depth[o] = a.depths[src];
+}
+
+__global__ void __launch_bounds__(kSampleBlock) k_sample_train_rays(SampleArgs a) {
+    __shared__ uint32_t s_hist[kWaves * 256];
+    __shared__ uint32_t s_scan[2 * kWaves];
+    __shared__ uint32_t s_sel[4];  // {digit, remaining k, total, step}
+    const uint32_t t = threadIdx.x, b = blockIdx.x, wave = t >> 6;
+    const uint32_t img = (uint32_t)a.index[b];
+    if (t == 0) {
+        s_sel[3] = a.ctl ? (uint32_t)a.ctl[0] : 0u;
+        if (a.out_index) a.out_index[b] = (int64_t)img;
+    }
+    __syncthreads();
+    const uint32_t step = s_sel[3];
+    const float* pose = a.poses + (size_t)img * 16;
+
+    if (img >= a.n_img) {
+        // (an index outside the dataset: the row is left unwritten rather than read out of bounds)
+    } else if (!a.error_map) {
+        // uniform pixels (nerf/utils.py:98: randint(0, H*W, [N]) shared by the batch rows)
+        const uint32_t key = pcg_hash(a.seed ^ 0x5BD1E995u), HW = a.H * a.W;
+        for (uint32_t n = t; n < a.N; n += kSampleBlock) {
+            const uint32_t pix = (uint32_t)(((uint64_t)hash_u32(key, step, n) * HW) >> 32);
+            emit_ray(a, b, img, n, pix, pose);
+        }
+    } else {
+        // keys of this thread's 16 consecutive cells, in registers
+        const uint32_t c0 = t * kPerThread;
+        const float4* w4 = reinterpret_cast<const float4*>(a.error_map + (size_t)img * kCells + c0);
+        const uint32_t row_key = pcg_hash(a.seed + 0x632BE5ABu * (img + 1u));
+        uint32_t key[kPerThread];
+#pragma unroll
+        for (uint32_t q = 0; q < kPerThread / 4; q++) {
+            const float4 w = w4[q];
+            const float wv[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+            for (uint32_t r = 0; r < 4; r++) {
+                const uint32_t c = c0 + q * 4 + r;
+                const float E = a.u_keys ? 0.0f - logf(a.u_keys[(size_t)b * kCells + c]) : exp_variate(hash_u32(row_key, step, c));
+                key[q * 4 + r] = key_bits(wv[r], E);
+            }
+        }
+        // radix select of the N-th largest key: prefix/mask of the bits decided so far, k = how many keys matching the prefix
+        // are still to be taken
+        uint32_t prefix = 0, mask = 0, k = a.N;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            for (uint32_t e = t; e < kWaves * 256; e += kSampleBlock) s_hist[e] = 0u;
+            __syncthreads();
+#pragma unroll
+            for (uint32_t q = 0; q < kPerThread; q++)
+                if ((key[q] & mask) == prefix) atomicAdd(&s_hist[wave * 256 + ((key[q] >> shift) & 255u)], 1u);
+            __syncthreads();
+            // thread t < 256 owns digit 255 - t: the inclusive scan over t counts the keys with a digit >= its own
+            uint32_t cnt = 0;
+            if (t < 256) {
+#pragma unroll
+                for (uint32_t w = 0; w < kWaves; w++) cnt += s_hist[w * 256 + (255u - t)];
+            }
+            uint32_t incl = 0;
+            if (t < 256) {
+                incl = wave_incl_scan(cnt);
+                if ((t & 63u) == 63u) s_scan[t >> 6] = incl;
+            }
+            __syncthreads();
+            if (t < 256) {
+                for (uint32_t w = 0; w < (t >> 6); w++) incl += s_scan[w];
+                const uint32_t excl = incl - cnt;
+                if (excl < k && incl >= k) { s_sel[0] = 255u - t; s_sel[1] = k - excl; }
+            }
+            __syncthreads();
+            prefix |= s_sel[0] << shift;
+            mask |= 255u << shift;
+            k = s_sel[1];
+            __syncthreads();
+        }
+        // prefix = the threshold key, k = how many of the keys equal to it are taken (the lowest cells first)
+        uint32_t n_gt = 0, n_eq = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < kPerThread; q++) { n_gt += key[q] > prefix; n_eq += key[q] == prefix; }
+        const uint32_t before = block_excl_scan((n_gt << 16) | n_eq, s_scan, &s_sel[2]);
+        uint32_t gt_before = before >> 16, eq_before = before & 0xFFFFu;
+        const uint32_t fine_key = pcg_hash(row_key ^ 0xA511E9B3u);
+#pragma unroll
+        for (uint32_t q = 0; q < kPerThread; q++) {
+            const bool gt = key[q] > prefix, eq = key[q] == prefix;
+            if (gt || (eq && eq_before < k)) {
+                const uint32_t n = gt_before + (eq_before < k ? eq_before : k);
+                if (n < a.N) {
+                    const uint32_t c = c0 + q;
+                    float ux, uy;
+                    if (a.u_fine) {
+                        ux = a.u_fine[((size_t)b * a.N + n) * 2];
+                        uy = a.u_fine[((size_t)b * a.N + n) * 2 + 1];
+                    } else {
+                        ux = (float)(hash_u32(fine_key, step, 2u * c) >> 8) * (1.0f / 16777216.0f);
+                        uy = (float)(hash_u32(fine_key, step, 2u * c + 1u) >> 8) * (1.0f / 16777216.0f);
+                    }
+                    // (inds_x * sx + rand * sx).long().clamp(max=H - 1), the same for y (nerf/utils.py:108-111)
+                    const float fxv = (float)(c >> 7) * a.sx + ux * a.sx, fyv = (float)(c & 127u) * a.sy + uy * a.sy;
+                    uint32_t px = (uint32_t)(int64_t)fxv, py = (uint32_t)(int64_t)fyv;
+                    px = px < a.H - 1 ? px : a.H - 1;
+                    py = py < a.W - 1 ? py : a.W - 1;
+                    a.inds_coarse[(size_t)b * a.N + n] = (int64_t)c;
+                    emit_ray(a, b, img, n, px * a.W + py, pose);
+                }
+            }
+            gt_before += gt;
+            eq_before += eq;
+        }
+    }
+    // the last workgroup to finish advances the step number (every workgroup read it above)
+    if (a.ctl) {
+        __syncthreads();
+        if (t == 0) {
+            __threadfence();
+            const int32_t arrived = atomicAdd(&a.ctl[1], 1);
+            if (arrived == (int32_t)gridDim.x - 1) {
+                __threadfence();
+                a.ctl[1] = 0;
+                a.ctl[0] = (int32_t)(step + 1u);
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ float block_sum_fixed(float v, float* s_red) {
+    // fixed-order tree over the 1,024 per-thread partial sums
+    const uint32_t t = threadIdx.x;
+    s_red[t] = v;
+    __syncthreads();
+    for (uint32_t h = kUpdateBlock / 2; h > 0; h >>= 1) {
+        if (t < h) s_red[t] = s_red[t] + s_red[t + h];
+        __syncthreads();
+    }
+    const float r = s_red[0];
+    __syncthreads();
+    return r;
+}
+
+__global__ void __launch_bounds__(kUpdateBlock)
+k_error_map_update(float* __restrict__ error_map, const int64_t* __restrict__ index, const int64_t* __restrict__ inds_coarse,
+                   uint32_t B, uint32_t N, uint32_t n_img, const float* __restrict__ image, const float* __restrict__ weights_sum,
+                   const float* __restrict__ gt, float bg0, float bg1, float bg2, const float* __restrict__ bg_rays,
+                   const float* __restrict__ depth, const float* __restrict__ gt_depth, float depth_weight) {
+    __shared__ float s_red[kUpdateBlock];
+    const uint32_t t = threadIdx.x, R = B * N;
+    float dterm = 0.0f;
+    if (depth) {
+        float acc = 0.0f;
+        for (uint32_t r = t; r < R; r += kUpdateBlock) {
+            float d = depth[r];
+            d = d != d ? 0.0f : (d == INFINITY ? 3.4028234663852886e38f : (d == -INFINITY ? -3.4028234663852886e38f : d));
+            acc += fabsf(d - gt_depth[r]);
+        }
+        dterm = depth_weight * (block_sum_fixed(acc, s_red) / (float)R);
+    }
+    for (uint32_t r = t; r < R; r += kUpdateBlock) {
+        const uint32_t b = r / N;
+        const float ws = weights_sum ? 1.0f - weights_sum[r] : 0.0f;
+        float e = 0.0f;
+        float sq[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const float bg = bg_rays ? bg_rays[(size_t)r * 3 + k] : (k == 0 ? bg0 : (k == 1 ? bg1 : bg2));
+            const float p = weights_sum ? image[(size_t)r * 3 + k] + ws * bg : image[(size_t)r * 3 + k];
+            const float d = p - gt[(size_t)r * 3 + k];
+            sq[k] = d * d;
+        }
+        e = (sq[0] + sq[1] + sq[2]) * (1.0f / 3.0f);  // (torch's mean over the channels: the sum times 1 / 3)
+        if (depth) e = e + dterm;
+        if (!isfinite(e)) continue;  // (documented deviation: one bad step must not poison the sampler)
+        const uint64_t img = (uint64_t)index[b], c = (uint64_t)inds_coarse[r];
+        if (img >= n_img || c >= kCells) continue;  // (out-of-range entries: nothing to update)
+        float* cell = error_map + img * kCells + c;
+        *cell = 0.1f * *cell + 0.9f * e;
+    }
+}
+
+}  // namespace
+}  // namespace s3d
+
+using namespace s3d;
+
+S3D_EXPORT int s3d_sample_train_rays(const float* error_map, const int64_t* index, uint32_t B, uint32_t N, uint32_t n_img,
+                                     uint32_t H, uint32_t W, const float* poses, const float* intrinsics, const void* images,
+                                     int images_dtype, const float* depths, uint32_t seed, int32_t* ctl, const float* u_keys,
+                                     const float* u_fine, float* rays_o, float* rays_d, float* gt, float* gt_depth, int64_t* inds,
+                                     int64_t* inds_coarse, int64_t* out_index, s3d_stream_t stream) {
+    S3D_REQUIRE(index && poses && intrinsics && rays_o && rays_d && inds, "s3d_sample_train_rays: null argument");
+    S3D_REQUIRE(B > 0 && N > 0 && n_img > 0 && H > 0 && W > 0, "s3d_sample_train_rays: empty batch or frame");
+    S3D_REQUIRE(images_dtype == S3D_F32 || images_dtype == S3D_F16, "s3d_sample_train_rays: images must be fp32 or fp16");
+    S3D_REQUIRE((uint64_t)H * W < (1ull << 31), "s3d_sample_train_rays: frame too large");
+    if (error_map) {
+        S3D_REQUIRE(N <= kCells, "s3d_sample_train_rays: N = %u exceeds the 16,384 cells of the map", N);
+        S3D_REQUIRE(inds_coarse, "s3d_sample_train_rays: inds_coarse is required with an error map");
+        S3D_REQUIRE((reinterpret_cast<uintptr_t>(error_map) & 15u) == 0, "s3d_sample_train_rays: error_map must be 16-byte aligned");
+        S3D_REQUIRE(ctl || (u_keys && u_fine), "s3d_sample_train_rays: needs ctl or both explicit uniform arrays");
+    } else {
+        S3D_REQUIRE(ctl, "s3d_sample_train_rays: uniform pixels need ctl");
+    }
+    SampleArgs a;
+    a.error_map = error_map; a.index = index; a.poses = poses; a.images = images; a.depths = depths;
+    a.u_keys = error_map ? u_keys : nullptr; a.u_fine = error_map ? u_fine : nullptr;
+    a.ctl = (error_map && u_keys && u_fine) ? nullptr : ctl;
+    a.rays_o = rays_o; a.rays_d = rays_d; a.gt = gt; a.gt_depth = gt_depth; a.inds = inds; a.inds_coarse = inds_coarse;
+    a.out_index = out_index;
+    a.N = N; a.n_img = n_img; a.H = H; a.W = W; a.seed = seed; a.img_f16 = images_dtype == S3D_F16;
+    a.fx = intrinsics[0]; a.fy = intrinsics[1]; a.cx = intrinsics[2]; a.cy = intrinsics[3];
+    a.sx = (float)((double)H / 128.0); a.sy = (float)((double)W / 128.0);
+    hipLaunchKernelGGL(k_sample_train_rays, dim3(B), dim3(kSampleBlock), 0, as_stream(stream), a);
+    return check_launch("k_sample_train_rays");
+}
+
+S3D_EXPORT int s3d_error_map_update(float* error_map, uint32_t n_img, const int64_t* index, const int64_t* inds_coarse, uint32_t B,
+                                    uint32_t N, const float* image, const float* weights_sum, const float* gt, const float* bg_rgb,
+                                    const float* bg_rays, const float* depth, const float* gt_depth, float depth_weight,
+                                    s3d_stream_t stream) {
+    S3D_REQUIRE(error_map && index && inds_coarse && image && gt, "s3d_error_map_update: null argument");
+    S3D_REQUIRE(B > 0 && N > 0 && N <= kCells, "s3d_error_map_update: bad batch shape");
+    S3D_REQUIRE((depth == nullptr) == (gt_depth == nullptr), "s3d_error_map_update: depth and gt_depth go together");
+    S3D_REQUIRE(weights_sum || (!bg_rgb && !bg_rays), "s3d_error_map_update: a background needs weights_sum");
+    const float b0 = bg_rgb ? bg_rgb[0] : 0.0f, b1 = bg_rgb ? bg_rgb[1] : 0.0f, b2 = bg_rgb ? bg_rgb[2] : 0.0f;
+    hipLaunchKernelGGL(k_error_map_update, dim3(1), dim3(kUpdateBlock), 0, as_stream(stream), error_map, index, inds_coarse, B, N,
+                       n_img, image, weights_sum, gt, b0, b1, b2, bg_rays, depth, gt_depth, depth_weight);
+    return check_launch("k_error_map_update");
+}

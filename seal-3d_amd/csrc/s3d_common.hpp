@@ -103,4 +103,19 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
     return v;
 }
 
+// counter-based random numbers with the step number read from device memory, so that a graph-replayed launch draws fresh
+// values (torch.rand inside a captured graph costs its own kernel plus two seed/offset fills before every replay):
+// hash_u32(key, step, n) is a full 32-bit word, ray_noise its top 24 bits as a uniform in [0, 1) (the marcher's per-ray jitter)
+__device__ __forceinline__ uint32_t pcg_hash(uint32_t v) {
+    v = v * 747796405u + 2891336453u;
+    const uint32_t w = ((v >> ((v >> 28u) + 4u)) ^ v) * 277803737u;
+    return (w >> 22u) ^ w;
+}
+__device__ __forceinline__ uint32_t hash_u32(uint32_t key, uint32_t step, uint32_t n) {
+    return pcg_hash(pcg_hash(key ^ (step * 0x9E3779B9u)) + n);
+}
+__device__ __forceinline__ float ray_noise(uint32_t key, uint32_t step, uint32_t n) {
+    return (float)(hash_u32(key, step, n) >> 8) * (1.0f / 16777216.0f);  // [0, 1)
+}
+
 }  // namespace s3d

@@ -47,13 +47,27 @@ def orbit_poses(n, seed=0, radius=LEGO_RADIUS, theta_range=(math.pi / 6, math.pi
     return poses.to(device)
 
 
-def get_rays(poses, intrinsics, H, W, N=-1, generator=None):
-    """Pixel-centre rays (nerf/utils.py:54-139 without error maps / patches).
-    poses [B,4,4] cam2world; returns dict(rays_o [B,n,3], rays_d [B,n,3], inds [B,n])."""
+def get_rays(poses, intrinsics, H, W, N=-1, error_map=None, generator=None):
+    """Pixel-centre rays (nerf/utils.py:54-139 without patches).
+    poses [B,4,4] cam2world; returns dict(rays_o [B,n,3], rays_d [B,n,3], inds [B,n]).
+    error_map [B, 128*128] (with N > 0): the reference's weighted draw of N coarse cells without replacement (nerf/utils.py:
+    102-114) — multinomial, then one uniform per ray for x, then one for y, in this order from `generator` (None: torch's
+    global generator, so that torch.manual_seed reproduces the reference) — jittered to a pixel of the cell; the dict gains
+    `inds_coarse` [B,N]."""
     device = poses.device
     B = poses.shape[0]
     fx, fy, cx, cy = [float(v) for v in intrinsics]
-    if N > 0:
+    results = {}
+    if N > 0 and error_map is not None:
+        N = min(N, H * W)
+        inds_coarse = torch.multinomial(error_map.to(device), N, replacement=False, generator=generator)  # [B, N] in [0, 128*128)
+        inds_x, inds_y = inds_coarse // 128, inds_coarse % 128
+        sx, sy = H / 128, W / 128
+        inds_x = (inds_x * sx + torch.rand(B, N, device=device, generator=generator) * sx).long().clamp(max=H - 1)
+        inds_y = (inds_y * sy + torch.rand(B, N, device=device, generator=generator) * sy).long().clamp(max=W - 1)
+        inds = inds_x * W + inds_y
+        results["inds_coarse"] = inds_coarse
+    elif N > 0:
         N = min(N, H * W)
         inds = torch.randint(0, H * W, size=[N], generator=generator).to(device)
         inds = inds.expand([B, N])
@@ -66,7 +80,8 @@ def get_rays(poses, intrinsics, H, W, N=-1, generator=None):
     dirs = dirs / torch.norm(dirs, dim=-1, keepdim=True)
     rays_d = dirs @ poses[:, :3, :3].transpose(-1, -2)
     rays_o = poses[..., :3, 3][..., None, :].expand_as(rays_d)
-    return {"rays_o": rays_o, "rays_d": rays_d, "inds": inds}
+    results.update(rays_o=rays_o, rays_d=rays_d, inds=inds)
+    return results
 
 
 def _expand_bits(v):

@@ -53,9 +53,51 @@ class _BgMse(torch.autograd.Function):
         return (g_image, g_ws) + (None,) * 6
 
 
-def render_loss(out, gt_rgb, expected_grad=None, gt_depth=None, depth_weight=1.0):
+def update_error_map(out, gt_rgb, error_map, gt_depth=None, depth_weight=1.0):
+    """nerf/utils.py:506-528: fold the step's per-ray error into the error map as 0.1 old + 0.9 err.  `error_map` =
+    (map [n, 128*128], index [B], inds_coarse [B, N]); err = mean_c((pred - gt)^2) (+ depth_weight * the batch's mean L1 depth
+    error, added to every ray as `loss += criterion_depth(...)` does).  A renderer output that defers its background (the GPU's
+    native route) is folded in by one launch of s3d_error_map_update, which composites the background itself; otherwise the
+    reference's gather / scatter sequence runs."""
+    emap, index, inds = error_map
+    index = torch.as_tensor(index, dtype=torch.int64, device=emap.device).reshape(-1)
+    inds = inds.to(emap.device).reshape(index.numel(), -1)
+    B, N = inds.shape
+    depth = None
+    if gt_depth is not None:
+        depth = torch.nan_to_num(out["depth"].detach().float(), nan=0.0).reshape(-1)
+    if out.get("premultiplied", False) and emap.is_cuda:
+        import s3d_hip
+        bg = out["bg_color"]
+        bg = bg.detach().float().reshape(-1, 3).contiguous() if torch.is_tensor(bg) else \
+            ((float(bg),) * 3 if not isinstance(bg, (tuple, list)) else tuple(float(v) for v in bg))
+        s3d_hip.RaySampleBackend.error_map_update(
+            emap, index, inds.contiguous(), out["image"].detach().float().reshape(-1, 3).contiguous(),
+            gt_rgb.detach().float().reshape(-1, 3).contiguous(), out["weights_sum"].detach().float().reshape(-1).contiguous(), bg,
+            depth.contiguous() if depth is not None else None,
+            gt_depth.detach().float().reshape(-1).contiguous() if gt_depth is not None else None, depth_weight)
+        return
+    pred = out["image"]
+    if out.get("premultiplied", False):
+        bg = out["bg_color"]
+        bg = bg.view(pred.shape) if torch.is_tensor(bg) else (bg if not isinstance(bg, (tuple, list)) else torch.tensor(bg, device=pred.device))
+        pred = pred + (1 - out["weights_sum"]).unsqueeze(-1) * bg
+    with torch.no_grad():
+        error = F.mse_loss(pred.detach().float(), gt_rgb.detach().float().view(pred.shape), reduction="none").mean(-1).view(B, N)
+        if gt_depth is not None:
+            error = error + depth_weight * F.l1_loss(depth.view(gt_depth.shape), gt_depth.float())
+        em = emap[index]  # [B, 128*128] (advanced indexing: a copy)
+        ema = 0.1 * em.gather(1, inds) + 0.9 * error.to(em.device)
+        em.scatter_(1, inds, ema)
+        emap[index] = em
+
+
+def render_loss(out, gt_rgb, expected_grad=None, gt_depth=None, depth_weight=1.0, error_map=None):
     """MSE between the rendered batch and the targets (+ Seal-3D's L1 depth term when `gt_depth` is given); uses the fused
-    kernel when the renderer deferred the background (`expected_grad`: see _BgMse.forward)"""
+    kernel when the renderer deferred the background (`expected_grad`: see _BgMse.forward).  `error_map`: (map, index,
+    inds_coarse) of an error-map batch — the step's per-ray errors are folded into the map (update_error_map)."""
+    if error_map is not None:
+        update_error_map(out, gt_rgb, error_map, gt_depth, depth_weight)
     if "loss" in out:  # the renderer's compositing launch formed the criterion itself (Trainer._fused_loss -> render(fused_loss=...))
         return out["loss"]
     if out.get("premultiplied", False) and torch.is_tensor(out["bg_color"]):  # (a background model's colours, unfused criterion)
@@ -101,6 +143,10 @@ class Trainer:
             self.rebuild_optimizer()
         self.global_step = 0
         self.epoch = 0
+        # the training set's error map (nerf/utils.py:616 `self.error_map = train_loader._data.error_map`): with it, steps that
+        # are handed `index` / `inds_coarse` fold their per-ray errors into it (update_error_map)
+        self.error_map = None
+        self._em_batch = None
         self.stats = {"loss": [], "valid_loss": [], "results": [], "checkpoints": [], "best_result": None}
         if dist is not None:
             dist.register(model)  # broadcasts rank 0's parameters through `.data` (no version bump) ...
@@ -159,6 +205,17 @@ class Trainer:
             return True
         return False
 
+    def _error_map_batch(self, index, inds_coarse, gt_rgb):
+        """(map, index, inds_coarse) of this step's update, or None (no map, or the batch was not drawn from it)"""
+        if self.error_map is None or inds_coarse is None or index is None:
+            return None
+        if self.dist is not None:
+            raise NotImplementedError("error map: not supported with data parallelism (the ranks' rays update one map; "
+                                      "keeping it consistent across ranks is not implemented)")
+        if gt_rgb is not None and not isinstance(gt_rgb, tuple) and gt_rgb.shape[-1] != 3:
+            raise ValueError("error map: RGBA targets (the reference's per-pixel random background) are not supported")
+        return (self.error_map, index, inds_coarse)
+
     def _eager_step(self, rays_o, rays_d, gt_rgb, bg_color=1):
         model = self.model
         # without data parallelism the gradients are simply replaced each step (no 49 MB zero fill + 147 MB accumulate);
@@ -167,7 +224,7 @@ class Trainer:
         with torch.autocast("cuda", dtype=torch.float16, enabled=self.fp16):
             out = model.render(rays_o, rays_d, bg_color=bg_color, perturb=True, force_all_rays=False,
                                defer_background=self.native_optim, fused_loss=self._fused_loss(gt_rgb), **self.render_kwargs)
-            loss = self._regularized(render_loss(out, gt_rgb, self._expected_grad()))
+            loss = self._regularized(render_loss(out, gt_rgb, self._expected_grad(), error_map=self._em_batch))
         self._backward(loss)
         self._reduce_and_step()
         return loss.detach()
@@ -234,13 +291,18 @@ class Trainer:
         else:
             self.scaler.scale(loss).backward()
 
-    def train_step(self, rays_o, rays_d, gt_rgb, bg_color=1):
-        """rays_o/d [N,3], gt_rgb [N,3].  Returns the (detached) loss tensor; no host sync."""
-        self.model.train()
-        self._maybe_update_extra_state()
-        self.global_step += 1
-        loss = self._eager_step(rays_o, rays_d, gt_rgb, bg_color)
-        self._sched_step()
+    def train_step(self, rays_o, rays_d, gt_rgb, bg_color=1, index=None, inds_coarse=None):
+        """rays_o/d [N,3], gt_rgb [N,3].  Returns the (detached) loss tensor; no host sync.  `index` / `inds_coarse` (a batch
+        of NeRFDataset.collate / sample with the error map on): the step updates `self.error_map`."""
+        self._em_batch = self._error_map_batch(index, inds_coarse, gt_rgb)
+        try:
+            self.model.train()
+            self._maybe_update_extra_state()
+            self.global_step += 1
+            loss = self._eager_step(rays_o, rays_d, gt_rgb, bg_color)
+            self._sched_step()
+        finally:
+            self._em_batch = None
         return loss
 
     @torch.no_grad()
@@ -298,13 +360,25 @@ class GraphedTrainer(Trainer):
         self.noise_key = (torch.initial_seed() * 0x9E3779B1 + (self.dist.rank if self.dist is not None else 0) * 0x85EBCA6B) & 0xFFFFFFFF
         self._counter_ring = None
         self._ring_args = None
+        # error-map batches: the captured step reads the batch's image index and cells from static buffers too (written by
+        # NeRFDataset.sample(out=static_batch()) or staged), and its update launch is part of the graph
+        self.s_index = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.s_inds_coarse = torch.zeros(1, num_rays, dtype=torch.int64, device=dev)
+        self._graph_em = None
+
+    def static_batch(self):
+        """the step's static input buffers as a `sample(out=...)` target (one image of num_rays rays): the sampler's launch
+        writes the batch where the captured step reads it"""
+        n = self.s_ro.shape[0]
+        return {"rays_o": self.s_ro.view(1, n, 3), "rays_d": self.s_rd.view(1, n, 3), "images": self.s_gt.view(1, n, 3),
+                "inds_coarse": self.s_inds_coarse, "index": self.s_index}
 
     def _static_loss(self):
         """the step's loss on the static input buffers (subclasses: other criteria, e.g. Seal's depth term)"""
         with torch.autocast("cuda", dtype=torch.float16, enabled=self.fp16):
             out = self.model.render(self.s_ro, self.s_rd, bg_color=1, perturb=True, force_all_rays=False,
                                     defer_background=self.native_optim, fused_loss=self._fused_loss(self.s_gt), **self.render_kwargs)
-            return self._regularized(render_loss(out, self.s_gt, self._expected_grad()))
+            return self._regularized(render_loss(out, self.s_gt, self._expected_grad(), error_map=self._em_batch))
 
     def _body_fb(self):
         """zero grads -> render -> loss -> scaled backward"""
@@ -443,8 +517,24 @@ class GraphedTrainer(Trainer):
         return True
 
     def _stage_inputs(self, rays_o, rays_d, gt_rgb):
+        if rays_o.data_ptr() == self.s_ro.data_ptr() and rays_d.data_ptr() == self.s_rd.data_ptr() \
+                and gt_rgb.data_ptr() == self.s_gt.data_ptr():
+            return  # (drawn into the static buffers by the sampler: static_batch)
         torch._foreach_copy_([self.s_ro, self.s_rd, self.s_gt],
                              [rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), gt_rgb.reshape(-1, 3)])  # one launch
+
+    def _stage_error_map(self, em):
+        """the static (map, index, inds_coarse) of the captured step; the batch's are copied in unless the sampler wrote them
+        there"""
+        emap, index, inds = em
+        index = torch.as_tensor(index, dtype=torch.int64).reshape(-1)
+        if index.numel() != 1 or inds.numel() != self.s_inds_coarse.numel():
+            raise ValueError("GraphedTrainer: an error-map batch is one image of num_rays rays")
+        if index.data_ptr() != self.s_index.data_ptr():
+            self.s_index.copy_(index, non_blocking=True)
+        if inds.data_ptr() != self.s_inds_coarse.data_ptr():
+            self.s_inds_coarse.copy_(inds.reshape(1, -1))
+        return (emap, self.s_index, self.s_inds_coarse)
 
     def _replay(self):
         # an eager backward without a step since the last replay left gradients in the hand-over buffer that the captured
@@ -463,7 +553,14 @@ class GraphedTrainer(Trainer):
             self._pushes += 1
         return slot
 
-    def train_step(self, rays_o, rays_d, gt_rgb, bg_color=1):
+    def train_step(self, rays_o, rays_d, gt_rgb, bg_color=1, index=None, inds_coarse=None):
+        self._em_batch = self._error_map_batch(index, inds_coarse, gt_rgb)
+        try:
+            return self._graphed_step(rays_o, rays_d, gt_rgb, bg_color)
+        finally:
+            self._em_batch = None
+
+    def _graphed_step(self, rays_o, rays_d, gt_rgb, bg_color):
         model = self.model
         model.train()
         if self._maybe_update_extra_state():
@@ -480,11 +577,17 @@ class GraphedTrainer(Trainer):
             raise ValueError("GraphedTrainer: the captured step composites on the white background (bg_color=1) of the "
                              "BASELINE configs; use Trainer for per-batch background colours")
         self._stage_inputs(rays_o, rays_d, gt_rgb)
+        if self._em_batch is not None:
+            self._em_batch = self._stage_error_map(self._em_batch)
+        em_key = None if self._em_batch is None else self._em_batch[0].data_ptr()
+        if self.graph is not None and em_key != self._graph_em:
+            self.graph = None  # (the captured step updates another map, or none: re-capture)
         if self.graph is not None and hasattr(self.optimizer, "follow_lr_schedule") and not self.optimizer.follow_lr_schedule():
             self.graph = None  # (parameter groups moved by different factors: the captured lr arguments no longer fit)
         if self.graph is not None and getattr(self.optimizer, "lr_epoch", 0) != getattr(self, "_graph_lr_epoch", 0):
             self.graph = None  # (somebody rebased the captured lrs since — another graph's capture, an eager step: re-capture)
         if self.graph is None:
+            self._graph_em = em_key
             self._capture()  # runs this step eagerly (one optimizer update), then records the graph
             loss = self.s_warm_loss
             filed = self._counter_ring is not None

@@ -49,6 +49,7 @@ EXPORTS = [
     "s3d_vm_features_backward", "s3d_vm_color_forward", "s3d_vm_color_backward",
     "s3d_composite_rays_train_loss_bg", "s3d_bg_targets_rays",
     "s3d_background_forward", "s3d_background_backward_workspace_size", "s3d_background_backward",
+    "s3d_sample_train_rays", "s3d_error_map_update",
 ]
 
 
@@ -1083,6 +1084,79 @@ class NgpHeadBackend:
         bg = (C.c_float * 3)(*[float(v) for v in bg_rgb])
         _check(lib().s3d_bg_mse_backward(_p(image), _p(weights_sum), _p(gt), bg, _u(image.shape[0]), _p(grad_loss),
                                          _p(grad_image), _p(grad_weights_sum), _stream()), "bg_mse_backward")
+
+
+class RaySampleBackend:
+    """csrc/raysample.hip — training rays drawn on the device (nerf/utils.py:92-114 with or without an error map) and the
+    error map's EMA update (nerf/utils.py:506-528)"""
+
+    @staticmethod
+    def sample_train_rays(error_map, index, N, H, W, poses, intrinsics, rays_o, rays_d, inds, inds_coarse=None, images=None,
+                          depths=None, gt=None, gt_depth=None, seed=0, ctl=None, u_keys=None, u_fine=None, out_index=None):
+        """seal3d_hip.h: s3d_sample_train_rays.  index [B] int64; outputs [B, N, ...] preallocated by the caller"""
+        B = index.numel()
+        _need(index, torch.int64, "index"); _need(poses, torch.float32, "poses"); _need(inds, torch.int64, "inds")
+        for t, n in ((rays_o, "rays_o"), (rays_d, "rays_d"), (gt, "gt"), (gt_depth, "gt_depth"), (error_map, "error_map"),
+                     (depths, "depths"), (u_keys, "u_keys"), (u_fine, "u_fine")):
+            if t is not None:
+                _need(t, torch.float32, n)
+        for t, n in ((inds_coarse, "inds_coarse"), (out_index, "out_index")):
+            if t is not None:
+                _need(t, torch.int64, n)
+        if out_index is not None and out_index.numel() != B:
+            raise RuntimeError("sample_train_rays: out_index must hold B values")
+        if ctl is not None:
+            _need(ctl, torch.int32, "ctl")
+        for t, n, w in ((rays_o, "rays_o", 3), (rays_d, "rays_d", 3), (inds, "inds", 1), (inds_coarse, "inds_coarse", 1),
+                        (gt, "gt", 3), (gt_depth, "gt_depth", 1), (u_fine, "u_fine", 2)):
+            if t is not None and t.numel() != B * N * w:
+                raise RuntimeError(f"sample_train_rays: {n} must hold {B} x {N} x {w} values")
+        n_img = poses.shape[0]
+        if error_map is not None and error_map.numel() != n_img * 128 * 128:
+            raise RuntimeError("sample_train_rays: error_map must be [n_images, 128 * 128]")
+        if u_keys is not None and u_keys.numel() != B * 128 * 128:
+            raise RuntimeError("sample_train_rays: u_keys must be [B, 128 * 128]")
+        dt = F32
+        if images is not None:
+            if images.dtype not in (torch.float32, torch.float16) or images.shape[-1] != 3 or images.numel() != n_img * H * W * 3:
+                raise RuntimeError("sample_train_rays: images must be [n_images, H, W, 3] fp32 / fp16")
+            dt = F16 if images.dtype == torch.float16 else F32
+        if depths is not None and depths.numel() != n_img * H * W:
+            raise RuntimeError("sample_train_rays: depths must hold one value per pixel")
+        intr = (C.c_float * 4)(*[float(v) for v in intrinsics])
+        _check(lib().s3d_sample_train_rays(_p(error_map), _p(index), _u(B), _u(N), _u(n_img), _u(H), _u(W), _p(poses), intr,
+                                           _p(images), C.c_int(dt), _p(depths), _u(int(seed) & 0xFFFFFFFF), _p(ctl), _p(u_keys),
+                                           _p(u_fine), _p(rays_o), _p(rays_d), _p(gt), _p(gt_depth), _p(inds), _p(inds_coarse),
+                                           _p(out_index), _stream()), "s3d_sample_train_rays")
+
+    @staticmethod
+    def error_map_update(error_map, index, inds_coarse, image, gt, weights_sum=None, bg=None, depth=None, gt_depth=None,
+                         depth_weight=1.0):
+        """seal3d_hip.h: s3d_error_map_update.  bg: None, 3 floats, or a per-ray fp32 tensor [B*N, 3]"""
+        B, N = inds_coarse.shape
+        _need(error_map, torch.float32, "error_map"); _need(index, torch.int64, "index"); _need(inds_coarse, torch.int64, "inds_coarse")
+        for t, n in ((image, "image"), (gt, "gt"), (weights_sum, "weights_sum"), (depth, "depth"), (gt_depth, "gt_depth")):
+            if t is not None:
+                _need(t, torch.float32, n)
+        if index.numel() != B or image.numel() != B * N * 3 or gt.numel() != B * N * 3:
+            raise RuntimeError("error_map_update: index [B], inds_coarse [B, N], image / gt [B*N, 3]")
+        if weights_sum is not None and weights_sum.numel() != B * N:
+            raise RuntimeError("error_map_update: weights_sum holds one value per ray")
+        if (depth is None) != (gt_depth is None) or (depth is not None and (depth.numel() != B * N or gt_depth.numel() != B * N)):
+            raise RuntimeError("error_map_update: depth and gt_depth (one value per ray) go together")
+        bg_rgb, bg_rays = None, None
+        if torch.is_tensor(bg):
+            _need(bg, torch.float32, "bg")
+            if bg.numel() != B * N * 3:
+                raise RuntimeError("error_map_update: a per-ray background is [B*N, 3]")
+            bg_rays = bg
+        elif bg is not None:
+            bg_rgb = (C.c_float * 3)(*[float(v) for v in bg])
+        if error_map.dim() != 2 or error_map.shape[1] != 128 * 128:
+            raise RuntimeError("error_map_update: error_map must be [n_images, 128 * 128]")
+        _check(lib().s3d_error_map_update(_p(error_map), _u(error_map.shape[0]), _p(index), _p(inds_coarse), _u(B), _u(N), _p(image), _p(weights_sum),
+                                          _p(gt), bg_rgb, _p(bg_rays), _p(depth), _p(gt_depth), C.c_float(float(depth_weight)),
+                                          _stream()), "s3d_error_map_update")
 
 
 class SealBackend:

@@ -4,12 +4,17 @@ pixels from them (`collate`).  The disk loader under it (nerf/provider.py: trans
 hot path — poses, intrinsics and the frame size are handed in."""
 import torch
 
+from nerf.provider import MAP_CELLS, DeviceSampling
 from nerf.synthetic import get_rays
 
 
-class SealDataset:
+class SealDataset(DeviceSampling):
+    """`error_map=True` (training only): the reference's per-image map of recent per-pixel loss, torch.ones(n, 128*128) on the
+    device (nerf/provider.py:234-256, inherited by SealNeRF/provider.py); `collate` then draws error-weighted pixels and hands
+    out `index` / `inds_coarse`, and `sample()` (nerf/provider.py: DeviceSampling) draws the batch on the GPU."""
+
     def __init__(self, poses, intrinsics, H, W, num_rays=4096, images=None, device=None, training=True, render_kwargs=None,
-                 fp16=False):
+                 fp16=False, error_map=False, seed=0):
         self.device = torch.device(device) if device is not None else poses.device
         self.poses = poses.to(self.device)
         self.intrinsics, self.H, self.W = intrinsics, H, W
@@ -20,6 +25,9 @@ class SealDataset:
         self.proxy_flag = False
         self.fp16 = fp16
         self.render_kwargs = dict(render_kwargs or {})
+        self.error_map = torch.ones(len(self.poses), MAP_CELLS, dtype=torch.float, device=self.device) \
+            if (training and error_map) else None
+        self._init_sampling(seed)
 
     def __len__(self):
         return self.poses.shape[0]
@@ -56,11 +64,13 @@ class SealDataset:
         self.proxy_flag = True
 
     def collate(self, index, generator=None):
-        """SealNeRF/provider.py:72-128 for a dataset pose: `num_rays` random pixels of pose `index[0]`, their rays and the
-        targets gathered from `images` / `depths`"""
+        """SealNeRF/provider.py:72-131 for a dataset pose: `num_rays` random pixels of pose `index[0]` (error-map weighted when
+        the map is on), their rays and the targets gathered from `images` / `depths`; with the map also `index` and
+        `inds_coarse` (the trainer's update)"""
         B = len(index)
         poses = self.poses[index]
-        rays = get_rays(poses, self.intrinsics, self.H, self.W, self.num_rays, generator=generator)
+        error_map = None if self.error_map is None else self.error_map[index]
+        rays = get_rays(poses, self.intrinsics, self.H, self.W, self.num_rays, error_map, generator=generator)
         out = {"H": self.H, "W": self.W, "rays_o": rays["rays_o"], "rays_d": rays["rays_d"], "skip_proxy": self.proxy_flag,
                "data_index": torch.tensor(index), "pixel_index": rays["inds"] if self.num_rays > 0 else None}
         for name, frames in (("images", self.images), ("depths", self.depths)):
@@ -71,4 +81,7 @@ class SealDataset:
                 C = v.shape[-1]
                 v = torch.gather(v.view(B, -1, C), 1, torch.stack(C * [rays["inds"]], -1))
             out[name] = v
+        if error_map is not None:
+            out["index"] = index
+            out["inds_coarse"] = rays["inds_coarse"]
         return out

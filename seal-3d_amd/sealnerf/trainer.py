@@ -251,7 +251,8 @@ class SealSteps:
                                     fused_loss=self._fused_loss(gt_rgb, gt_depth, self.depth_weight), **self.render_kwargs)
             # (+ the backbone trainer's own term: TensoRF's L1 penalty, tensoRF/utils.py:42-49 — the student's train_step of
             #  the reference is the backbone trainer's, SealNeRF/trainer.py:589-594)
-            loss = self._regularized(render_loss(out, gt_rgb, self._expected_grad(), gt_depth, self.depth_weight))
+            loss = self._regularized(render_loss(out, gt_rgb, self._expected_grad(), gt_depth, self.depth_weight,
+                                                 error_map=getattr(self, "_em_batch", None)))
         return loss, out
 
     def pretrain_step(self, points, dirs, gt_sigma, gt_color, n_total=None):
@@ -470,15 +471,21 @@ class SealTrainer(SealSteps, Trainer):
         Trainer.__init__(self, student, lr=lr, fp16=fp16, dist=dist, **kw)
         self._init_seal(teacher, lr, depth_weight)
 
-    def train_step(self, rays_o, rays_d, gt_rgb=None, gt_depth=None, bg_color=1):
-        self.end_pretraining()
-        if gt_rgb is None:
-            gt_rgb, gt_depth = self.proxy_truth(rays_o, rays_d)
-        self.model.train()
-        self._maybe_update_extra_state()  # (with data parallelism: occupancy state re-synchronised over the ranks)
-        self.global_step += 1
-        loss = self._seal_step(rays_o, rays_d, gt_rgb, gt_depth, bg_color)
-        self._sched_step()
+    def train_step(self, rays_o, rays_d, gt_rgb=None, gt_depth=None, bg_color=1, index=None, inds_coarse=None):
+        """`index` / `inds_coarse` (an error-map batch of SealDataset): the step updates `self.error_map` (nerf/trainer.py:
+        update_error_map) with the errors against the targets it trains on — the proxy's when gt_rgb is None"""
+        self._em_batch = self._error_map_batch(index, inds_coarse, gt_rgb)
+        try:
+            self.end_pretraining()
+            if gt_rgb is None:
+                gt_rgb, gt_depth = self.proxy_truth(rays_o, rays_d)
+            self.model.train()
+            self._maybe_update_extra_state()  # (with data parallelism: occupancy state re-synchronised over the ranks)
+            self.global_step += 1
+            loss = self._seal_step(rays_o, rays_d, gt_rgb, gt_depth, bg_color)
+            self._sched_step()
+        finally:
+            self._em_batch = None
         return loss
 
 
@@ -496,8 +503,8 @@ def _tensorf_seal_trainer():
             self._init_seal(teacher, lr0, depth_weight)
             self._attach_source_checks()
 
-        def train_step(self, rays_o, rays_d, gt_rgb=None, gt_depth=None, bg_color=1):
-            loss = SealTrainer.train_step(self, rays_o, rays_d, gt_rgb, gt_depth, bg_color)
+        def train_step(self, rays_o, rays_d, gt_rgb=None, gt_depth=None, bg_color=1, index=None, inds_coarse=None):
+            loss = SealTrainer.train_step(self, rays_o, rays_d, gt_rgb, gt_depth, bg_color, index=index, inds_coarse=inds_coarse)
             self._maybe_upsample()
             return loss
     return SealTensoRFTrainer
@@ -517,8 +524,8 @@ def _tensorf_seal_graphed_trainer():
             GraphedSealTrainer.__init__(self, student, teacher, num_rays, lr=lr0, fp16=fp16, dist=dist, depth_weight=depth_weight, **kw)
             self._attach_source_checks()
 
-        def train_step(self, rays_o, rays_d, gt_rgb=None, gt_depth=None, bg_color=1):
-            loss = GraphedSealTrainer.train_step(self, rays_o, rays_d, gt_rgb, gt_depth, bg_color)
+        def train_step(self, rays_o, rays_d, gt_rgb=None, gt_depth=None, bg_color=1, index=None, inds_coarse=None):
+            loss = GraphedSealTrainer.train_step(self, rays_o, rays_d, gt_rgb, gt_depth, bg_color, index=index, inds_coarse=inds_coarse)
             self._maybe_upsample()
             return loss
     return SealTensoRFGraphedTrainer
@@ -545,6 +552,11 @@ class GraphedSealTrainer(SealSteps, GraphedTrainer):
         self._init_seal(teacher, lr, depth_weight)
         self.s_depth = torch.zeros(num_rays, device=self.s_ro.device)
         self.proxy_graph = None
+
+    def static_batch(self):
+        b = GraphedTrainer.static_batch(self)
+        b["depths"] = self.s_depth.view(1, -1, 1)
+        return b
 
     graph_proxy = True  # the teacher's proxy render replayed from its own HIP graph (static rays in, static targets out)
 
@@ -574,13 +586,16 @@ class GraphedSealTrainer(SealSteps, GraphedTrainer):
         gt_rgb, gt_depth = gt_rgb
         if gt_rgb is self.s_gt:  # targets (and rays) were staged by the proxy graph's caller
             return
+        if gt_rgb.data_ptr() == self.s_gt.data_ptr() and rays_o.data_ptr() == self.s_ro.data_ptr() \
+                and gt_depth.data_ptr() == self.s_depth.data_ptr():
+            return  # (drawn into the static buffers by the sampler: static_batch)
         torch._foreach_copy_([self.s_ro, self.s_rd, self.s_gt, self.s_depth],
                              [rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), gt_rgb.reshape(-1, 3), gt_depth.reshape(-1)])
 
     def _eager_step(self, rays_o, rays_d, gt, bg_color=1):
         return self._seal_step(rays_o, rays_d, gt[0], gt[1], bg_color)
 
-    def train_step(self, rays_o, rays_d, gt_rgb=None, gt_depth=None, bg_color=1):
+    def train_step(self, rays_o, rays_d, gt_rgb=None, gt_depth=None, bg_color=1, index=None, inds_coarse=None):
         self.end_pretraining()
         if gt_rgb is None:
             mode = self.online_proxy_mode
@@ -593,4 +608,4 @@ class GraphedSealTrainer(SealSteps, GraphedTrainer):
                 gt_rgb, gt_depth = self.s_gt, self.s_depth
             else:
                 gt_rgb, gt_depth = self.proxy_truth(rays_o, rays_d)
-        return GraphedTrainer.train_step(self, rays_o, rays_d, (gt_rgb, gt_depth), bg_color)
+        return GraphedTrainer.train_step(self, rays_o, rays_d, (gt_rgb, gt_depth), bg_color, index=index, inds_coarse=inds_coarse)

@@ -72,8 +72,8 @@ class Trainer(TensoRFSteps, _Trainer):
         _Trainer.__init__(self, model, lr=lr0, **kw)
         self._attach_source_checks()
 
-    def train_step(self, rays_o, rays_d, gt_rgb, bg_color=1):
-        loss = _Trainer.train_step(self, rays_o, rays_d, gt_rgb, bg_color)
+    def train_step(self, rays_o, rays_d, gt_rgb, bg_color=1, index=None, inds_coarse=None):
+        loss = _Trainer.train_step(self, rays_o, rays_d, gt_rgb, bg_color, index=index, inds_coarse=inds_coarse)
         self._maybe_upsample()
         return loss
 
@@ -90,7 +90,7 @@ class GraphedTrainer(TensoRFSteps, _GraphedTrainer):
         _GraphedTrainer.__init__(self, model, num_rays, lr=lr0, **kw)
         self._attach_source_checks()
 
-    def train_step(self, rays_o, rays_d, gt_rgb, bg_color=1):
-        loss = _GraphedTrainer.train_step(self, rays_o, rays_d, gt_rgb, bg_color)
+    def train_step(self, rays_o, rays_d, gt_rgb, bg_color=1, index=None, inds_coarse=None):
+        loss = _GraphedTrainer.train_step(self, rays_o, rays_d, gt_rgb, bg_color, index=index, inds_coarse=inds_coarse)
         self._maybe_upsample()
         return loss
