@@ -22,7 +22,6 @@
 // WMMA; parity target is the dense math of testing/test_ffmlp.py's torch twin, fp16 tolerance).
 #include "s3d_common.hpp"
 #include "sh_eval.hpp"
-#include <stdlib.h>
 
 namespace s3d {
 namespace {
@@ -469,15 +468,7 @@ __device__ __forceinline__ float16v pair_network(const half8* a0, uint32_t NH, c
 template <bool SEAL>
 // (occupancy, measured with tools/bench_pair.py at 1.6e6 rows: the NGP variant needs 114 registers — two 8-wave workgroups per
 //  CU; the Seal variant 148: forced down to 128 it spills 14 and takes 104 - 118 us against 98 with ONE workgroup per CU)
-#ifndef S3D_PAIR_WPE
-#define S3D_PAIR_WPE 0
-#endif
-#if S3D_PAIR_WPE
-#define S3D_PAIR_OCC __attribute__((amdgpu_waves_per_eu(S3D_PAIR_WPE, S3D_PAIR_WPE)))
-#else
-#define S3D_PAIR_OCC
-#endif
-__global__ void __launch_bounds__(kPairWaves * 64) S3D_PAIR_OCC k_ffmlp_ngp_pair(const _Float16* __restrict__ X, const PairNets nets, uint32_t B,
+__global__ void __launch_bounds__(kPairWaves * 64) k_ffmlp_ngp_pair(const _Float16* __restrict__ X, const PairNets nets, uint32_t B,
                                                                    uint32_t in_layout, const int32_t* __restrict__ n_valid,
                                                                    float* __restrict__ rgb_head, const MidFwd mid) {
     constexpr uint32_t W = 64, MB = 2, KS = 4, KP = 2, IN = 32;
@@ -965,14 +956,14 @@ __global__ void k_ffmlp_wgrad_reduce_jobs(ReduceJobs jobs) {
 
 // ------------------------------------------------------------------------------------ backward: fused
 // One kernel for the whole backward pass, nothing but the network input, the output gradient and the weights read
-// from HBM: per 32-point tile a wave (1) RE-COMPUTES the forward activations from the input (36 kFLOP per point is
+// from HBM: per 32-point tile the kernel (1) RE-COMPUTES the forward activations from the input (36 kFLOP per point is
 // nothing next to the 256-384 B per point the stored forward_buffer costs to write and read back), (2) walks the
 // transposed network for the data gradient exactly like k_ffmlp_dgrad, and (3) accumulates every layer's weight
 // gradient dW[o][i] += sum_p G[p][o] X[p][i] on the spot.  For (3) the batch is the MFMA K dimension, so both
 // operands are transposed through a per-wave LDS tile: lanes scatter their (point, feature) values into
 // T[feature][point] (rows padded to 40 halfs: the two lane halves hit disjoint banks) and read their fragment back
 // as ONE 16-byte row segment (8 consecutive points of one feature).  Weight-gradient accumulators stay in registers
-// (MFMA accumulation VGPRs) for all tiles of the wave; at the end the four waves are summed through LDS in a fixed
+// (MFMA accumulation VGPRs) for all tiles of the wave; at the end the workgroup's waves are summed through LDS in a fixed
 // order and one fp32 partial per workgroup goes to the same reduce kernel as the two-kernel path.  Deterministic.
 // HBM traffic per point: in*2 + 32 B read (+ in*2 B grad_inputs) instead of ~1.2 KB.
 constexpr uint32_t kTRow = 72;   // halfs per row of a per-wave tile: 64 features + 8 pad (144 B: 8-byte aligned segments)
@@ -1018,13 +1009,13 @@ __device__ __forceinline__ half8 transpose_load(const _Float16* __restrict__ T, 
     return v;
 }
 
-// Sum one weight-gradient matrix over the four waves of the workgroup and write the workgroup's fp32 partial.
-// Each wave stores its accumulator blocks to its OWN [64][64] LDS plane (independent stores, no read-modify-write
-// chains), then all 256 threads add the four planes in a fixed order.
-template <uint32_t MBLK, uint32_t NBLK, uint32_t THREADS = 256, uint32_t NPL = 4, typename Get>
+// Sum one weight-gradient matrix over the NPL accumulator-holding waves of the workgroup and write the workgroup's fp32
+// partial.  Each of them stores its accumulator blocks to its OWN [64][64] LDS plane (independent stores, no
+// read-modify-write chains), then all THREADS threads add the NPL planes in a fixed order.
+template <uint32_t MBLK, uint32_t NBLK, uint32_t THREADS, uint32_t NPL, typename Get>
 __device__ __forceinline__ void flush_matrix(float* __restrict__ red, float* __restrict__ partial, uint32_t matrix, uint32_t wave,
                                              uint32_t n, uint32_t h, Get&& get) {
-    // (THREADS > 256: the waves behind the fourth hold no accumulators — `wave` >= 4 — and only help with the sum)
+    // (the other waves hold no accumulators — `wave` >= NPL — and only help with the sum)
     constexpr uint32_t kPlane = kWgradPad * kWgradPad;
     __syncthreads();
     float* mine = red + (size_t)wave * kPlane;
@@ -1052,265 +1043,6 @@ __device__ __forceinline__ void flush_matrix(float* __restrict__ red, float* __r
     }
 }
 
-// KS0T: compile-time in_dim / 16 (0 = run-time).  With a run-time count every layer-0 MFMA step sits in its own branch and
-// the compiler shuttles the accumulators between VGPRs and AGPRs around each one (~1000 v_accvgpr moves per tile).
-template <int W, int NH, int IMB, int ACT, int KS0T>
-__global__ void __launch_bounds__(256) k_ffmlp_backward_fused(const _Float16* __restrict__ grad, const _Float16* __restrict__ X,
-                                                             const _Float16* __restrict__ Wt, uint32_t B, uint32_t in_dim,
-                                                             uint32_t out_dim, uint32_t act, _Float16* __restrict__ grad_inputs,
-                                                             float* __restrict__ partial, uint32_t in_layout,
-                                                             const int32_t* __restrict__ n_valid,
-                                                             const float* __restrict__ d_rgb, const float* __restrict__ rgb_head,
-                                                             const MidBwd midb) {
-    constexpr uint32_t MB = W / 32, KS = W / 16;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t n = lane & 31, h = lane >> 5;
-    const uint32_t KS0 = KS0T ? (uint32_t)KS0T : in_dim / 16;
-    // LDS: forward A frags [layer0: MB*KS0 | hidden: NH*MB*KS] | transposed A frags [last^T: MB | hidden^T: NH*MB*KS |
-    //      first^T: IMB*KS (only with grad_inputs)] | per-wave transpose tiles TG, TX | (aliased at the end) red[64*64]
-    const uint32_t nf_f0 = MB * KS0, nf_fh = NH * MB * KS;
-    const uint32_t nf_bl = MB, nf_bh = NH * MB * KS, nf_b0 = grad_inputs ? IMB * KS : 0;
-    const uint32_t nfrag = nf_f0 + nf_fh + nf_bl + nf_bh + nf_b0;
-    half8* frags = reinterpret_cast<half8*>(smem_raw);
-    half8* ff0 = frags;
-    half8* ffh = ff0 + (size_t)nf_f0 * 64;
-    half8* fbl = ffh + (size_t)nf_fh * 64;
-    half8* fbh = fbl + (size_t)nf_bl * 64;
-    half8* fb0 = fbh + (size_t)nf_bh * 64;
-    _Float16* tiles = reinterpret_cast<_Float16*>(frags + (size_t)nfrag * 64);
-    _Float16* TG = tiles + (size_t)wave * 2 * kTRows * kTRow;
-    _Float16* TX = TG + (size_t)kTRows * kTRow;
-    const _Float16* w_hid = Wt + (size_t)W * in_dim;
-    const _Float16* w_last = w_hid + (size_t)NH * W * W;
-
-    for (uint32_t f = wave; f < nfrag; f += 4) {
-        half8 v;
-        if (f < nf_f0) {  // forward, layer 0: A[row = hidden feature][k = input]
-            const uint32_t mblk = f / KS0, s = f % KS0;
-            const _Float16* r = Wt + (size_t)(mblk * 32 + n) * in_dim + 16 * s;
-#pragma unroll
-            for (uint32_t j = 0; j < 8; j++) v[j] = r[kperm(h, j)];
-        } else if (f < nf_f0 + nf_fh) {  // forward, hidden k
-            const uint32_t g = f - nf_f0, k = g / (MB * KS), mblk = (g / KS) % MB, s = g % KS;
-            const _Float16* r = w_hid + (size_t)k * W * W + (size_t)(mblk * 32 + n) * W + 16 * s;
-#pragma unroll
-            for (uint32_t j = 0; j < 8; j++) v[j] = r[kperm(h, j)];
-        } else if (f < nf_f0 + nf_fh + nf_bl) {  // last^T: A[i = hidden feature][k = output] = W_last[k][i]
-            const uint32_t i = (f - nf_f0 - nf_fh) * 32 + n;
-#pragma unroll
-            for (uint32_t j = 0; j < 8; j++) {
-                const uint32_t k = kperm(h, j);
-                v[j] = (k < out_dim) ? w_last[(size_t)k * W + i] : (_Float16)0.0f;
-            }
-        } else if (f < nf_f0 + nf_fh + nf_bl + nf_bh) {  // hidden^T: A[i = in feature][k = out feature] = W_k[k][i]
-            const uint32_t g = f - nf_f0 - nf_fh - nf_bl, k = g / (MB * KS), mblk = (g / KS) % MB, s = g % KS;
-            const _Float16* wk = w_hid + (size_t)k * W * W;
-#pragma unroll
-            for (uint32_t j = 0; j < 8; j++) v[j] = wk[(size_t)(16 * s + kperm(h, j)) * W + mblk * 32 + n];
-        } else {  // first^T: A[i = network input][k = first hidden feature] = W_0[k][i]
-            const uint32_t g = f - nf_f0 - nf_fh - nf_bl - nf_bh, mblk = g / KS, s = g % KS;
-            const uint32_t i = mblk * 32 + n;
-#pragma unroll
-            for (uint32_t j = 0; j < 8; j++)
-                v[j] = (i < in_dim) ? Wt[(size_t)(16 * s + kperm(h, j)) * in_dim + i] : (_Float16)0.0f;
-        }
-        frags[f * 64 + lane] = v;
-    }
-    __syncthreads();
-
-    // weight-gradient accumulators: layer 0 [W x in], hidden [W x W] x NH, last [16 (one block) x W]
-    float16v dw0[MB][IMB], dwh[NH > 0 ? NH : 1][MB][MB], dwl[MB];
-#pragma unroll
-    for (uint32_t a = 0; a < MB; a++) {
-#pragma unroll
-        for (uint32_t b = 0; b < (uint32_t)IMB; b++) dw0[a][b] = zero16();
-#pragma unroll
-        for (uint32_t k = 0; k < (uint32_t)NH; k++)
-#pragma unroll
-            for (uint32_t b = 0; b < MB; b++) dwh[k][a][b] = zero16();
-        dwl[a] = zero16();
-    }
-
-    const uint32_t ntiles = valid_rows(B, n_valid) / 32;
-    for (uint32_t tile = blockIdx.x * 4 + wave; tile < ntiles; tile += gridDim.x * 4) {
-        const size_t row = (size_t)tile * 32 + n;
-        // ---- inputs of the tile: network input (B fragments) and output gradient (one k-step)
-        half8 xf[4];  // in_dim <= 64
-#pragma unroll
-        for (uint32_t s = 0; s < 4; s++)
-            if (s < KS0) xf[s] = load_bfrag_input(X, in_layout, B, in_dim, row, s, h);
-        half8 gf;
-        if (d_rgb) {  // colour head: d(out_c) = d(rgb_c) * y (1 - y) formed here from the fp32 gradient of the compositing
-#pragma unroll
-            for (uint32_t j = 0; j < 8; j++) gf[j] = (_Float16)0.0f;
-            if (h == 0) {
-#pragma unroll
-                for (uint32_t c = 0; c < 3; c++) {  // (kperm(0, c) == c for c < 4)
-                    const float y = rgb_head[row * 3 + c];
-                    gf[c] = (_Float16)((float)(_Float16)d_rgb[row * 3 + c] * (y * (1.0f - y)));
-                }
-            }
-        } else if (midb.g_cin) {
-            gf = mid_grad_fragment(midb, row, h);
-        } else {
-            gf = load_bfrag_rowmajor(grad + row * 16, 0, h);
-        }
-
-        // ---- forward re-computation (same operations and roundings as k_ffmlp_forward)
-        half8 a[NH + 1][KS];
-        {
-            float16v acc[MB];
-#pragma unroll
-            for (uint32_t m = 0; m < MB; m++) acc[m] = zero16();
-#pragma unroll
-            for (uint32_t s = 0; s < 4; s++)
-                if (s < KS0) {
-#pragma unroll
-                    for (uint32_t m = 0; m < MB; m++) acc[m] = mfma(ff0[(m * KS0 + s) * 64 + lane], xf[s], acc[m]);
-                }
-#pragma unroll
-            for (uint32_t layer = 0; layer <= (uint32_t)NH; layer++) {
-#pragma unroll
-                for (uint32_t m = 0; m < MB; m++)
-#pragma unroll
-                    for (uint32_t r = 0; r < 16; r += 2) {
-                        if constexpr (ACT == ACT_RELU) {
-                            const half2p v = relu2(cvt2(acc[m][r], acc[m][r + 1]));
-                            a[layer][2 * m + (r >> 3)][r & 7] = v[0];
-                            a[layer][2 * m + (r >> 3)][(r & 7) + 1] = v[1];
-                        } else {
-#pragma unroll
-                            for (uint32_t q = r; q < r + 2; q++) {
-                                const float pre = (float)(_Float16)acc[m][q];
-                                a[layer][2 * m + (q >> 3)][q & 7] = (_Float16)act_fwd_t<ACT>(act, pre);
-                            }
-                        }
-                    }
-                if (layer < (uint32_t)NH) {
-                    const half8* wf = ffh + (size_t)(layer * MB * KS) * 64;
-#pragma unroll
-                    for (uint32_t m = 0; m < MB; m++) {
-                        acc[m] = zero16();
-#pragma unroll
-                        for (uint32_t s = 0; s < KS; s++) acc[m] = mfma(wf[(m * KS + s) * 64 + lane], a[layer][s], acc[m]);
-                    }
-                }
-            }
-        }
-
-        // ---- last layer: dW_last += g^T a_NH ; dA_NH = W_last^T g
-        {
-            const half8 gtmp[1] = {gf};
-            transpose_store<1>(TG, gtmp, 1, n, h);
-            transpose_store<(int)KS>(TX, a[NH], KS, n, h);
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (uint32_t s = 0; s < 2; s++) {
-                const half8 af = transpose_load(TG, 0, s, n, h, 16);
-#pragma unroll
-                for (uint32_t ni = 0; ni < MB; ni++) dwl[ni] = mfma(af, transpose_load(TX, ni, s, n, h, W), dwl[ni]);
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-        float16v acc[MB];
-#pragma unroll
-        for (uint32_t m = 0; m < MB; m++) acc[m] = mfma(fbl[m * 64 + lane], gf, zero16());
-
-        // ---- hidden layers, top down
-        half8 G[KS];
-#pragma unroll
-        for (int k = NH; k >= 0; k--) {
-            // gradient w.r.t. the pre-activation of hidden layer k (activation transfer with the re-computed output)
-#pragma unroll
-            for (uint32_t m = 0; m < MB; m++)
-#pragma unroll
-                for (uint32_t r = 0; r < 16; r += 2) {
-                    if constexpr (ACT == ACT_RELU) {
-                        half2p av;
-                        av[0] = a[k][2 * m + (r >> 3)][r & 7]; av[1] = a[k][2 * m + (r >> 3)][(r & 7) + 1];
-                        const half2p v = gate2(cvt2(acc[m][r], acc[m][r + 1]), av);
-                        G[2 * m + (r >> 3)][r & 7] = v[0];
-                        G[2 * m + (r >> 3)][(r & 7) + 1] = v[1];
-                    } else {
-#pragma unroll
-                        for (uint32_t q = r; q < r + 2; q++) {
-                            const float g = (float)(_Float16)acc[m][q];
-                            G[2 * m + (q >> 3)][q & 7] = (_Float16)act_bwd_t<ACT>(act, g, (float)a[k][2 * m + (q >> 3)][q & 7]);
-                        }
-                    }
-                }
-            transpose_store<(int)KS>(TG, G, KS, n, h);
-            if (k > 0) {
-                transpose_store<(int)KS>(TX, a[k - 1], KS, n, h);
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (uint32_t s = 0; s < 2; s++) {
-                    half8 bfr[MB];
-#pragma unroll
-                    for (uint32_t ni = 0; ni < MB; ni++) bfr[ni] = transpose_load(TX, ni, s, n, h, W);
-#pragma unroll
-                    for (uint32_t mo = 0; mo < MB; mo++) {
-                        const half8 af = transpose_load(TG, mo, s, n, h, W);
-#pragma unroll
-                        for (uint32_t ni = 0; ni < MB; ni++) dwh[k - 1][mo][ni] = mfma(af, bfr[ni], dwh[k - 1][mo][ni]);
-                    }
-                }
-                __builtin_amdgcn_wave_barrier();
-                const half8* wf = fbh + (size_t)((k - 1) * MB * KS) * 64;
-#pragma unroll
-                for (uint32_t m = 0; m < MB; m++) {
-                    acc[m] = zero16();
-#pragma unroll
-                    for (uint32_t s = 0; s < KS; s++) acc[m] = mfma(wf[(m * KS + s) * 64 + lane], G[s], acc[m]);
-                }
-            } else {
-                transpose_store<4>(TX, xf, KS0, n, h);
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (uint32_t s = 0; s < 2; s++) {
-                    half8 bfr[IMB];
-#pragma unroll
-                    for (uint32_t ni = 0; ni < (uint32_t)IMB; ni++) bfr[ni] = transpose_load(TX, ni, s, n, h, in_dim);
-#pragma unroll
-                    for (uint32_t mo = 0; mo < MB; mo++) {
-                        const half8 af = transpose_load(TG, mo, s, n, h, W);
-#pragma unroll
-                        for (uint32_t ni = 0; ni < (uint32_t)IMB; ni++) dw0[mo][ni] = mfma(af, bfr[ni], dw0[mo][ni]);
-                    }
-                }
-                __builtin_amdgcn_wave_barrier();
-            }
-        }
-        if (grad_inputs) {
-#pragma unroll
-            for (uint32_t m = 0; m < (uint32_t)IMB; m++) {
-                float16v gi = zero16();
-#pragma unroll
-                for (uint32_t s = 0; s < KS; s++) gi = mfma(fb0[(m * KS + s) * 64 + lane], G[s], gi);
-#pragma unroll
-                for (uint32_t q = 0; q < 4; q++) {
-                    const uint32_t feat = m * 32 + 8 * q + 4 * h;
-                    if (feat < in_dim) {
-                        half4 v;
-#pragma unroll
-                        for (uint32_t e = 0; e < 4; e++) v[e] = (_Float16)gi[4 * q + e];
-                        store_grad_input(grad_inputs, in_layout, B, in_dim, row, feat, v);
-                    }
-                }
-            }
-        }
-    }
-
-    // ---- sum the four waves in a fixed order through LDS, one [64][64] fp32 partial per (matrix, workgroup)
-    float* red = reinterpret_cast<float*>(smem_raw);  // 4 planes x 16 KiB over the (no longer needed) fragments and tiles
-    flush_matrix<MB, IMB>(red, partial, 0, wave, n, h, [&](auto mo, auto ni) { return dw0[mo][ni]; });
-#pragma unroll
-    for (uint32_t k = 0; k < (uint32_t)NH; k++)
-        flush_matrix<MB, MB>(red, partial, 1 + k, wave, n, h, [&](auto mo, auto ni) { return dwh[k][mo][ni]; });
-    flush_matrix<1, MB>(red, partial, NH + 1, wave, n, h, [&](auto mo, auto ni) { (void)mo; return dwl[ni]; });
-}
-
 template <typename F, uint32_t... I>
 __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<uint32_t, I...>) {
     (f(std::integral_constant<uint32_t, I>{}), ...);
@@ -1328,29 +1060,27 @@ __device__ unsigned long long s3d_ffmlp_prof[2][1024];
 #define DUO_STAMP() do { } while (0)
 #endif
 // ------------------------------------------------------------------------------------ backward: fused, two roles
-// The fused kernel above runs ONE 456-register wave per SIMD: nothing hides the latencies of its MFMA chains, conversions and
-// LDS round trips, and it spends ~70 % of a launch in the re-computation + data-gradient chain and ~30 % in the weight-gradient
-// MFMAs (measured by switching the halves off).  Here the two halves are different WAVES: workgroup = 4 pairs; the compute
-// wave of a pair re-computes the activations and walks the data gradient, storing each layer's (gradient, activation) tile to
-// LDS; its partner keeps the weight-gradient accumulators (192 registers) and consumes the tiles one stage behind, through a
+// One wave doing all three steps of a tile needs 456 registers, so ONE wave per SIMD: nothing hides the latencies of its MFMA
+// chains, conversions and LDS round trips, and it spends ~70 % of a launch in the re-computation + data-gradient chain and
+// ~30 % in the weight-gradient MFMAs (measured by switching the halves off).  Here the two halves are different WAVES: a compute
+// wave re-computes the activations and walks the data gradient, storing each layer's (gradient, activation) tile to
+// LDS; a weight-gradient wave keeps the accumulators (192 registers) and consumes the tiles one stage behind, through a
 // double-buffered slot and one workgroup barrier per stage.  Two waves of <= 256 registers per SIMD: the matrix pipe, the VALU
-// and the LDS overlap across the pair.  Same per-wave tile sequence, same MFMA order per accumulator: bit-identical results.
+// and the LDS overlap across them.
 // NC compute waves and NG weight-gradient waves per workgroup (NC a multiple of NG): weight-gradient wave g consumes the tiles
-// of the compute waves g, g + NG, ... in that order, one stage behind each.  Deterministic; the sums differ from the (NC = NG)
-// arrangement only in the order the tiles of a workgroup enter an accumulator.
+// of the compute waves g, g + NG, ... in that order, one stage behind each.  Deterministic: the order in which the tiles of a
+// workgroup enter an accumulator is fixed.
 // The stage barriers of the two-role kernel order LDS traffic only (tile slots): a __syncthreads() would also drain every wave's
 // vector-memory queue — the input-gradient stores of a tile's last stage and the next tile's input loads — at each of the NS + 1
-// barriers of a round.  S3D_DUO_FULL_BARRIER: the old behaviour (A/B).
+// barriers of a round.
 __device__ __forceinline__ void duo_barrier() {
-#ifdef S3D_DUO_FULL_BARRIER
-    __syncthreads();
-#else
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-#endif
 }
-template <int W, int NH, int IMB, int ACT, int KS0T, int NC = 4, int NG = 4>
+// KS0T: compile-time in_dim / 16 (0 = run-time).  With a run-time count every layer-0 MFMA step sits in its own branch and
+// the compiler shuttles the accumulators between VGPRs and AGPRs around each one (~1000 v_accvgpr moves per tile).
+template <int W, int NH, int IMB, int ACT, int KS0T, int NC, int NG>
 __global__ void __launch_bounds__((NC + NG) * 64) k_ffmlp_backward_duo(const _Float16* __restrict__ grad, const _Float16* __restrict__ X,
                                                             const _Float16* __restrict__ Wt, uint32_t B, uint32_t in_dim,
                                                             uint32_t out_dim, uint32_t act, _Float16* __restrict__ grad_inputs,
@@ -1801,18 +1531,11 @@ int launch_backward_fused_k(const _Float16* grad, const _Float16* X, const _Floa
     // weight-gradient wave serves THREE compute waves: 6 + 2 waves of <= 256 registers, two per SIMD, six tile streams per CU
     // behind the same weights in LDS (18 KiB of tile slots per stream).  Measured at 269,824 rows (profiles/r11_mlp_backward.md):
     // colour network 48.0 -> 45.5 us, density network 37.5 - 38.8 (six pairs) -> 36.9 us; 6 + 3 and 6 + 6 within noise of 6 + 2,
-    // seven pairs 57 us (three waves per SIMD no longer fit the registers).  S3D_DUO_MIX / S3D_DUO_MIX_LIGHT = 4x4: round 5's pairs.
-    constexpr bool light = W == 64 && NH == 1 && IMB == 1 && KS0T == 2 && ACT == ACT_RELU;
+    // seven pairs 57 us (three waves per SIMD no longer fit the registers).
+    constexpr int NC = 6, NG = 2;
     const uint32_t nfrag = MB * (in_dim / 16) + NH * MB * KS + MB + NH * MB * KS + (grad_inputs ? IMB * KS : 0);
-    static const bool duo = [] { const char* e = getenv("S3D_FFMLP_DUO"); return !(e && e[0] == '0'); }();  // A/B switch
-    static const int mix = [] {
-        const char* e = getenv(light ? "S3D_DUO_MIX_LIGHT" : "S3D_DUO_MIX");
-        unsigned c = 0, g = 0;
-        if (e && sscanf(e, "%ux%u", &c, &g) == 2) return (int)(c * 16 + g);
-        return 6 * 16 + 2;
-    }();
     const uint32_t ntiles = B / 32;
-    // (four tile owners per workgroup decide the partial count whatever the kernel: s3d_ffmlp_wgrad_reduce_pair derives the
+    // (four tile owners per workgroup decide the partial count whatever the wave mix: s3d_ffmlp_wgrad_reduce_pair derives the
     //  layout of a deferred reduce from B alone; a workgroup of a small batch simply has idle streams)
     uint32_t nblk = div_up<uint32_t>(ntiles, 4);
     if (nblk > kWgradBlocks) nblk = kWgradBlocks;
@@ -1821,40 +1544,17 @@ int launch_backward_fused_k(const _Float16* grad, const _Float16* X, const _Floa
         if (v < planes * kWgradPad * kWgradPad * sizeof(float)) v = planes * kWgradPad * kWgradPad * sizeof(float);  // epilogue planes
         return v;
     };
-    auto run_duo = [&](auto ncc, auto ngc) -> int {
-        constexpr int NCv = decltype(ncc)::value, NGv = decltype(ngc)::value;
-        const size_t smem = smem_for(NCv, 2, NGv);
-        S3D_REQUIRE(smem <= 160 * 1024, "ffmlp_backward: wave mix %dx%d needs %zu bytes of LDS", NCv, NGv, smem);
-        static std::atomic<uint64_t> attr_devs{0};
-        int dev;
-        if (device_needs_setup(attr_devs, &dev)) {
-            S3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ffmlp_backward_duo<W, NH, IMB, ACT, KS0T, NCv, NGv>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            device_setup_done(attr_devs, dev);
-        }
-        hipLaunchKernelGGL((k_ffmlp_backward_duo<W, NH, IMB, ACT, KS0T, NCv, NGv>), dim3(nblk), dim3((NCv + NGv) * 64), smem, st, grad, X, Wt,
-                           B, in_dim, out_dim, act, grad_inputs, partial, in_layout, t_n_valid, t_d_rgb, t_rgb_in, t_mid_bwd);
-        return S3D_OK;
-    };
-    using std::integral_constant;
-    if (duo) {
-        int rc;
-        switch (mix) {
-            case 4 * 16 + 4: rc = run_duo(integral_constant<int, 4>{}, integral_constant<int, 4>{}); break;  // (round 5's pairs: A/B)
-            default: rc = run_duo(integral_constant<int, 6>{}, integral_constant<int, 2>{}); break;
-        }
-        if (rc) return rc;
-    } else {
-        static std::atomic<uint64_t> attr_devs{0};
-        int dev;
-        if (device_needs_setup(attr_devs, &dev)) {
-            S3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ffmlp_backward_fused<W, NH, IMB, ACT, KS0T>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            device_setup_done(attr_devs, dev);
-        }
-        hipLaunchKernelGGL((k_ffmlp_backward_fused<W, NH, IMB, ACT, KS0T>), dim3(nblk), dim3(256), smem_for(4, 1, 4), st, grad, X, Wt, B, in_dim,
-                           out_dim, act, grad_inputs, partial, in_layout, t_n_valid, t_d_rgb, t_rgb_in, t_mid_bwd);
+    const size_t smem = smem_for(NC, 2, NG);
+    S3D_REQUIRE(smem <= 160 * 1024, "ffmlp_backward: wave mix %dx%d needs %zu bytes of LDS", NC, NG, smem);
+    static std::atomic<uint64_t> attr_devs{0};
+    int dev;
+    if (device_needs_setup(attr_devs, &dev)) {
+        S3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ffmlp_backward_duo<W, NH, IMB, ACT, KS0T, NC, NG>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        device_setup_done(attr_devs, dev);
     }
+    hipLaunchKernelGGL((k_ffmlp_backward_duo<W, NH, IMB, ACT, KS0T, NC, NG>), dim3(nblk), dim3((NC + NG) * 64), smem, st, grad, X, Wt,
+                       B, in_dim, out_dim, act, grad_inputs, partial, in_layout, t_n_valid, t_d_rgb, t_rgb_in, t_mid_bwd);
     WgradPlan plan;
     memset(&plan, 0, sizeof(plan));
     plan.n = NH + 2;
@@ -2000,11 +1700,7 @@ S3D_EXPORT int s3d_ffmlp_ngp_pair_inference(const uint16_t* inputs, const uint16
     // persistent workgroups, as many as are resident at once: two per CU (NGP: 60 KB of LDS, 114 registers), one per CU (Seal:
     // 148 registers).  [384 workgroups — three waves per SIMD on paper — left half of the CUs with two workgroups and half with
     // one: 93 us per render iteration of 1.6e6 rows against 79 at 512; Seal variant 118 against 98 at 256]
-#ifdef S3D_PAIR_CAP  // (variant builds for A/B runs)
-    const uint32_t cap = S3D_PAIR_CAP;
-#else
     const uint32_t cap = (seal ? 1u : 2u) * cu_count() * 8u / kPairWaves;
-#endif
     if (grid > cap) grid = cap;
     if (seal)
         hipLaunchKernelGGL(k_ffmlp_ngp_pair<true>, dim3(grid), dim3(kPairWaves * 64), smem, as_stream(stream), (const _Float16*)inputs, nets, B,

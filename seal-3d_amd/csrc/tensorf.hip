@@ -10,8 +10,6 @@
 #include "s3d_common.hpp"
 #include <algorithm>
 #include <array>
-#include <cstdio>
-#include <cstdlib>
 
 namespace s3d {
 namespace {
@@ -481,34 +479,18 @@ __device__ __forceinline__ int vm_border_index(int lx, int ly) {
 constexpr int kVmFixBits = 50;
 constexpr uint32_t kVmMaxPts = 4096;
 __device__ __forceinline__ long long vm_fixed(float v, float scale) {
-#ifdef S3D_VM_FIXED_TWO_LIMB  // rounds 5 / 6a: hi = trunc(t / 2^24), lo = t - hi 2^24 (exact), q = hi 2^24 + rn(lo) — the same integer, ~12 vector instructions
-    const float t = v * scale;                                  // (power-of-two scale: exact)
-    const float hi = truncf(t * 5.9604644775390625e-08f);       // t / 2^24, |hi| < 2^27
-    const float lo = __builtin_fmaf(-hi, 16777216.0f, t);       // exact remainder, |lo| < 2^24
-    return (long long)(int)hi * 16777216ll + (long long)__float2int_rn(lo);
-#else
     // rn(t) for |t| < 2^51 as the low mantissa bits of t + 1.5 x 2^52 (the sum has an ulp of 1: the double add IS the rounding to
-    // nearest even): one conversion, one double add, one 64-bit subtract — the same integer as the two-limb form.  Colour plane
-    // pass 252 -> 234 us, colour line 38.7 -> 33.9 us (profiles/r11_tensorf_vm.md; an eighth of the LDS adds changes nothing there:
-    // the conversions, not the LDS atomics, are what the fixed-point sums cost).
+    // nearest even): one conversion, one double add, one 64-bit subtract, where a split into two 24-bit limbs took ~12 vector
+    // instructions for the same integer.  Colour plane pass 252 -> 234 us, colour line 38.7 -> 33.9 us
+    // (profiles/r11_tensorf_vm.md; an eighth of the LDS adds changes nothing there: the conversions, not the LDS atomics, are
+    // what the fixed-point sums cost).
     const double d = (double)(v * scale) + 6755399441055744.0;  // (power-of-two scale: exact; |v * scale| <= 2^50 by the bound)
     return __double_as_longlong(d) - 0x4338000000000000ll;
-#endif
 }
 __device__ __forceinline__ void vm_lds_add(long long* a, long long q) {
-#ifdef S3D_VM_EXP_NOLDSADD  // timing experiment only (wrong sums): what the LDS atomics cost
-    if (q == 0x7fffffffffffffffll) *a = q;
-#else
     atomicAdd(reinterpret_cast<unsigned long long*>(a), (unsigned long long)q);
-#endif
 }
-__device__ __forceinline__ void vm_flush_add(float* dst, float v) {
-#ifdef S3D_VM_EXP_PLAINFLUSH  // timing experiment only (wrong sums where segments share cells): what the global atomics cost
-    *dst = v;
-#else
-    atomicAdd(dst, v);
-#endif
-}
+__device__ __forceinline__ void vm_flush_add(float* dst, float v) { atomicAdd(dst, v); }
 // scale for a bound given as two (three) factors' bit patterns; returns false when there is nothing to add (a zero factor)
 // and sets `poison` when a factor is not finite (the gradient is then non-finite as the float sums would be)
 __device__ __forceinline__ bool vm_scale(float bound, float& scale, float& inv, bool& poison) {
@@ -1667,18 +1649,12 @@ S3D_EXPORT int s3d_vm_backward_bins(const float* x, uint32_t N, const uint32_t* 
     return check_launch("vm_backward_bins");
 }
 
-static const std::array<uint32_t, 4>& vm_lane_pts() {
-    static const std::array<uint32_t, 4> pts = [] {
-        std::array<uint32_t, 4> v = {256u, 512u, 1024u, 1024u};  // (same-box sweep, tools/vm_pts_sweep.sh)
-        if (const char* e = getenv("S3D_VM_PTS")) {
-            unsigned a, b2, c, d;
-            if (sscanf(e, "%u,%u,%u,%u", &a, &b2, &c, &d) == 4 && a && b2 && c && d) v = {a, b2, c, d};
-        }
-        return v;
-    }();
-    return pts;
-}
-static uint32_t vm_mm_pts(uint32_t which);
+// nominal sorted positions per workgroup, {plane, plane at rank <= 16, line, line at rank <= 16}: of the lane-per-rank passes
+// (same-box sweep, profiles/r11_tensorf_vm.md) and of the 32-points-per-trip passes (those serve ranks 32 .. 64 only: entries 0
+// and 2; line: 2,048 without the staged flush, 1,024 with it)
+constexpr std::array<uint32_t, 4> kVmLanePts = {256u, 512u, 1024u, 1024u};
+constexpr std::array<uint32_t, 4> kVmMmPts = {512u, 512u, 1024u, 1024u};
+static_assert(kVmMmPts[0] <= kVmMaxPts && kVmMmPts[2] <= kVmMaxPts, "the accumulators' headroom: kVmMaxPts contributions per cell");
 // staging rows of the flushes (VmBackward::stage_*): flags | plane rows | line rows
 struct VmStage { uint32_t tiles, lslots, R; size_t flag_words, plane_floats, line_floats, bytes; };
 static VmStage vm_stage_layout(uint32_t N, const uint32_t* rank, const uint32_t* resolution) {
@@ -1690,8 +1666,7 @@ static VmStage vm_stage_layout(uint32_t N, const uint32_t* rank, const uint32_t*
             v.tiles = t > v.tiles ? t : v.tiles;
         }
     }
-    const std::array<uint32_t, 4>& lp = vm_lane_pts();
-    const uint32_t min_line = std::min(std::min(std::min(lp[2], lp[3]), kVmMaxPts), vm_mm_pts(2));  // whichever line kernel runs
+    constexpr uint32_t min_line = std::min(std::min(std::min(kVmLanePts[2], kVmLanePts[3]), kVmMaxPts), kVmMmPts[2]);  // whichever line kernel runs
     v.lslots = 2 * div_up<uint32_t>(N, min_line);
     v.flag_words = ((size_t)3 * v.tiles + (size_t)3 * v.lslots + 63) & ~(size_t)63;
     v.plane_floats = (size_t)3 * v.tiles * 32 * v.R;
@@ -1705,17 +1680,14 @@ static uint32_t vm_stage_arm(VmBackward& b, uint32_t N, const uint32_t* rank, co
     b.stage_plane = b.stage_line = nullptr; b.plane_flag = b.line_flag = nullptr;
     b.stage_tiles = b.stage_lslots = b.stage_R = 0;
     flags = nullptr;
-    static const int mode = [] { const char* e = getenv("S3D_VM_STAGE"); return e ? atoi(e) : 1; }();  // (A/B: 0 off, 1 planes + lines, 2 lines only)
-    const bool on = mode != 0;
     const VmStage v = vm_stage_layout(N, rank, resolution);
-    if (!on || !stage || stage_bytes < v.bytes || (reinterpret_cast<uintptr_t>(stage) & 15u) || v.lslots > kVmStageMaxSlots) return 0;
+    if (!stage || stage_bytes < v.bytes || (reinterpret_cast<uintptr_t>(stage) & 15u) || v.lslots > kVmStageMaxSlots) return 0;
     flags = reinterpret_cast<uint32_t*>(stage);
     b.plane_flag = flags;
     b.line_flag = flags + (size_t)3 * v.tiles;
     b.stage_plane = reinterpret_cast<float*>(flags + v.flag_words);
     b.stage_line = b.stage_plane + v.plane_floats;
     b.stage_tiles = v.tiles; b.stage_lslots = v.lslots; b.stage_R = v.R;
-    if (mode == 2) { b.stage_plane = nullptr; b.stage_tiles = 0; }
     return (uint32_t)v.flag_words;
 }
 S3D_EXPORT size_t s3d_vm_backward_stage_bytes(uint32_t N, const uint32_t* rank, const uint32_t* resolution) {
@@ -1731,10 +1703,9 @@ static void vm_backward_geometry(VmBackward& b, uint32_t N, uint32_t max_rank, b
     const uint32_t rp = max_rank <= 16 ? 16u : 64u;
     // Every (range, tile) segment ends with one global atomic per cell of the 9 x 9 window and rank channel (3,888 at rank 48)
     // and global atomics retire at ~21 G/s chip-wide: segments = ranges + occupied tiles, so the ranges are as long as the
-    // workgroup count allows (tools/bench_tensorf_step.py with S3D_VM_PTS=plane64,plane16,line64,line16 sweeps them)
-    const std::array<uint32_t, 4>& pts = vm_lane_pts();
-    b.pts_plane = std::min(rp == 16 ? pts[1] : pts[0], kVmMaxPts);  // (the accumulators' headroom: kVmMaxPts contributions per cell)
-    b.pts_line = std::min(rp == 16 ? pts[3] : pts[2], kVmMaxPts);
+    // workgroup count allows
+    b.pts_plane = std::min(rp == 16 ? kVmLanePts[1] : kVmLanePts[0], kVmMaxPts);  // (the accumulators' headroom: kVmMaxPts contributions per cell)
+    b.pts_line = std::min(rp == 16 ? kVmLanePts[3] : kVmLanePts[2], kVmMaxPts);
     gp = dim3(div_up<uint32_t>(N, b.pts_plane), 3);
     gl = dim3(div_up<uint32_t>(N, b.pts_line), 3);
     smem_p = (size_t)kVmTileCells * max_rank * (sizeof(long long) + sizeof(float));
@@ -1745,40 +1716,28 @@ static void vm_backward_geometry(VmBackward& b, uint32_t N, uint32_t max_rank, b
 
 // the 32-points-per-trip passes (k_vm_plane_backward_mm / k_vm_line_backward_mm) serve calls whose three components share one
 // rank of 32, 48 or 64 (VM-48's colour factors); anything else — rank 16 included: 127 / 30 us on the lane-per-rank kernels
-// against 139 / 34 us here, profiles/r11_tensorf_vm.md — takes the lane-per-rank kernels.  S3D_VM_MM=0 switches them off (A/B),
-// S3D_VM_MM_PTS=plane,-,line,- sets the nominal sorted positions per workgroup (<= kVmMaxPts).
-static uint32_t vm_mm_pts(uint32_t which) {
-    static const std::array<uint32_t, 4> pts = [] {
-        std::array<uint32_t, 4> v = {512u, 512u, 1024u, 1024u};  // (line: 2,048 without the staged flush, 1,024 with it)
-        if (const char* e = getenv("S3D_VM_MM_PTS")) {
-            unsigned a, b2, c, d;
-            if (sscanf(e, "%u,%u,%u,%u", &a, &b2, &c, &d) == 4 && a >= 32 && b2 >= 32 && c >= 32 && d >= 32)
-                v = {std::min(a, kVmMaxPts), std::min(b2, kVmMaxPts), std::min(c, kVmMaxPts), std::min(d, kVmMaxPts)};
-        }
-        return v;
-    }();
-    return pts[which];
-}
+// against 139 / 34 us here, profiles/r11_tensorf_vm.md — takes the lane-per-rank kernels.
 template <int RB, int MODE>
-static void launch_plane_mm_t(const float* x, uint32_t N, const VmFactors& f, VmBackward& b, hipStream_t st) {
+static int launch_plane_mm_t(const float* x, uint32_t N, const VmFactors& f, VmBackward& b, hipStream_t st) {
     constexpr size_t smem = vm_mm_smem(RB, MODE == 2);
-    static const bool attr = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vm_plane_backward_mm<RB, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        return true;
-    }();
-    (void)attr;
-    b.pts_plane = vm_mm_pts(0);
+    static std::atomic<uint64_t> attr_devs{0};
+    int dev;
+    if (device_needs_setup(attr_devs, &dev)) {
+        S3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vm_plane_backward_mm<RB, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        device_setup_done(attr_devs, dev);
+    }
+    b.pts_plane = kVmMmPts[0];
     hipLaunchKernelGGL((k_vm_plane_backward_mm<RB, MODE>), dim3(div_up<uint32_t>(N, b.pts_plane), 3), dim3(kVmMmThreads), smem, st, x, N, f, b);
+    return S3D_OK;
 }
 template <int RB>
 static void launch_line_mm_t(const float* x, uint32_t N, const VmFactors& f, VmBackward& b, hipStream_t st) {
-    b.pts_line = vm_mm_pts(2);
+    b.pts_line = kVmMmPts[2];
     const size_t smem = (size_t)(kVmZChunk + 1) * 16 * RB * sizeof(long long) + (size_t)kVmMmWaves * 32 * sizeof(uint4);
     hipLaunchKernelGGL((k_vm_line_backward_mm<RB>), dim3(div_up<uint32_t>(N, b.pts_line), 3), dim3(kVmMmThreads), smem, st, x, N, f, b);
 }
 static bool launch_line_mm(const float* x, uint32_t N, const VmFactors& f, VmBackward& b, hipStream_t st) {
-    static const bool on = [] { const char* e = getenv("S3D_VM_MM"); return !(e && e[0] == '0'); }();
-    if (!on || f.rank[0] != f.rank[1] || f.rank[0] != f.rank[2] || f.rank[0] % 16 != 0 || f.rank[0] < 32 || f.rank[0] > 64) return false;
+    if (f.rank[0] != f.rank[1] || f.rank[0] != f.rank[2] || f.rank[0] % 16 != 0 || f.rank[0] < 32 || f.rank[0] > 64) return false;
     if (reinterpret_cast<uintptr_t>(b.gm) & 15u) return false;
     switch (f.rank[0] / 16) {
         case 2: launch_line_mm_t<2>(x, N, f, b, st); break;
@@ -1787,18 +1746,19 @@ static bool launch_line_mm(const float* x, uint32_t N, const VmFactors& f, VmBac
     }
     return true;
 }
+// `launched`: false = the call is not one of theirs, nothing was launched
 template <int MODE>
-static bool launch_plane_mm(const float* x, uint32_t N, const VmFactors& f, VmBackward& b, hipStream_t st) {
-    static const bool on = [] { const char* e = getenv("S3D_VM_MM"); return !(e && e[0] == '0'); }();
-    if (!on || f.rank[0] != f.rank[1] || f.rank[0] != f.rank[2] || f.rank[0] % 16 != 0 || f.rank[0] < 32 || f.rank[0] > 64) return false;
+static int launch_plane_mm(const float* x, uint32_t N, const VmFactors& f, VmBackward& b, hipStream_t st, bool& launched) {
+    launched = false;
+    if (f.rank[0] != f.rank[1] || f.rank[0] != f.rank[2] || f.rank[0] % 16 != 0 || f.rank[0] < 32 || f.rank[0] > 64) return S3D_OK;
     if ((reinterpret_cast<uintptr_t>(b.gm) | reinterpret_cast<uintptr_t>(b.line_t) | (MODE == 1 ? reinterpret_cast<uintptr_t>(b.g) : 0) |
-         (MODE == 2 ? reinterpret_cast<uintptr_t>(b.g_out) : 0)) & 15u) return false;
+         (MODE == 2 ? reinterpret_cast<uintptr_t>(b.g_out) : 0)) & 15u) return S3D_OK;
+    launched = true;
     switch (f.rank[0] / 16) {
-        case 2: launch_plane_mm_t<2, MODE>(x, N, f, b, st); break;
-        case 3: launch_plane_mm_t<3, MODE>(x, N, f, b, st); break;
-        default: launch_plane_mm_t<4, MODE>(x, N, f, b, st); break;
+        case 2: return launch_plane_mm_t<2, MODE>(x, N, f, b, st);
+        case 3: return launch_plane_mm_t<3, MODE>(x, N, f, b, st);
+        default: return launch_plane_mm_t<4, MODE>(x, N, f, b, st);
     }
-    return true;
 }
 
 S3D_EXPORT int s3d_vm_features_backward(const float* x, uint32_t N, const float* const* planes, const float* const* lines,
@@ -1849,7 +1809,8 @@ S3D_EXPORT int s3d_vm_features_backward(const float* x, uint32_t N, const float*
     const uint32_t n_stage_flags = vm_stage_arm(b, N, rank, resolution, stage, stage_bytes, stage_flags);
     hipLaunchKernelGGL(k_vm_bound, dim3(std::min<uint32_t>(stream_grid(n_g / 4 + 1, 256), 512u)), dim3(256), 0, st, grad, n_g, (const _Float16*)nullptr, (size_t)0, f,
                        (const _Float16*)nullptr, 0u, b.rows, bound_words, line_scratch, stage_flags, n_stage_flags, N, n_valid);
-    const bool mm = reduce ? launch_plane_mm<0>(x, N, f, b, st) : launch_plane_mm<1>(x, N, f, b, st);
+    bool mm;
+    if (int rc = reduce ? launch_plane_mm<0>(x, N, f, b, st, mm) : launch_plane_mm<1>(x, N, f, b, st, mm)) return rc;
     if (max_rank <= 16) {
         if (mm) {}
         else if (reduce) hipLaunchKernelGGL((k_vm_plane_backward<16, true>), gp, block, smem_p, st, x, N, f, b);
@@ -1936,7 +1897,9 @@ S3D_EXPORT int s3d_vm_color_backward(const float* x, uint32_t N, const float* co
     const uint32_t n_stage_flags = vm_stage_arm(b, N, rank, resolution, stage, stage_bytes, stage_flags);
     hipLaunchKernelGGL(k_vm_bound, dim3(std::min<uint32_t>(stream_grid(n_g16 / 8 + 1, 256), 512u)), dim3(256), 0, st, (const float*)nullptr, (size_t)0,
                        (const _Float16*)grad_out, n_g16, f, (const _Float16*)basis, basis_rows, b.rows, bound_words, line_scratch, stage_flags, n_stage_flags, N, n_valid);
-    if (!launch_plane_mm<2>(x, N, f, b, st)) hipLaunchKernelGGL((k_vm_plane_backward<64, false, true>), gp, block, smem_p, st, x, N, f, b);
+    bool mm;
+    if (int rc = launch_plane_mm<2>(x, N, f, b, st, mm)) return rc;
+    if (!mm) hipLaunchKernelGGL((k_vm_plane_backward<64, false, true>), gp, block, smem_p, st, x, N, f, b);
     if (!launch_line_mm(x, N, f, b, st)) hipLaunchKernelGGL((k_vm_line_backward<64>), gl, block, smem_l, st, x, N, f, b);
     if (b.stage_line) hipLaunchKernelGGL(k_vm_flush_reduce, dim3(div_up<uint32_t>(b.stage_tiles, kVmReduceTiles) + kVmLineParts * max_chunks, 3), dim3(256), 0, st, f, b);
     return check_launch("vm_color_backward");

@@ -9,7 +9,6 @@ library (MFMA fragment order), exactly as they are private scratch in the
 reference.
 """
 import math
-import os
 
 import torch
 import torch.nn as nn
@@ -20,7 +19,7 @@ import s3d_hip
 
 _backend = s3d_hip.FFMLPBackend
 
-_FUSED_BACKWARD = os.environ.get("S3D_FFMLP_FUSED", "1") != "0"  # A/B switch: 0 = store activations, two-kernel backward
+_FUSED_BACKWARD = True  # False (test reference): store activations, two-kernel backward
 
 _ACTIVATIONS = {"relu": 0, "exponential": 1, "sine": 2, "sigmoid": 3, "squareplus": 4, "softplus": 5}
 

@@ -1,7 +1,5 @@
 """NGP network used by Seal-3D (nerf/network.py of the reference): TWO hash encoders (density and colour),
 degree-4 SH on the view direction, bias-free nn.Linear MLPs, `trunc_exp` density, sigmoid colour."""
-import os
-
 import numpy as np
 import torch
 import torch.nn as nn
@@ -327,9 +325,9 @@ class NeRFNetwork(NeRFRenderer):
     #   colour net 63 -> 64 -> 64 -> 3 = ffmlp [W0 padded to 64 columns | W1 | W2 padded to 16 rows]
     # Same arithmetic as the reference's autocast path: fp16 operands, fp32 accumulation, fp16 activations; SH values
     # rounded to fp16 where the first Linear's input cast rounds them; sigmoid evaluated in fp32 and rounded to fp16.
-    fused_pair = os.environ.get("S3D_FUSED_PAIR", "1") != "0"  # A-B runs: False = density MLP, head kernel and colour MLP as three launches
-    fused_encoders = os.environ.get("S3D_FUSED_ENCODERS", "1") != "0"  # A-B runs: False = one forward launch per encoder
-    fused_mlp = os.environ.get("S3D_FUSED_SEAL", "1") != "0"  # tests / A-B runs: False = nn.Linear op sequence
+    fused_pair = True  # False (test reference): density MLP, head kernel and colour MLP as three launches
+    fused_encoders = True  # False (test reference): one forward launch per encoder
+    fused_mlp = True  # False (test reference): nn.Linear op sequence
 
     def honours_row_limit(self, rows):
         return self._can_fuse_rows(self.density_bitfield.is_cuda, 2, rows)
@@ -429,7 +427,7 @@ class NeRFNetwork(NeRFRenderer):
             rgbs[mask] = self._rgb(x[mask], d[mask], geo_feat[mask]).to(rgbs.dtype)
         return rgbs
 
-    fused_background = os.environ.get("S3D_FUSED_BG", "1") != "0"  # tests / A-B runs: False = the reference's op sequence
+    fused_background = True  # False (test reference): the reference's op sequence
 
     def _can_fuse_bg(self, x):
         enc = self.encoder_bg

@@ -1321,8 +1321,8 @@ class VmBackend:
         a = VmBackend._chain_args(mats, padded_rows, ld)
         _check(lib().s3d_unpack_linear_chain(_p(flat), a[0], a[1], a[2], a[3], a[4], a[5], _stream()), "unpack_linear_chain")
 
-    # False (S3D_VM_BINS=torch): keys + torch.sort + searchsorted, the A/B twin of s3d_vm_backward_bins
-    native_bins = os.environ.get("S3D_VM_BINS", "native") != "torch"
+    # False (test reference): keys + torch.sort + searchsorted, the twin of s3d_vm_backward_bins
+    native_bins = True
 
     @staticmethod
     def backward_bins(x, planes, resolution, n_valid=None):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time the one-launch network pair (s3d_ffmlp_ngp_pair_inference) alone: NGP and Seal variant, training-step and
-render-iteration batch sizes.  `S3D_PAIR_CAP` (workgroups) and variant libraries (`S3D_HIP_LIB`) for A/B runs."""
+render-iteration batch sizes.  Variant libraries (`S3D_HIP_LIB`) for A/B runs."""
 import os
 import sys
 
@@ -39,7 +39,7 @@ def main():
             b.record()
             torch.cuda.synchronize()
             out.append(f"{'seal' if seal else 'ngp '} B={B}: {a.elapsed_time(b) / 20 * 1e3:7.1f} us")
-    print(f"cap={os.environ.get('S3D_PAIR_CAP', 'default')} lib={os.path.basename(os.environ.get('S3D_HIP_LIB', 'shipped'))}: " + " | ".join(out))
+    print(f"lib={os.path.basename(os.environ.get('S3D_HIP_LIB', 'shipped'))}: " + " | ".join(out))
 
 
 if __name__ == "__main__":
