@@ -1410,18 +1410,35 @@ int ffmlp_generic_backward(const _Float16* grad, const _Float16* X, const _Float
                            bool accumulate, float* found_inf, float* workspace, size_t workspace_bytes, hipStream_t st);
 namespace {
 
-// `n_valid` of the entry point being served on this thread (see valid_rows()); the launch helpers below pass it on
-static thread_local const int32_t* t_n_valid = nullptr;
-static thread_local float* t_found_inf = nullptr;  // s3d_ffmlp_backward(found_inf) of the call being served
-static thread_local float* t_rgb_out = nullptr;          // colour head of the forward call being served (fp32 [B, 3] out)
-static thread_local const float* t_d_rgb = nullptr;      // ... of the backward call: gradient w.r.t. the head's output
-static thread_local const float* t_rgb_in = nullptr;     // ... and the head's output
-static thread_local MidFwd t_mid_fwd = {};               // density ("mid") head of the forward call being served
-static thread_local MidBwd t_mid_bwd = {};               // ... of the backward call
-static thread_local _Float16* t_generic_scratch = nullptr;  // inference_buffer of the s3d_ffmlp_inference call being served
-struct RowLimitScope {
-    explicit RowLimitScope(const int32_t* p, float* found_inf = nullptr) { t_n_valid = p; t_found_inf = found_inf; }
-    ~RowLimitScope() { t_n_valid = nullptr; t_found_inf = nullptr; }
+// One call of the forward / backward entry points: the ABI's pointers cast once (FwdArgs / BwdArgs) and what the call asks
+// for beyond the plain network (FwdOpts / BwdOpts).  The entry point fills them, the launch helpers below read them.
+struct FwdArgs {
+    const _Float16 *X, *Wt;
+    uint32_t B, in_dim, out_dim, n_layers, act, out_act;
+    _Float16 *fwd, *out;  // fwd: forward_buffer [n, B, W] (training) or nullptr
+    uint32_t in_layout;
+    hipStream_t st;
+};
+struct FwdOpts {
+    const int32_t* n_valid;  // see valid_rows()
+    float* rgb_out;          // colour head (fp32 [B, 3] out)
+    MidFwd mid;              // density ("mid") head
+    _Float16* scratch;       // inference_buffer [2, B, W]: only the layer-by-layer path of the non-native shapes uses it
+};
+struct BwdArgs {
+    const _Float16 *grad, *X, *Wt, *fwd;
+    uint32_t B, in_dim, out_dim, n_layers, act;
+    _Float16 *bwd, *grad_inputs, *grad_weights;
+    float* partial;  // the workspace
+    size_t partial_bytes;
+    uint32_t in_layout, accumulate;
+    hipStream_t st;
+};
+struct BwdOpts {
+    const int32_t* n_valid;
+    float* found_inf;
+    const float *d_rgb, *rgb_in;  // colour head: gradient w.r.t. the head's output, and the head's output
+    MidBwd mid;                   // density ("mid") head
 };
 
 int check_shape(uint32_t B, uint32_t in_dim, uint32_t out_dim, uint32_t W, uint32_t n_layers) {
@@ -1435,12 +1452,11 @@ int check_shape(uint32_t B, uint32_t in_dim, uint32_t out_dim, uint32_t W, uint3
 }
 
 template <int W>
-int launch_forward(const _Float16* X, const _Float16* Wt, uint32_t B, uint32_t in_dim, uint32_t out_dim, uint32_t n_layers,
-                   uint32_t act, uint32_t out_act, _Float16* fwd, _Float16* out, uint32_t in_layout, hipStream_t st) {
+int launch_forward(const FwdArgs& a, const FwdOpts& o) {
     constexpr uint32_t MB = W / 32, KS = W / 16;
-    const uint32_t nfr = MB * (in_dim / 16) + (n_layers - 1) * MB * KS + KS;
-    const size_t smem = (size_t)nfr * 64 * sizeof(half8) + (t_mid_fwd.cin ? (size_t)4 * 32 * kMidRow * sizeof(_Float16) : 0);
-    const uint32_t ntiles = B / 32;
+    const uint32_t nfr = MB * (a.in_dim / 16) + (a.n_layers - 1) * MB * KS + KS;
+    const size_t smem = (size_t)nfr * 64 * sizeof(half8) + (o.mid.cin ? (size_t)4 * 32 * kMidRow * sizeof(_Float16) : 0);
+    const uint32_t ntiles = a.B / 32;
     uint32_t grid = div_up<uint32_t>(ntiles, 4);
     // (measured at 2.6e5 points: 768 workgroups 11.8 / 14.6 us for the 2- / 3-matrix net, 1024: 12.7 / 16.2, 2048: 16.9 / 21.6,
     //  512: 12.2 / 14.7 — every workgroup stages all weights once, three per CU still hide the tile latencies)
@@ -1449,10 +1465,10 @@ int launch_forward(const _Float16* X, const _Float16* Wt, uint32_t B, uint32_t i
     if (big && grid > 256) grid = 256;
 #define S3D_FWD_K(TRAIN, A, O, K0) do { \
         if (big) S3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ffmlp_forward<W, TRAIN, A, O, K0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-        hipLaunchKernelGGL((k_ffmlp_forward<W, TRAIN, A, O, K0>), dim3(grid), dim3(256), smem, st, X, Wt, B, in_dim, out_dim, n_layers, act, out_act, fwd, out, in_layout, t_n_valid, t_rgb_out, t_mid_fwd); } while (0)
-#define S3D_FWD(TRAIN, A, O) do { if (in_dim == 32) S3D_FWD_K(TRAIN, A, O, 2); else if (in_dim == 64) S3D_FWD_K(TRAIN, A, O, 4); else S3D_FWD_K(TRAIN, A, O, 0); } while (0)
-    const bool fast = act == ACT_RELU && out_act == ACT_NONE;  // the networks of the hot path; anything else: run-time switch
-    if (fwd) { if (fast) S3D_FWD(true, ACT_RELU, ACT_NONE); else S3D_FWD(true, -1, -1); }
+        hipLaunchKernelGGL((k_ffmlp_forward<W, TRAIN, A, O, K0>), dim3(grid), dim3(256), smem, a.st, a.X, a.Wt, a.B, a.in_dim, a.out_dim, a.n_layers, a.act, a.out_act, a.fwd, a.out, a.in_layout, o.n_valid, o.rgb_out, o.mid); } while (0)
+#define S3D_FWD(TRAIN, A, O) do { if (a.in_dim == 32) S3D_FWD_K(TRAIN, A, O, 2); else if (a.in_dim == 64) S3D_FWD_K(TRAIN, A, O, 4); else S3D_FWD_K(TRAIN, A, O, 0); } while (0)
+    const bool fast = a.act == ACT_RELU && a.out_act == ACT_NONE;  // the networks of the hot path; anything else: run-time switch
+    if (a.fwd) { if (fast) S3D_FWD(true, ACT_RELU, ACT_NONE); else S3D_FWD(true, -1, -1); }
     else { if (fast) S3D_FWD(false, ACT_RELU, ACT_NONE); else S3D_FWD(false, -1, -1); }
 #undef S3D_FWD_K
 #undef S3D_FWD
@@ -1460,12 +1476,13 @@ int launch_forward(const _Float16* X, const _Float16* Wt, uint32_t B, uint32_t i
 }
 
 template <int W>
-int launch_backward(const _Float16* grad, const _Float16* X, const _Float16* Wt, const _Float16* fwd, uint32_t B,
-                    uint32_t in_dim, uint32_t out_dim, uint32_t n_layers, uint32_t act, _Float16* bwd,
-                    _Float16* grad_inputs, _Float16* grad_weights, float* partial, uint32_t accumulate, hipStream_t st) {
+int launch_backward(const BwdArgs& a, const BwdOpts& o) {
+    const _Float16 *grad = a.grad, *X = a.X, *fwd = a.fwd;
+    _Float16* bwd = a.bwd;
+    const uint32_t B = a.B, in_dim = a.in_dim, n_layers = a.n_layers;
     constexpr uint32_t MB = W / 32, KS = W / 16;
     const uint32_t NH = n_layers - 1;
-    const uint32_t nfr = MB + NH * MB * KS + (grad_inputs ? ((in_dim + 31) / 32) * KS : 0);
+    const uint32_t nfr = MB + NH * MB * KS + (a.grad_inputs ? ((in_dim + 31) / 32) * KS : 0);
     const size_t smem = (size_t)nfr * 64 * sizeof(half8);
     const uint32_t ntiles = B / 32;
     uint32_t grid = div_up<uint32_t>(ntiles, 4);
@@ -1475,12 +1492,12 @@ int launch_backward(const _Float16* grad, const _Float16* X, const _Float16* Wt,
         S3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ffmlp_dgrad<W, ACT_RELU>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
         S3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ffmlp_dgrad<W, -1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     }
-    if (act == ACT_RELU)
-        hipLaunchKernelGGL((k_ffmlp_dgrad<W, ACT_RELU>), dim3(grid), dim3(256), smem, st, grad, Wt, fwd, B, in_dim, out_dim, n_layers,
-                           act, bwd, grad_inputs, t_n_valid);
+    if (a.act == ACT_RELU)
+        hipLaunchKernelGGL((k_ffmlp_dgrad<W, ACT_RELU>), dim3(grid), dim3(256), smem, a.st, grad, a.Wt, fwd, B, in_dim, a.out_dim, n_layers,
+                           a.act, bwd, a.grad_inputs, o.n_valid);
     else
-        hipLaunchKernelGGL((k_ffmlp_dgrad<W, -1>), dim3(grid), dim3(256), smem, st, grad, Wt, fwd, B, in_dim, out_dim, n_layers,
-                           act, bwd, grad_inputs, t_n_valid);
+        hipLaunchKernelGGL((k_ffmlp_dgrad<W, -1>), dim3(grid), dim3(256), smem, a.st, grad, a.Wt, fwd, B, in_dim, a.out_dim, n_layers,
+                           a.act, bwd, a.grad_inputs, o.n_valid);
 
     // weight gradients, all layers in one launch
     WgradPlan plan;
@@ -1504,10 +1521,10 @@ int launch_backward(const _Float16* grad, const _Float16* X, const _Float16* Wt,
     }
     uint32_t nblk = div_up<uint32_t>(ntiles, 4);
     if (nblk > wgrad_blocks(W)) nblk = wgrad_blocks(W);
-    hipLaunchKernelGGL((k_ffmlp_wgrad<W>), dim3(nblk, plan.n), dim3(256), 0, st, plan, B, partial, t_n_valid);
+    hipLaunchKernelGGL((k_ffmlp_wgrad<W>), dim3(nblk, plan.n), dim3(256), 0, a.st, plan, B, a.partial, o.n_valid);
     const uint32_t widest = (uint32_t)W > in_dim ? (uint32_t)W : in_dim;
-    hipLaunchKernelGGL(k_ffmlp_wgrad_reduce, dim3(div_up<uint32_t>(W * widest * kReduceSplit, 256), plan.n), dim3(256), 0, st, plan, nblk,
-                       (const float*)partial, grad_weights, accumulate, t_found_inf, wgrad_pad(W));
+    hipLaunchKernelGGL(k_ffmlp_wgrad_reduce, dim3(div_up<uint32_t>(W * widest * kReduceSplit, 256), plan.n), dim3(256), 0, a.st, plan, nblk,
+                       (const float*)a.partial, a.grad_weights, a.accumulate, o.found_inf, wgrad_pad(W));
     return check_launch("ffmlp_backward");
 }
 
@@ -1522,9 +1539,8 @@ inline bool fused_backward_supported(uint32_t in_dim, uint32_t out_dim, uint32_t
 }
 
 template <int W, int NH, int IMB, int ACT, int KS0T>
-int launch_backward_fused_k(const _Float16* grad, const _Float16* X, const _Float16* Wt, uint32_t B, uint32_t in_dim,
-                            uint32_t out_dim, uint32_t act, _Float16* grad_inputs, _Float16* grad_weights, float* partial,
-                            uint32_t in_layout, uint32_t accumulate, hipStream_t st) {
+int launch_backward_fused_k(const BwdArgs& a, const BwdOpts& o) {
+    const uint32_t B = a.B, in_dim = a.in_dim;
     constexpr uint32_t MB = W / 32, KS = W / 16;
     // Wave mix of the two-role kernel, (compute waves, weight-gradient waves) per workgroup.  The compute wave of a 32-row tile
     // is 3.5x the work of its weight-gradient partner (profiles/r10_mlp_backward.md: 8.2 k against 2.3 k ticks per round), so one
@@ -1533,7 +1549,7 @@ int launch_backward_fused_k(const _Float16* grad, const _Float16* X, const _Floa
     // colour network 48.0 -> 45.5 us, density network 37.5 - 38.8 (six pairs) -> 36.9 us; 6 + 3 and 6 + 6 within noise of 6 + 2,
     // seven pairs 57 us (three waves per SIMD no longer fit the registers).
     constexpr int NC = 6, NG = 2;
-    const uint32_t nfrag = MB * (in_dim / 16) + NH * MB * KS + MB + NH * MB * KS + (grad_inputs ? IMB * KS : 0);
+    const uint32_t nfrag = MB * (in_dim / 16) + NH * MB * KS + MB + NH * MB * KS + (a.grad_inputs ? IMB * KS : 0);
     const uint32_t ntiles = B / 32;
     // (four tile owners per workgroup decide the partial count whatever the wave mix: s3d_ffmlp_wgrad_reduce_pair derives the
     //  layout of a deferred reduce from B alone; a workgroup of a small batch simply has idle streams)
@@ -1553,8 +1569,8 @@ int launch_backward_fused_k(const _Float16* grad, const _Float16* X, const _Floa
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         device_setup_done(attr_devs, dev);
     }
-    hipLaunchKernelGGL((k_ffmlp_backward_duo<W, NH, IMB, ACT, KS0T, NC, NG>), dim3(nblk), dim3((NC + NG) * 64), smem, st, grad, X, Wt,
-                       B, in_dim, out_dim, act, grad_inputs, partial, in_layout, t_n_valid, t_d_rgb, t_rgb_in, t_mid_bwd);
+    hipLaunchKernelGGL((k_ffmlp_backward_duo<W, NH, IMB, ACT, KS0T, NC, NG>), dim3(nblk), dim3((NC + NG) * 64), smem, a.st, a.grad, a.X,
+                       a.Wt, B, in_dim, a.out_dim, a.act, a.grad_inputs, a.partial, a.in_layout, o.n_valid, o.d_rgb, o.rgb_in, o.mid);
     WgradPlan plan;
     memset(&plan, 0, sizeof(plan));
     plan.n = NH + 2;
@@ -1562,19 +1578,16 @@ int launch_backward_fused_k(const _Float16* grad, const _Float16* X, const _Floa
     for (uint32_t m = 0; m < (uint32_t)NH; m++)
         plan.layer[1 + m] = WgradLayer{nullptr, nullptr, 0u, 0u, (uint32_t)W, (uint32_t)W, (uint32_t)(W * in_dim + m * W * W)};
     plan.layer[NH + 1] = WgradLayer{nullptr, nullptr, 0u, 0u, 16u, (uint32_t)W, (uint32_t)(W * in_dim + NH * W * W)};
-    if (accumulate != 2u)  // (2: the caller finishes several networks with one s3d_ffmlp_wgrad_reduce_pair)
-        hipLaunchKernelGGL(k_ffmlp_wgrad_reduce, dim3(div_up<uint32_t>(W * W * kReduceSplit, 256), plan.n), dim3(256), 0, st, plan, nblk,
-                           (const float*)partial, grad_weights, accumulate, t_found_inf, kWgradPad);
+    if (a.accumulate != 2u)  // (2: the caller finishes several networks with one s3d_ffmlp_wgrad_reduce_pair)
+        hipLaunchKernelGGL(k_ffmlp_wgrad_reduce, dim3(div_up<uint32_t>(W * W * kReduceSplit, 256), plan.n), dim3(256), 0, a.st, plan, nblk,
+                           (const float*)a.partial, a.grad_weights, a.accumulate, o.found_inf, kWgradPad);
     return check_launch("ffmlp_backward (fused)");
 }
 
 template <int W>
-int launch_backward_fused(const _Float16* grad, const _Float16* X, const _Float16* Wt, uint32_t B, uint32_t in_dim,
-                          uint32_t out_dim, uint32_t n_layers, uint32_t act, _Float16* gi, _Float16* gw, float* partial,
-                          uint32_t in_layout, uint32_t accumulate, hipStream_t st) {
-    const uint32_t NH = n_layers - 1, IMB = (in_dim + 31) / 32;
-#define S3D_FUSED_K(NHV, IMBV, ACTV, KSV) \
-    launch_backward_fused_k<W, NHV, IMBV, ACTV, KSV>(grad, X, Wt, B, in_dim, out_dim, act, gi, gw, partial, in_layout, accumulate, st)
+int launch_backward_fused(const BwdArgs& a, const BwdOpts& o) {
+    const uint32_t NH = a.n_layers - 1, in_dim = a.in_dim, IMB = (in_dim + 31) / 32, act = a.act;
+#define S3D_FUSED_K(NHV, IMBV, ACTV, KSV) launch_backward_fused_k<W, NHV, IMBV, ACTV, KSV>(a, o)
     // the hot path's networks (ReLU, in_dim a multiple of 32) get the layer-0 step count at compile time
 #define S3D_FUSED(NHV, IMBV)                                                                                  \
     (act == ACT_RELU ? (in_dim == 32u * IMBV ? S3D_FUSED_K(NHV, IMBV, ACT_RELU, 2 * IMBV) : S3D_FUSED_K(NHV, IMBV, ACT_RELU, 0)) \
@@ -1594,6 +1607,45 @@ int launch_backward_fused(const _Float16* grad, const _Float16* X, const _Float1
 #undef S3D_FUSED_K
 }
 
+// s3d_ffmlp_forward (forward_buffer) and s3d_ffmlp_inference (inference_buffer) behind one signature
+int ffmlp_forward(const uint16_t* inputs, const uint16_t* weights, uint32_t B, uint32_t input_dim, uint32_t output_dim,
+                  uint32_t hidden_dim, uint32_t num_layers, uint32_t activation, uint32_t output_activation,
+                  uint16_t* forward_buffer, uint16_t* inference_buffer, uint16_t* outputs, int input_layout, const int32_t* n_valid,
+                  float* rgb_head, const float* mid_dirs, float* mid_sigma, uint16_t* mid_color_in, uint16_t* mid_h0,
+                  s3d_stream_t stream) {
+    if (B == 0) return S3D_OK;
+    S3D_REQUIRE(!mid_color_in || (mid_dirs && mid_sigma && mid_h0 && !rgb_head && output_dim == 16),
+                "ffmlp_forward: the density head needs dirs, sigma, color_in and h0 (and no colour head)");
+    S3D_REQUIRE(inputs && weights && (outputs || rgb_head || mid_color_in), "ffmlp_forward: null pointer");
+    S3D_REQUIRE(!rgb_head || output_dim >= 3, "ffmlp_forward: the colour head reads outputs 0..2");
+    S3D_REQUIRE(input_layout == 0 || input_layout == 1, "ffmlp_forward: input_layout must be 0 (row-major) or 1 (level-major [in/2][B][2])");
+    if (int rc = check_shape(B, input_dim, output_dim, hidden_dim, num_layers)) return rc;
+    S3D_REQUIRE(output_dim == 16, "ffmlp_forward: the output must be padded to 16 columns (ffmlp.py:117)");
+    const FwdArgs a{(const _Float16*)inputs, (const _Float16*)weights, B, input_dim, output_dim, num_layers, activation, output_activation,
+                    (_Float16*)forward_buffer, (_Float16*)outputs, (uint32_t)input_layout, as_stream(stream)};
+    FwdOpts o{n_valid, rgb_head, MidFwd{}, (_Float16*)inference_buffer};
+    if (mid_color_in) {
+        o.mid.dirs = mid_dirs; o.mid.sigma = mid_sigma; o.mid.cin = (_Float16*)mid_color_in; o.mid.h0 = (_Float16*)mid_h0;
+        host_sh_norm(4, o.mid.K);
+    }
+    if (!ffmlp_native_shape(input_dim, hidden_dim, num_layers)) {
+        S3D_REQUIRE(input_layout == 0 && !n_valid && !rgb_head && !mid_color_in && outputs,
+                    "ffmlp_forward: hidden_dim %u / input_dim %u take the layer-by-layer path, which implements the reference's "
+                    "interface only (row-major inputs, no heads, no n_valid)", hidden_dim, input_dim);
+        S3D_REQUIRE(a.fwd || o.scratch, "ffmlp_forward: this shape needs forward_buffer [n, B, W] (training) or "
+                    "inference_buffer [2, B, W] (inference)");
+        return ffmlp_generic_forward(a.X, a.Wt, B, input_dim, hidden_dim, num_layers, activation, output_activation,
+                                     a.fwd ? a.fwd : o.scratch, a.fwd != nullptr, a.out, a.st);
+    }
+    switch (hidden_dim) {
+        case 64: return launch_forward<64>(a, o);
+        case 128:
+            S3D_REQUIRE(!rgb_head && !mid_color_in, "ffmlp_forward: the NGP heads belong to the 64-wide networks");
+            return launch_forward<128>(a, o);
+        default: return launch_forward<32>(a, o);
+    }
+}
+
 }  // namespace
 }  // namespace s3d
 
@@ -1604,43 +1656,9 @@ S3D_EXPORT int s3d_ffmlp_forward(const uint16_t* inputs, const uint16_t* weights
                                  uint32_t output_activation, uint16_t* forward_buffer, uint16_t* outputs,
                                  int input_layout, const int32_t* n_valid, float* rgb_head, const float* mid_dirs,
                                  float* mid_sigma, uint16_t* mid_color_in, uint16_t* mid_h0, s3d_stream_t stream) {
-    if (B == 0) return S3D_OK;
-    const RowLimitScope rows(n_valid);
-    struct HeadScope {
-        HeadScope(float* p, const float* d, float* s, uint16_t* c, uint16_t* h0) {
-            t_rgb_out = p;
-            t_mid_fwd = MidFwd{};
-            if (c) {
-                t_mid_fwd.dirs = d; t_mid_fwd.sigma = s; t_mid_fwd.cin = (_Float16*)c; t_mid_fwd.h0 = (_Float16*)h0;
-                host_sh_norm(4, t_mid_fwd.K);
-            }
-        }
-        ~HeadScope() { t_rgb_out = nullptr; t_mid_fwd = MidFwd{}; }
-    } head(rgb_head, mid_dirs, mid_sigma, mid_color_in, mid_h0);
-    S3D_REQUIRE(!mid_color_in || (mid_dirs && mid_sigma && mid_h0 && !rgb_head && output_dim == 16),
-                "ffmlp_forward: the density head needs dirs, sigma, color_in and h0 (and no colour head)");
-    S3D_REQUIRE(inputs && weights && (outputs || rgb_head || mid_color_in), "ffmlp_forward: null pointer");
-    S3D_REQUIRE(!rgb_head || output_dim >= 3, "ffmlp_forward: the colour head reads outputs 0..2");
-    S3D_REQUIRE(input_layout == 0 || input_layout == 1, "ffmlp_forward: input_layout must be 0 (row-major) or 1 (level-major [in/2][B][2])");
-    if (int rc = check_shape(B, input_dim, output_dim, hidden_dim, num_layers)) return rc;
-    S3D_REQUIRE(output_dim == 16, "ffmlp_forward: the output must be padded to 16 columns (ffmlp.py:117)");
-    const _Float16* X = (const _Float16*)inputs; const _Float16* Wt = (const _Float16*)weights;
-    _Float16* fb = (_Float16*)forward_buffer; _Float16* o = (_Float16*)outputs;
-    if (!ffmlp_native_shape(input_dim, hidden_dim, num_layers)) {
-        S3D_REQUIRE(input_layout == 0 && !n_valid && !rgb_head && !mid_color_in && outputs,
-                    "ffmlp_forward: hidden_dim %u / input_dim %u take the layer-by-layer path, which implements the reference's "
-                    "interface only (row-major inputs, no heads, no n_valid)", hidden_dim, input_dim);
-        S3D_REQUIRE(forward_buffer || t_generic_scratch, "ffmlp_forward: this shape needs forward_buffer [n, B, W] (training) or "
-                    "inference_buffer [2, B, W] (inference)");
-        return ffmlp_generic_forward(X, Wt, B, input_dim, hidden_dim, num_layers, activation, output_activation,
-                                     fb ? fb : t_generic_scratch, fb != nullptr, o, as_stream(stream));
-    }
-    if (hidden_dim == 64) return launch_forward<64>(X, Wt, B, input_dim, output_dim, num_layers, activation, output_activation, fb, o, (uint32_t)input_layout, as_stream(stream));
-    if (hidden_dim == 128) {
-        S3D_REQUIRE(!rgb_head && !mid_color_in, "ffmlp_forward: the NGP heads belong to the 64-wide networks");
-        return launch_forward<128>(X, Wt, B, input_dim, output_dim, num_layers, activation, output_activation, fb, o, (uint32_t)input_layout, as_stream(stream));
-    }
-    return launch_forward<32>(X, Wt, B, input_dim, output_dim, num_layers, activation, output_activation, fb, o, (uint32_t)input_layout, as_stream(stream));
+    return ffmlp_forward(inputs, weights, B, input_dim, output_dim, hidden_dim, num_layers, activation, output_activation,
+                         forward_buffer, nullptr, outputs, input_layout, n_valid, rgb_head, mid_dirs, mid_sigma, mid_color_in,
+                         mid_h0, stream);
 }
 
 S3D_EXPORT int s3d_ffmlp_inference(const uint16_t* inputs, const uint16_t* weights, uint32_t B, uint32_t input_dim,
@@ -1648,25 +1666,9 @@ S3D_EXPORT int s3d_ffmlp_inference(const uint16_t* inputs, const uint16_t* weigh
                                    uint32_t output_activation, uint16_t* inference_buffer, uint16_t* outputs,
                                    int input_layout, const int32_t* n_valid, float* rgb_head, const float* mid_dirs,
                                    float* mid_sigma, uint16_t* mid_color_in, uint16_t* mid_h0, s3d_stream_t stream) {
-    struct Scratch { explicit Scratch(_Float16* p) { t_generic_scratch = p; } ~Scratch() { t_generic_scratch = nullptr; } }
-        scratch((_Float16*)inference_buffer);  // (only the layer-by-layer path of the non-native shapes uses it: [2, B, W])
-    return s3d_ffmlp_forward(inputs, weights, B, input_dim, output_dim, hidden_dim, num_layers, activation,
-                             output_activation, nullptr, outputs, input_layout, n_valid, rgb_head, mid_dirs, mid_sigma,
-                             mid_color_in, mid_h0, stream);
-}
-
-// CUs of the current device, cached per device ordinal (resident-workgroup counts of the persistent kernels)
-static uint32_t cu_count() {
-    static std::atomic<uint32_t> cus[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return 256;
-    uint32_t n = cus[dev].load(std::memory_order_relaxed);
-    if (!n) {
-        int v = 0;
-        n = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? (uint32_t)v : 256u;
-        cus[dev].store(n, std::memory_order_relaxed);
-    }
-    return n;
+    return ffmlp_forward(inputs, weights, B, input_dim, output_dim, hidden_dim, num_layers, activation, output_activation,
+                         nullptr, inference_buffer, outputs, input_layout, n_valid, rgb_head, mid_dirs, mid_sigma, mid_color_in,
+                         mid_h0, stream);
 }
 
 S3D_EXPORT int s3d_ffmlp_ngp_pair_inference(const uint16_t* inputs, const uint16_t* weights_sigma, const uint16_t* weights_color,
@@ -1700,7 +1702,7 @@ S3D_EXPORT int s3d_ffmlp_ngp_pair_inference(const uint16_t* inputs, const uint16
     // persistent workgroups, as many as are resident at once: two per CU (NGP: 60 KB of LDS, 114 registers), one per CU (Seal:
     // 148 registers).  [384 workgroups — three waves per SIMD on paper — left half of the CUs with two workgroups and half with
     // one: 93 us per render iteration of 1.6e6 rows against 79 at 512; Seal variant 118 against 98 at 256]
-    const uint32_t cap = (seal ? 1u : 2u) * cu_count() * 8u / kPairWaves;
+    const uint32_t cap = (seal ? 1u : 2u) * device_cus() * 8u / kPairWaves;
     if (grid > cap) grid = cap;
     if (seal)
         hipLaunchKernelGGL(k_ffmlp_ngp_pair<true>, dim3(grid), dim3(kPairWaves * 64), smem, as_stream(stream), (const _Float16*)inputs, nets, B,
@@ -1764,14 +1766,6 @@ S3D_EXPORT int s3d_ffmlp_backward(const uint16_t* grad, const uint16_t* inputs, 
                                   const float* grad_rgb, const float* rgb_head, const float* mid_grad_sigma,
                                   const uint16_t* mid_grad_color_in, const uint16_t* mid_h0, s3d_stream_t stream) {
     (void)output_activation;
-    const RowLimitScope rows(n_valid, found_inf);
-    struct HeadScope {
-        HeadScope(const float* g, const float* y, const float* gs, const uint16_t* gc, const uint16_t* h0) {
-            t_d_rgb = g; t_rgb_in = y;
-            t_mid_bwd = MidBwd{gs, (const _Float16*)gc, (const _Float16*)h0};
-        }
-        ~HeadScope() { t_d_rgb = nullptr; t_rgb_in = nullptr; t_mid_bwd = MidBwd{}; }
-    } head(grad_rgb, rgb_head, mid_grad_sigma, mid_grad_color_in, mid_h0);
     S3D_REQUIRE(!mid_grad_color_in || (mid_h0 && !forward_buffer && !grad_rgb && output_dim == 16),
                 "ffmlp_backward: the density head needs grad_color_in and h0 and is implemented by the fused backward");
     S3D_REQUIRE((grad_rgb == nullptr) == (rgb_head == nullptr), "ffmlp_backward: the colour head needs both grad_rgb and rgb_head");
@@ -1792,37 +1786,27 @@ S3D_EXPORT int s3d_ffmlp_backward(const uint16_t* grad, const uint16_t* inputs, 
     S3D_REQUIRE(!calc_grad_inputs || grad_inputs, "ffmlp_backward: grad_inputs requested but null");
     S3D_REQUIRE(workspace && workspace_bytes >= s3d_ffmlp_backward_workspace_size(input_dim, output_dim, hidden_dim, num_layers),
                 "ffmlp_backward: workspace too small");
-    _Float16* gi = calc_grad_inputs ? (_Float16*)grad_inputs : nullptr;
+    const BwdArgs a{(const _Float16*)grad, (const _Float16*)inputs, (const _Float16*)weights, (const _Float16*)forward_buffer,
+                    B, input_dim, output_dim, num_layers, activation, (_Float16*)backward_buffer,
+                    calc_grad_inputs ? (_Float16*)grad_inputs : nullptr, (_Float16*)grad_weights, (float*)workspace, workspace_bytes,
+                    (uint32_t)input_layout, accumulate, as_stream(stream)};
+    const BwdOpts o{n_valid, found_inf, grad_rgb, rgb_head,
+                    MidBwd{mid_grad_sigma, (const _Float16*)mid_grad_color_in, (const _Float16*)mid_h0}};
     if (!ffmlp_native_shape(input_dim, hidden_dim, num_layers)) {
         S3D_REQUIRE(forward_buffer && backward_buffer && grad && input_layout == 0 && !n_valid && !grad_rgb && !mid_grad_color_in,
                     "ffmlp_backward: hidden_dim %u / input_dim %u take the layer-by-layer path: forward_buffer and backward_buffer "
                     "[n, B, W], row-major inputs, no heads, no n_valid", hidden_dim, input_dim);
-        return ffmlp_generic_backward((const _Float16*)grad, (const _Float16*)inputs, (const _Float16*)weights, (const _Float16*)forward_buffer,
-                                      B, input_dim, hidden_dim, num_layers, activation, (_Float16*)backward_buffer, gi,
-                                      (_Float16*)grad_weights, accumulate != 0, found_inf, (float*)workspace, workspace_bytes, as_stream(stream));
+        return ffmlp_generic_backward(a.grad, a.X, a.Wt, a.fwd, B, input_dim, hidden_dim, num_layers, activation, a.bwd, a.grad_inputs,
+                                      a.grad_weights, accumulate != 0, found_inf, a.partial, a.partial_bytes, a.st);
     }
-    if (!forward_buffer) {
-        S3D_REQUIRE(fused_backward_supported(input_dim, 16, hidden_dim, num_layers, activation),
-                    "ffmlp_backward: this network shape needs forward_buffer/backward_buffer (s3d_ffmlp_fused_backward_supported)");
-        if (hidden_dim == 64)
-            return launch_backward_fused<64>((const _Float16*)grad, (const _Float16*)inputs, (const _Float16*)weights, B, input_dim,
-                                             output_dim, num_layers, activation, gi, (_Float16*)grad_weights, (float*)workspace,
-                                             (uint32_t)input_layout, accumulate, as_stream(stream));
-        return launch_backward_fused<32>((const _Float16*)grad, (const _Float16*)inputs, (const _Float16*)weights, B, input_dim,
-                                         output_dim, num_layers, activation, gi, (_Float16*)grad_weights, (float*)workspace,
-                                         (uint32_t)input_layout, accumulate, as_stream(stream));
+    const bool fused = !forward_buffer;  // (re-computing backward: no stored activations)
+    S3D_REQUIRE(!fused || fused_backward_supported(input_dim, 16, hidden_dim, num_layers, activation),
+                "ffmlp_backward: this network shape needs forward_buffer/backward_buffer (s3d_ffmlp_fused_backward_supported)");
+    switch (hidden_dim) {
+        case 64: return fused ? launch_backward_fused<64>(a, o) : launch_backward<64>(a, o);
+        case 128: return launch_backward<128>(a, o);  // (fused_backward_supported: widths 32 and 64)
+        default: return fused ? launch_backward_fused<32>(a, o) : launch_backward<32>(a, o);
     }
-    if (hidden_dim == 64)
-        return launch_backward<64>((const _Float16*)grad, (const _Float16*)inputs, (const _Float16*)weights,
-                                   (const _Float16*)forward_buffer, B, input_dim, output_dim, num_layers, activation,
-                                   (_Float16*)backward_buffer, gi, (_Float16*)grad_weights, (float*)workspace, accumulate, as_stream(stream));
-    if (hidden_dim == 128)
-        return launch_backward<128>((const _Float16*)grad, (const _Float16*)inputs, (const _Float16*)weights,
-                                    (const _Float16*)forward_buffer, B, input_dim, output_dim, num_layers, activation,
-                                    (_Float16*)backward_buffer, gi, (_Float16*)grad_weights, (float*)workspace, accumulate, as_stream(stream));
-    return launch_backward<32>((const _Float16*)grad, (const _Float16*)inputs, (const _Float16*)weights,
-                               (const _Float16*)forward_buffer, B, input_dim, output_dim, num_layers, activation,
-                               (_Float16*)backward_buffer, gi, (_Float16*)grad_weights, (float*)workspace, accumulate, as_stream(stream));
 }
 
 S3D_EXPORT int s3d_ffmlp_fused_backward_supported(uint32_t input_dim, uint32_t output_dim, uint32_t hidden_dim,

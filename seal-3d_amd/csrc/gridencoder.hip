@@ -1771,11 +1771,6 @@ __global__ void __launch_bounds__(256) k_table_nonfinite(const T* __restrict__ t
         bad |= !(fabsf(Acc<T>::to_f(table[i])) <= 3.402823466e38f);
     if (bad) *found_inf = 1.0f;
 }
-// found_inf of the entry point being served on this thread, and whether the path taken has reported into it
-static thread_local float* t_found_inf = nullptr;
-static thread_local bool t_reported = false;
-static thread_local const struct GridAdam* t_adam = nullptr;  // s3d_grid_encode_backward_adam: the update to apply in the accumulate
-static thread_local bool t_adam_applied = false;
 
 // gridencoder.cu:340-366
 template <typename T, uint32_t D, uint32_t C>
@@ -1933,10 +1928,29 @@ inline FwdPlan balance_forward_plan(uint32_t L, const LevelScales& sc, bool bala
     return p;
 }
 
+// One forward call as launch_forward sees it: table and output pointers still untyped (cast to T there); emb_b / outputs_b
+// are the second table of s3d_grid_encode_forward_pair, or nullptr
+struct GridFwd {
+    const float* inputs;
+    const void *emb, *emb_b;
+    const int32_t* offsets;
+    void *outputs, *outputs_b, *dy_dx;
+    uint32_t B, C, L, gridtype, interp;
+    bool ac;
+    LevelScales sc;
+    hipStream_t st;
+};
+
 template <typename T, uint32_t D>
-int launch_forward(const float* inputs, const T* emb, const int32_t* offsets, T* outputs, uint32_t B, uint32_t C,
-                   uint32_t L, const LevelScales& sc, T* dy_dx, uint32_t gridtype, bool ac, uint32_t interp,
-                   hipStream_t st, const T* emb_b = nullptr, T* outputs_b = nullptr) {
+int launch_forward(const GridFwd& a) {
+    const T *emb = (const T*)a.emb, *emb_b = (const T*)a.emb_b;
+    T *outputs = (T*)a.outputs, *outputs_b = (T*)a.outputs_b, *dy_dx = (T*)a.dy_dx;
+    const float* inputs = a.inputs;
+    const int32_t* offsets = a.offsets;
+    const uint32_t B = a.B, C = a.C, L = a.L, gridtype = a.gridtype, interp = a.interp;
+    const LevelScales& sc = a.sc;
+    const bool ac = a.ac;
+    hipStream_t st = a.st;
     // (chunk slots of the lane-pair kernel: the inference loop's launches — `live` rows, all of them filled — keep one
     //  workgroup per chunk; everything else walks its chunks from 2,048 slots per XCD, i.e. unchanged up to 2^19 rows)
     const uint32_t chunks = div_up<uint32_t>(B, kFwdBlock);
@@ -2050,27 +2064,39 @@ inline BinLayout3 bin_layout3(uint32_t B, uint32_t D, uint32_t C, uint32_t L, ui
     return o;
 }
 
-// CUs of the current device (workgroups of the persistent accumulate), cached per device ordinal
-inline uint32_t device_cus() {
-    static std::atomic<uint32_t> cus[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return 256;
-    uint32_t n = cus[dev].load(std::memory_order_relaxed);
-    if (!n) {
-        int v = 0;
-        n = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? (uint32_t)v : 256u;
-        cus[dev].store(n, std::memory_order_relaxed);
-    }
-    return n;
-}
-
 // control block of the third generation: hdr[kMaxLevels] | ticket (byte 128) | cursor[L][smax][NSUB] (x kCurStride words) | ovn[L][smax]
 inline size_t bin3_control_bytes(const BinLayout3& lay, uint32_t L) { return align256(lay.ovn + (size_t)L * lay.smax * 4); }
 
+// One backward call as the launch helpers below see it: the entry point's arguments, table and gradient pointers still
+// untyped (the templated leaves cast them to T), and what the path taken reports back
+struct GridBwd {
+    const void *grad, *dy_dx;
+    void *grad_emb, *grad_inputs;
+    const float* inputs;
+    const int32_t* offsets;
+    uint32_t B, C, L, max_level_rows, gridtype, interp;
+    bool ac;
+    LevelScales sc;
+    unsigned char *ws, *control;
+    size_t ws_bytes, control_bytes;
+    int force_path;  // 0 auto: binned for large batches; 1 direct atomics; 2 binned
+    hipStream_t st;
+    float* found_inf;      // s3d_grid_encode_backward(found_inf), or nullptr
+    const GridAdam* adam;  // s3d_grid_encode_backward_adam: the update to apply in the accumulate, or nullptr
+};
+struct GridBwdResult {
+    bool reported;  // the path taken has written found_inf while it accumulated (otherwise the caller checks the table)
+    bool applied;   // the accumulate applied `adam`
+};
+
+// `control`: the caller's control block if it is large enough for this layout, else nullptr
 template <typename T, uint32_t D, uint32_t C, bool FIXED24>
-int launch_binned3(const T* grad, const float* inputs, const int32_t* offsets, T* grad_emb, uint32_t B, uint32_t L,
-                   const LevelScales& sc, uint32_t gridtype, bool ac, uint32_t interp, unsigned char* ws, const BinLayout3& lay,
-                   unsigned char* control, hipStream_t st) {
+int launch_binned3(const GridBwd& a, const BinLayout3& lay, unsigned char* control, GridBwdResult& res) {
+    const T* grad = (const T*)a.grad;
+    T* grad_emb = (T*)a.grad_emb;
+    const uint32_t B = a.B, L = a.L;
+    unsigned char* ws = a.ws;
+    hipStream_t st = a.st;
     constexpr uint32_t P = S3D_BIN3_P;
     constexpr uint32_t K = 1u << D;
     constexpr uint32_t stage_max = 4 * kBinMaxSlices * 4 + P * K * 8;  // counters, run starts, run table (8 B), staged records
@@ -2102,16 +2128,17 @@ int launch_binned3(const T* grad, const float* inputs, const int32_t* offsets, T
     }
     if constexpr (!FIXED24)
         hipLaunchKernelGGL((k_bin_amax<T, D, C>), dim3(std::min<uint32_t>(div_up<uint32_t>(B, 1024), 64u), L), dim3(1024), 0, st, grad,
-                           inputs, B, sc, hdr);
+                           a.inputs, B, a.sc, hdr);
     const uint32_t cus = device_cus();
     for (uint32_t l0 = 0; l0 < L; l0 += lay.levels_per_pass) {
         const uint32_t nl = (L - l0 < lay.levels_per_pass) ? L - l0 : lay.levels_per_pass;
-        hipLaunchKernelGGL((k_bin_scatter6<T, D, C, FIXED24, P>), dim3(lay.chunks, nl), dim3(P), stage, st, grad, inputs, offsets, B, l0,
-                           sc, hdr, cursor, ovn, ovl, lay.smax, lay.chunks, lay.cap, keys, vals, skeys, svals, gridtype, ac, interp);
+        hipLaunchKernelGGL((k_bin_scatter6<T, D, C, FIXED24, P>), dim3(lay.chunks, nl), dim3(P), stage, st, grad, a.inputs, a.offsets, B,
+                           l0, a.sc, hdr, cursor, ovn, ovl, lay.smax, lay.chunks, lay.cap, keys, vals, skeys, svals, a.gridtype, a.ac,
+                           a.interp);
         const uint32_t items = lay.smax * nl;
         bool fused = false;
         if constexpr (FIXED24 && sizeof(T) == 2 && C == 2) {
-            if (t_adam && nl == L) {  // (one pass covers every level: the skip decision needs all poison words up front)
+            if (a.adam && nl == L) {  // (one pass covers every level: the skip decision needs all poison words up front)
                 static std::atomic<uint64_t> attr_adam{0};
                 int dev2;
                 if (device_needs_setup(attr_adam, &dev2)) {
@@ -2121,39 +2148,43 @@ int launch_binned3(const T* grad, const float* inputs, const int32_t* offsets, T
                 }
                 hipLaunchKernelGGL((k_bin_accumulate6<T, D, C, FIXED24, P, true>), dim3(std::min(items, cus * kBinAccPerCu)), dim3(kBinAccThreads),
                                    kBinAccBytes, st, (const uint16_t*)keys, (const uint32_t*)vals, (const uint16_t*)skeys, (const uint32_t*)svals,
-                                   offsets, grad_emb, B, l0, nl, hdr, done, cursor, ovn, (const uint2*)ovl, lay.smax, lay.chunks, lay.cap,
-                                   t_found_inf, *t_adam);
+                                   a.offsets, grad_emb, B, l0, nl, hdr, done, cursor, ovn, (const uint2*)ovl, lay.smax, lay.chunks, lay.cap,
+                                   a.found_inf, *a.adam);
                 fused = true;
-                t_adam_applied = true;
+                res.applied = true;
             }
         }
         if (!fused)
         hipLaunchKernelGGL((k_bin_accumulate6<T, D, C, FIXED24, P>), dim3(std::min(items, cus * kBinAccPerCu)), dim3(kBinAccThreads), kBinAccBytes, st,
-                           (const uint16_t*)keys, (const uint32_t*)vals, (const uint16_t*)skeys, (const uint32_t*)svals, offsets,
-                           grad_emb, B, l0, nl, hdr, done, cursor, ovn, (const uint2*)ovl, lay.smax, lay.chunks, lay.cap, t_found_inf, GridAdam{});
+                           (const uint16_t*)keys, (const uint32_t*)vals, (const uint16_t*)skeys, (const uint32_t*)svals, a.offsets,
+                           grad_emb, B, l0, nl, hdr, done, cursor, ovn, (const uint2*)ovl, lay.smax, lay.chunks, lay.cap, a.found_inf, GridAdam{});
     }
-    t_reported = true;
+    res.reported = true;
     return check_launch("grid_encode_backward");
 }
 
 template <typename T, uint32_t D, uint32_t C>
-int launch_backward_c(const T* grad, const float* inputs, const int32_t* offsets, uint32_t max_level_rows, T* grad_emb,
-                      uint32_t B, uint32_t L, const LevelScales& sc, const T* dy_dx, T* grad_inputs, uint32_t gridtype, bool ac,
-                      uint32_t interp, unsigned char* ws, size_t ws_bytes, int force_path, unsigned char* control, size_t control_bytes,
-                      hipStream_t st) {
-    const BinLayout lay = bin_layout(B, D, C, L, max_level_rows, sizeof(T));
-    const bool bin_ok = lay.ok && ws && ws_bytes >= lay.total;
-    // 0 auto: binned for large batches; 1 direct atomics; 2 binned
-    const bool binned = bin_ok && (force_path >= 2 || (force_path == 0 && B >= kBinnedMinPoints));
+int launch_backward_c(const GridBwd& a, GridBwdResult& res) {
+    const T *grad = (const T*)a.grad, *dy_dx = (const T*)a.dy_dx;
+    T *grad_emb = (T*)a.grad_emb, *grad_inputs = (T*)a.grad_inputs;
+    const float* inputs = a.inputs;
+    const int32_t* offsets = a.offsets;
+    const uint32_t B = a.B, L = a.L, gridtype = a.gridtype, interp = a.interp;
+    const LevelScales& sc = a.sc;
+    unsigned char* ws = a.ws;
+    hipStream_t st = a.st;
+    const BinLayout lay = bin_layout(B, D, C, L, a.max_level_rows, sizeof(T));
+    const bool bin_ok = lay.ok && ws && a.ws_bytes >= lay.total;
+    const bool binned = bin_ok && (a.force_path >= 2 || (a.force_path == 0 && B >= kBinnedMinPoints));
     if constexpr (sizeof(T) * C == 4) {  // one 32-bit value word per record (fp16 C = 2, fp32 C = 1)
-        const BinLayout3 lay3 = bin_layout3(B, D, C, L, max_level_rows, sizeof(T));
-        if (binned && lay3.ok && ws && ws_bytes >= lay3.total) {  // 6-byte records, XCD-private sub-buckets
+        const BinLayout3 lay3 = bin_layout3(B, D, C, L, a.max_level_rows, sizeof(T));
+        if (binned && lay3.ok && ws && a.ws_bytes >= lay3.total) {  // 6-byte records, XCD-private sub-buckets
             int rc;
-            unsigned char* cb = (control && control_bytes >= bin3_control_bytes(lay3, L)) ? control : nullptr;
+            unsigned char* cb = (a.control && a.control_bytes >= bin3_control_bytes(lay3, L)) ? a.control : nullptr;
             if (sizeof(T) == 2 && ((uint64_t)B << D) <= (1ull << 23))
-                rc = launch_binned3<T, D, C, true>(grad, inputs, offsets, grad_emb, B, L, sc, gridtype, ac, interp, ws, lay3, cb, st);
+                rc = launch_binned3<T, D, C, true>(a, lay3, cb, res);
             else
-                rc = launch_binned3<T, D, C, false>(grad, inputs, offsets, grad_emb, B, L, sc, gridtype, ac, interp, ws, lay3, cb, st);
+                rc = launch_binned3<T, D, C, false>(a, lay3, cb, res);
             if (rc != S3D_OK) return rc;
             if (dy_dx && grad_inputs)
                 hipLaunchKernelGGL((k_grid_input_backward<T, D, C>), dim3(div_up<uint32_t>(B * D, 256)), dim3(256), 0, st, grad,
@@ -2164,7 +2195,6 @@ int launch_backward_c(const T* grad, const float* inputs, const int32_t* offsets
     if (binned) {
         using V = typename FeatVec<T, C>::type;
         constexpr uint32_t P = bin_chunk_points<T, D, C>();
-        constexpr uint32_t K = 1u << D;
         constexpr uint32_t stage = 2 * kBinMaxSlices * 4;  // slice counters + reserved bucket offsets
         static std::atomic<uint64_t> attr_devs{0};
         int dev;
@@ -2186,18 +2216,18 @@ int launch_backward_c(const T* grad, const float* inputs, const int32_t* offsets
         hipLaunchKernelGGL(k_zero_words, dim3(div_up<uint32_t>(clear_words, 1024)), dim3(1024), 0, st, hdr, clear_words);
         const uint32_t ppb = div_up<uint32_t>(div_up<uint32_t>(B, kBinCountChunks), kBinCountThreads) * kBinCountThreads;
         hipLaunchKernelGGL((k_bin_count<T, D, C>), dim3(div_up<uint32_t>(B, ppb), L), dim3(kBinCountThreads), 0, st, grad, inputs,
-                           offsets, B, ppb, sc, hdr, tot, lay.smax, gridtype, ac, interp);
+                           offsets, B, ppb, sc, hdr, tot, lay.smax, gridtype, a.ac, interp);
         for (uint32_t l0 = 0; l0 < L; l0 += lay.levels_per_pass) {
             const uint32_t nl = (L - l0 < lay.levels_per_pass) ? L - l0 : lay.levels_per_pass;
             hipLaunchKernelGGL((k_bin_scatter<T, D, C>), dim3(lay.chunks, nl), dim3(P / kBinQuad), stage, st, grad, inputs, offsets, B, l0, sc,
-                               (const uint32_t*)hdr, (const uint32_t*)tot, cursor, lay.smax, keys, vals, gridtype, ac, interp);
+                               (const uint32_t*)hdr, (const uint32_t*)tot, cursor, lay.smax, keys, vals, gridtype, a.ac, interp);
             hipLaunchKernelGGL((k_bin_accumulate<T, D, C>), dim3(lay.smax, nl), dim3(kBinAccThreads), kBinAccBytes, st,
                                (const uint32_t*)keys, (const V*)vals, offsets, grad_emb, B, l0, (const uint32_t*)hdr,
                                (const uint32_t*)tot, lay.smax);
         }
     } else {
         hipLaunchKernelGGL((k_grid_backward<T, D, C>), dim3(xcd_grid(B)), dim3(kFwdBlock), 0, st, grad, inputs, offsets,
-                           grad_emb, B, L, sc, gridtype, ac, interp);
+                           grad_emb, B, L, sc, gridtype, a.ac, interp);
     }
     if (dy_dx && grad_inputs)
         hipLaunchKernelGGL((k_grid_input_backward<T, D, C>), dim3(div_up<uint32_t>(B * D, 256)), dim3(256), 0, st, grad,
@@ -2206,19 +2236,16 @@ int launch_backward_c(const T* grad, const float* inputs, const int32_t* offsets
 }
 
 template <typename T, uint32_t D>
-int launch_backward(const T* grad, const float* inputs, const int32_t* offsets, uint32_t max_level_rows,
-                    T* grad_emb, uint32_t B, uint32_t C, uint32_t L, const LevelScales& sc, const T* dy_dx, T* grad_inputs, uint32_t gridtype,
-                    bool ac, uint32_t interp, unsigned char* ws, size_t ws_bytes, int force_path, unsigned char* control, size_t control_bytes,
-                    hipStream_t st) {
-    switch (C) {
+int launch_backward(const GridBwd& a, GridBwdResult& res) {
+    switch (a.C) {
         case 1:
             if constexpr (sizeof(T) == 2) {
                 set_error("GridEncoding: fp16 tables need an even C (the reference forces fp32 when C is odd, grid.py:42)");
                 return S3D_ERR_UNSUPPORTED;
-            } else return launch_backward_c<T, D, 1>(grad, inputs, offsets, max_level_rows, grad_emb, B, L, sc, dy_dx, grad_inputs, gridtype, ac, interp, ws, ws_bytes, force_path, control, control_bytes, st);
-        case 2: return launch_backward_c<T, D, 2>(grad, inputs, offsets, max_level_rows, grad_emb, B, L, sc, dy_dx, grad_inputs, gridtype, ac, interp, ws, ws_bytes, force_path, control, control_bytes, st);
-        case 4: return launch_backward_c<T, D, 4>(grad, inputs, offsets, max_level_rows, grad_emb, B, L, sc, dy_dx, grad_inputs, gridtype, ac, interp, ws, ws_bytes, force_path, control, control_bytes, st);
-        case 8: return launch_backward_c<T, D, 8>(grad, inputs, offsets, max_level_rows, grad_emb, B, L, sc, dy_dx, grad_inputs, gridtype, ac, interp, ws, ws_bytes, force_path, control, control_bytes, st);
+            } else return launch_backward_c<T, D, 1>(a, res);
+        case 2: return launch_backward_c<T, D, 2>(a, res);
+        case 4: return launch_backward_c<T, D, 4>(a, res);
+        case 8: return launch_backward_c<T, D, 8>(a, res);
         default: set_error("GridEncoding: C must be 1, 2, 4, or 8."); return S3D_ERR_UNSUPPORTED;
     }
 }
@@ -2270,6 +2297,14 @@ S3D_EXPORT void s3d_grid_level_scales(uint32_t L, float S, uint32_t H, float* sc
         case 5: return CALL5;                                                             \
         default: set_error("GridEncoding: D must be 2, 3, 4, or 5."); return S3D_ERR_UNSUPPORTED; \
     }
+// FN<float | __half, D>(...) by dtype (validated by the caller) and D; returns from the enclosing function
+#define S3D_DISPATCH_TD(DTYPE, D, FN, ...)                                                                       \
+    if ((DTYPE) == S3D_F32) {                                                                                    \
+        S3D_DISPATCH_D(D, (FN<float, 2>(__VA_ARGS__)), (FN<float, 3>(__VA_ARGS__)), (FN<float, 4>(__VA_ARGS__)), \
+                       (FN<float, 5>(__VA_ARGS__)))                                                              \
+    }                                                                                                            \
+    S3D_DISPATCH_D(D, (FN<__half, 2>(__VA_ARGS__)), (FN<__half, 3>(__VA_ARGS__)), (FN<__half, 4>(__VA_ARGS__)),  \
+                   (FN<__half, 5>(__VA_ARGS__)))
 
 S3D_EXPORT int s3d_grid_encode_forward(const float* inputs, const void* embeddings, const int32_t* offsets,
                                        void* outputs, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
@@ -2284,25 +2319,12 @@ S3D_EXPORT int s3d_grid_encode_forward(const float* inputs, const void* embeddin
     S3D_REQUIRE(L >= 1 && L <= kMaxLevels, "grid_encode_forward: L must be in [1, %u]", kMaxLevels);
     S3D_REQUIRE(dtype == S3D_F32 || dtype == S3D_F16, "grid_encode_forward: dtype must be f32 or f16");
     S3D_REQUIRE((uint64_t)B * L * C < (1ull << 32), "grid_encode_forward: B*L*C overflows 32 bits");
-    LevelScales sc;
-    host_scales(L, S, H, sc, bound, n_valid);
-    sc.live = live;
-    sc.live_stride = live ? (live_stride ? live_stride : 1u) : 0u;
-    hipStream_t st = as_stream(stream);
-    const bool ac = align_corners != 0;
-    if (dtype == S3D_F32) {
-        const float* e = (const float*)embeddings; float* o = (float*)outputs; float* j = (float*)dy_dx;
-        S3D_DISPATCH_D(D, (launch_forward<float, 2>(inputs, e, offsets, o, B, C, L, sc, j, gridtype, ac, interp, st)),
-                       (launch_forward<float, 3>(inputs, e, offsets, o, B, C, L, sc, j, gridtype, ac, interp, st)),
-                       (launch_forward<float, 4>(inputs, e, offsets, o, B, C, L, sc, j, gridtype, ac, interp, st)),
-                       (launch_forward<float, 5>(inputs, e, offsets, o, B, C, L, sc, j, gridtype, ac, interp, st)))
-    } else {
-        const __half* e = (const __half*)embeddings; __half* o = (__half*)outputs; __half* j = (__half*)dy_dx;
-        S3D_DISPATCH_D(D, (launch_forward<__half, 2>(inputs, e, offsets, o, B, C, L, sc, j, gridtype, ac, interp, st)),
-                       (launch_forward<__half, 3>(inputs, e, offsets, o, B, C, L, sc, j, gridtype, ac, interp, st)),
-                       (launch_forward<__half, 4>(inputs, e, offsets, o, B, C, L, sc, j, gridtype, ac, interp, st)),
-                       (launch_forward<__half, 5>(inputs, e, offsets, o, B, C, L, sc, j, gridtype, ac, interp, st)))
-    }
+    GridFwd a{inputs, embeddings, nullptr, offsets, outputs, nullptr, dy_dx, B, C, L, gridtype, interp, align_corners != 0,
+              LevelScales{}, as_stream(stream)};
+    host_scales(L, S, H, a.sc, bound, n_valid);
+    a.sc.live = live;
+    a.sc.live_stride = live ? (live_stride ? live_stride : 1u) : 0u;
+    S3D_DISPATCH_TD(dtype, D, launch_forward, a)
 }
 
 S3D_EXPORT int s3d_grid_encode_forward_pair(const float* inputs, const void* embeddings_a, const void* embeddings_b,
@@ -2316,27 +2338,12 @@ S3D_EXPORT int s3d_grid_encode_forward_pair(const float* inputs, const void* emb
     S3D_REQUIRE(L >= 1 && L <= kMaxLevels, "grid_encode_forward_pair: L must be in [1, %u]", kMaxLevels);
     S3D_REQUIRE(dtype == S3D_F32 || dtype == S3D_F16, "grid_encode_forward_pair: dtype must be f32 or f16");
     S3D_REQUIRE((uint64_t)B * L * C < (1ull << 32), "grid_encode_forward_pair: B*L*C overflows 32 bits");
-    LevelScales sc;
-    host_scales(L, S, H, sc, bound, n_valid);
-    sc.live = live;
-    sc.live_stride = live ? (live_stride ? live_stride : 1u) : 0u;
-    hipStream_t st = as_stream(stream);
-    const bool ac = align_corners != 0;
-    if (dtype == S3D_F32) {
-        const float* e = (const float*)embeddings_a; float* o = (float*)outputs_a;
-        const float* e2 = (const float*)embeddings_b; float* o2 = (float*)outputs_b;
-        S3D_DISPATCH_D(D, (launch_forward<float, 2>(inputs, e, offsets, o, B, C, L, sc, nullptr, gridtype, ac, interp, st, e2, o2)),
-                       (launch_forward<float, 3>(inputs, e, offsets, o, B, C, L, sc, nullptr, gridtype, ac, interp, st, e2, o2)),
-                       (launch_forward<float, 4>(inputs, e, offsets, o, B, C, L, sc, nullptr, gridtype, ac, interp, st, e2, o2)),
-                       (launch_forward<float, 5>(inputs, e, offsets, o, B, C, L, sc, nullptr, gridtype, ac, interp, st, e2, o2)))
-    } else {
-        const __half* e = (const __half*)embeddings_a; __half* o = (__half*)outputs_a;
-        const __half* e2 = (const __half*)embeddings_b; __half* o2 = (__half*)outputs_b;
-        S3D_DISPATCH_D(D, (launch_forward<__half, 2>(inputs, e, offsets, o, B, C, L, sc, nullptr, gridtype, ac, interp, st, e2, o2)),
-                       (launch_forward<__half, 3>(inputs, e, offsets, o, B, C, L, sc, nullptr, gridtype, ac, interp, st, e2, o2)),
-                       (launch_forward<__half, 4>(inputs, e, offsets, o, B, C, L, sc, nullptr, gridtype, ac, interp, st, e2, o2)),
-                       (launch_forward<__half, 5>(inputs, e, offsets, o, B, C, L, sc, nullptr, gridtype, ac, interp, st, e2, o2)))
-    }
+    GridFwd a{inputs, embeddings_a, embeddings_b, offsets, outputs_a, outputs_b, nullptr, B, C, L, gridtype, interp, align_corners != 0,
+              LevelScales{}, as_stream(stream)};
+    host_scales(L, S, H, a.sc, bound, n_valid);
+    a.sc.live = live;
+    a.sc.live_stride = live ? (live_stride ? live_stride : 1u) : 0u;
+    S3D_DISPATCH_TD(dtype, D, launch_forward, a)
 }
 
 template <uint32_t D>
@@ -2377,15 +2384,14 @@ S3D_EXPORT size_t s3d_grid_encode_backward_control_size(uint32_t D, uint32_t C, 
     return lay3.ok ? bin3_control_bytes(lay3, L) : 0;
 }
 
-S3D_EXPORT int s3d_grid_encode_backward(const void* grad, const float* inputs, const void* embeddings,
-                                        const int32_t* offsets, void* grad_embeddings,
-                                        uint32_t max_level_rows, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
-                                        const void* dy_dx, void* grad_inputs, uint32_t gridtype, int align_corners,
-                                        uint32_t interp, int dtype, void* workspace, size_t workspace_bytes,
-                                        float bound, const int32_t* n_valid, int path, float* found_inf,
-                                        void* control, size_t control_bytes, s3d_stream_t stream) {
+namespace {
+// s3d_grid_encode_backward, and with `adam` the fused update of s3d_grid_encode_backward_adam (*applied: whether it ran)
+int grid_backward(const void* grad, const float* inputs, const int32_t* offsets, void* grad_embeddings, uint32_t max_level_rows,
+                  uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, const void* dy_dx, void* grad_inputs,
+                  uint32_t gridtype, int align_corners, uint32_t interp, int dtype, void* workspace, size_t workspace_bytes, float bound,
+                  const int32_t* n_valid, int path, float* found_inf, void* control, size_t control_bytes, s3d_stream_t stream,
+                  const GridAdam* adam, bool* applied) {
     // path: 0 = auto (binned from 8,192 points), 1 = direct global atomics, 2 = binned (partition + LDS accumulate)
-    (void)embeddings;
     S3D_REQUIRE(path >= 0 && path <= 2, "grid_encode_backward: path must be 0 (auto), 1 (atomics) or 2 (binned)");
     S3D_REQUIRE(bound >= 0.0f && !(bound != 0.0f && dy_dx), "grid_encode_backward: bound must be >= 0 and 0 with an input Jacobian");
     if (B == 0) return S3D_OK;
@@ -2398,40 +2404,33 @@ S3D_EXPORT int s3d_grid_encode_backward(const void* grad, const float* inputs, c
                     "grid_encode_backward: the binned path needs max_level_rows and a workspace of "
                     "s3d_grid_encode_backward_workspace_size() bytes");
     }
-    LevelScales sc;
-    host_scales(L, S, H, sc, bound, n_valid);
-    hipStream_t st = as_stream(stream);
-    const bool ac = align_corners != 0;
-    unsigned char* ws = (unsigned char*)workspace;
-    unsigned char* cb = (unsigned char*)control;
-    const int fp = path;
-    t_found_inf = found_inf;
-    t_reported = false;
-    const auto run = [&]() -> int {
-    if (dtype == S3D_F32) {
-        const float* g = (const float*)grad; float* ge = (float*)grad_embeddings;
-        const float* j = (const float*)dy_dx; float* gi = (float*)grad_inputs;
-        S3D_DISPATCH_D(D, (launch_backward<float, 2>(g, inputs, offsets, max_level_rows, ge, B, C, L, sc, j, gi, gridtype, ac, interp, ws, workspace_bytes, fp, cb, control_bytes, st)),
-                       (launch_backward<float, 3>(g, inputs, offsets, max_level_rows, ge, B, C, L, sc, j, gi, gridtype, ac, interp, ws, workspace_bytes, fp, cb, control_bytes, st)),
-                       (launch_backward<float, 4>(g, inputs, offsets, max_level_rows, ge, B, C, L, sc, j, gi, gridtype, ac, interp, ws, workspace_bytes, fp, cb, control_bytes, st)),
-                       (launch_backward<float, 5>(g, inputs, offsets, max_level_rows, ge, B, C, L, sc, j, gi, gridtype, ac, interp, ws, workspace_bytes, fp, cb, control_bytes, st)))
-    } else {
-        const __half* g = (const __half*)grad; __half* ge = (__half*)grad_embeddings;
-        const __half* j = (const __half*)dy_dx; __half* gi = (__half*)grad_inputs;
-        S3D_DISPATCH_D(D, (launch_backward<__half, 2>(g, inputs, offsets, max_level_rows, ge, B, C, L, sc, j, gi, gridtype, ac, interp, ws, workspace_bytes, fp, cb, control_bytes, st)),
-                       (launch_backward<__half, 3>(g, inputs, offsets, max_level_rows, ge, B, C, L, sc, j, gi, gridtype, ac, interp, ws, workspace_bytes, fp, cb, control_bytes, st)),
-                       (launch_backward<__half, 4>(g, inputs, offsets, max_level_rows, ge, B, C, L, sc, j, gi, gridtype, ac, interp, ws, workspace_bytes, fp, cb, control_bytes, st)),
-                       (launch_backward<__half, 5>(g, inputs, offsets, max_level_rows, ge, B, C, L, sc, j, gi, gridtype, ac, interp, ws, workspace_bytes, fp, cb, control_bytes, st)))
-    }
-    };
-    const int rc = run();
-    t_found_inf = nullptr;
-    if (rc != S3D_OK || !found_inf || t_reported) return rc;
+    GridBwd a{grad, dy_dx, grad_embeddings, grad_inputs, inputs, offsets, B, C, L, max_level_rows, gridtype, interp, align_corners != 0,
+              LevelScales{}, (unsigned char*)workspace, (unsigned char*)control, workspace_bytes, control_bytes, path, as_stream(stream),
+              found_inf, adam};
+    host_scales(L, S, H, a.sc, bound, n_valid);
+    GridBwdResult res{false, false};
+    const int rc = [&]() -> int { S3D_DISPATCH_TD(dtype, D, launch_backward, a, res) }();
+    if (applied) *applied = res.applied;
+    if (rc != S3D_OK || !found_inf || res.reported) return rc;
     if (dtype == S3D_F32)
-        hipLaunchKernelGGL(k_table_nonfinite<float>, dim3(kMaxStreamBlocks), dim3(256), 0, st, (const float*)grad_embeddings, offsets, L, C, found_inf);
+        hipLaunchKernelGGL(k_table_nonfinite<float>, dim3(kMaxStreamBlocks), dim3(256), 0, a.st, (const float*)grad_embeddings, offsets, L, C, found_inf);
     else
-        hipLaunchKernelGGL(k_table_nonfinite<__half>, dim3(kMaxStreamBlocks), dim3(256), 0, st, (const __half*)grad_embeddings, offsets, L, C, found_inf);
+        hipLaunchKernelGGL(k_table_nonfinite<__half>, dim3(kMaxStreamBlocks), dim3(256), 0, a.st, (const __half*)grad_embeddings, offsets, L, C, found_inf);
     return check_launch("grid_encode_backward (gradient check)");
+}
+}  // namespace
+
+S3D_EXPORT int s3d_grid_encode_backward(const void* grad, const float* inputs, const void* embeddings,
+                                        const int32_t* offsets, void* grad_embeddings,
+                                        uint32_t max_level_rows, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
+                                        const void* dy_dx, void* grad_inputs, uint32_t gridtype, int align_corners,
+                                        uint32_t interp, int dtype, void* workspace, size_t workspace_bytes,
+                                        float bound, const int32_t* n_valid, int path, float* found_inf,
+                                        void* control, size_t control_bytes, s3d_stream_t stream) {
+    (void)embeddings;
+    return grid_backward(grad, inputs, offsets, grad_embeddings, max_level_rows, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype,
+                         align_corners, interp, dtype, workspace, workspace_bytes, bound, n_valid, path, found_inf, control,
+                         control_bytes, stream, nullptr, nullptr);
 }
 
 S3D_EXPORT int s3d_grid_encode_backward_adam(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
@@ -2440,6 +2439,7 @@ S3D_EXPORT int s3d_grid_encode_backward_adam(const void* grad, const float* inpu
                                              void* workspace, size_t workspace_bytes, float bound, const int32_t* n_valid, float* found_inf,
                                              void* control, size_t control_bytes, const s3d_grid_adam* adam, int* applied,
                                              s3d_stream_t stream) {
+    (void)embeddings;
     S3D_REQUIRE(adam && applied, "grid_encode_backward_adam: null pointer");
     S3D_REQUIRE(adam->param && adam->exp_avg && adam->exp_avg_sq && adam->step, "grid_encode_backward_adam: null optimizer state");
     *applied = 0;
@@ -2447,14 +2447,11 @@ S3D_EXPORT int s3d_grid_encode_backward_adam(const void* grad, const float* inpu
     ga.p = adam->param; ga.m = adam->exp_avg; ga.v = adam->exp_avg_sq; ga.ph = reinterpret_cast<__half*>(adam->param_half);
     ga.lr = adam->lr; ga.beta1 = adam->beta1; ga.beta2 = adam->beta2; ga.eps = adam->eps;
     ga.step = adam->step; ga.grad_scale = adam->grad_scale; ga.lr_scale = adam->lr_scale;
-    t_adam = &ga;
-    t_adam_applied = false;
-    const int rc = s3d_grid_encode_backward(grad, inputs, embeddings, offsets, grad_embeddings, max_level_rows, B, D, C, L, S, H, nullptr,
-                                            nullptr, gridtype, align_corners, interp, dtype, workspace, workspace_bytes, bound, n_valid, 0,
-                                            found_inf, control, control_bytes, stream);
-    t_adam = nullptr;
-    *applied = t_adam_applied ? 1 : 0;
-    t_adam_applied = false;
+    bool ran = false;
+    const int rc = grid_backward(grad, inputs, offsets, grad_embeddings, max_level_rows, B, D, C, L, S, H, nullptr, nullptr, gridtype,
+                                 align_corners, interp, dtype, workspace, workspace_bytes, bound, n_valid, 0, found_inf, control,
+                                 control_bytes, stream, &ga, &ran);
+    *applied = ran ? 1 : 0;
     return rc;
 }
 

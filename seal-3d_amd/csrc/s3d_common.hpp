@@ -61,6 +61,20 @@ inline void device_setup_done(std::atomic<uint64_t>& flags, int dev) {
     if (dev >= 0) flags.fetch_or(1ull << dev, std::memory_order_release);
 }
 
+// CUs of the current device, cached per device ordinal (resident-workgroup counts of the persistent kernels)
+inline uint32_t device_cus() {
+    static std::atomic<uint32_t> cus[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return 256;
+    uint32_t n = cus[dev].load(std::memory_order_relaxed);
+    if (!n) {
+        int v = 0;
+        n = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? (uint32_t)v : 256u;
+        cus[dev].store(n, std::memory_order_relaxed);
+    }
+    return n;
+}
+
 template <typename T>
 __host__ __device__ inline T div_up(T a, T b) { return (a + b - 1) / b; }
 

@@ -396,24 +396,31 @@ class RaymarchingBackend:
                "composite_rays_train_backward")
 
     @staticmethod
+    def _check_train_loss(name, M, N, gt_depth, grad_image, grad_weights_sum, exact, **tensors):
+        """argument checks of composite_rays_train_loss / _loss_bg (`name`, for the messages): fp32 `tensors`, the `exact` ones [N,3]"""
+        for n, t in tensors.items():
+            _need(t, torch.float32, n)
+        if (any(tensors[n].numel() != 3 * N for n in exact) or tensors["workspace"].numel() < 4 * N
+                or tensors["grad_sigmas"].numel() < M or tensors["grad_rgbs"].numel() < 3 * M):
+            raise RuntimeError(f"{name}: {' / '.join(exact)} [N,3], workspace >= 4N floats, grad_sigmas [M], grad_rgbs [M,3]")
+        if gt_depth is not None:
+            _need(gt_depth, torch.float32, "gt_depth")
+            if gt_depth.numel() != N:
+                raise RuntimeError(f"{name}: gt_depth holds one value per ray")
+        if (grad_image is None) != (grad_weights_sum is None):
+            raise RuntimeError(f"{name}: grad_image and grad_weights_sum come together")
+        if RaymarchingBackend._composite_path != 0:
+            raise RuntimeError(f"{name}: the fused launch exists for the wave-per-ray path only")
+
+    @staticmethod
     def composite_rays_train_loss(sigmas, rgbs, deltas, rays, M, N, T_thresh, gt, bg_rgb, grad_loss, weights_sum, depth, image,
                                   grad_sigmas, grad_rgbs, loss, workspace, gt_depth=None, depth_weight=1.0, grad_image=None,
                                   grad_weights_sum=None):
         """composite forward + background / MSE loss (announced upstream gradient `grad_loss`) + composite backward of one ray batch
         in one launch + a one-workgroup sum of the loss terms (seal3d_hip.h); workspace: 4N floats of scratch"""
-        for t, n in ((sigmas, "sigmas"), (rgbs, "rgbs"), (deltas, "deltas"), (gt, "gt"), (grad_loss, "grad_loss"), (loss, "loss"),
-                     (workspace, "workspace"), (grad_sigmas, "grad_sigmas"), (grad_rgbs, "grad_rgbs")):
-            _need(t, torch.float32, n)
-        if gt.numel() != 3 * N or workspace.numel() < 4 * N or grad_sigmas.numel() < M or grad_rgbs.numel() < 3 * M:
-            raise RuntimeError("composite_rays_train_loss: gt [N,3], workspace >= 4N floats, grad_sigmas [M], grad_rgbs [M,3]")
-        if gt_depth is not None:
-            _need(gt_depth, torch.float32, "gt_depth")
-            if gt_depth.numel() != N:
-                raise RuntimeError("composite_rays_train_loss: gt_depth holds one value per ray")
-        if (grad_image is None) != (grad_weights_sum is None):
-            raise RuntimeError("composite_rays_train_loss: grad_image and grad_weights_sum come together")
-        if RaymarchingBackend._composite_path != 0:
-            raise RuntimeError("composite_rays_train_loss: the fused launch exists for the wave-per-ray path only")
+        RaymarchingBackend._check_train_loss(
+            "composite_rays_train_loss", M, N, gt_depth, grad_image, grad_weights_sum, ("gt",), sigmas=sigmas, rgbs=rgbs, deltas=deltas,
+            gt=gt, grad_loss=grad_loss, loss=loss, workspace=workspace, grad_sigmas=grad_sigmas, grad_rgbs=grad_rgbs)
         bg = (C.c_float * 3)(*[float(v) for v in bg_rgb])
         _check(lib().s3d_composite_rays_train_loss(_p(sigmas), _p(rgbs), _p(deltas), _p(rays), _u(M), _u(N), _f(T_thresh), _p(gt), bg,
                                                    _p(grad_loss), _p(gt_depth), _f(depth_weight), _p(weights_sum), _p(depth), _p(image),
@@ -425,22 +432,10 @@ class RaymarchingBackend:
                                      grad_sigmas, grad_rgbs, grad_bg, loss, workspace, gt_depth=None, depth_weight=1.0,
                                      grad_image=None, grad_weights_sum=None):
         """composite_rays_train_loss with a per-ray background bg [N,3] (device) and its gradient grad_bg [N,3] (seal3d_hip.h)"""
-        for t, n in ((sigmas, "sigmas"), (rgbs, "rgbs"), (deltas, "deltas"), (gt, "gt"), (bg, "bg"), (grad_bg, "grad_bg"),
-                     (grad_loss, "grad_loss"), (loss, "loss"), (workspace, "workspace"), (grad_sigmas, "grad_sigmas"),
-                     (grad_rgbs, "grad_rgbs")):
-            _need(t, torch.float32, n)
-        if (gt.numel() != 3 * N or bg.numel() != 3 * N or grad_bg.numel() != 3 * N or workspace.numel() < 4 * N
-                or grad_sigmas.numel() < M or grad_rgbs.numel() < 3 * M):
-            raise RuntimeError("composite_rays_train_loss_bg: gt / bg / grad_bg [N,3], workspace >= 4N floats, grad_sigmas [M], "
-                               "grad_rgbs [M,3]")
-        if gt_depth is not None:
-            _need(gt_depth, torch.float32, "gt_depth")
-            if gt_depth.numel() != N:
-                raise RuntimeError("composite_rays_train_loss_bg: gt_depth holds one value per ray")
-        if (grad_image is None) != (grad_weights_sum is None):
-            raise RuntimeError("composite_rays_train_loss_bg: grad_image and grad_weights_sum come together")
-        if RaymarchingBackend._composite_path != 0:
-            raise RuntimeError("composite_rays_train_loss_bg: the fused launch exists for the wave-per-ray path only")
+        RaymarchingBackend._check_train_loss(
+            "composite_rays_train_loss_bg", M, N, gt_depth, grad_image, grad_weights_sum, ("gt", "bg", "grad_bg"), sigmas=sigmas,
+            rgbs=rgbs, deltas=deltas, gt=gt, bg=bg, grad_bg=grad_bg, grad_loss=grad_loss, loss=loss, workspace=workspace,
+            grad_sigmas=grad_sigmas, grad_rgbs=grad_rgbs)
         _check(lib().s3d_composite_rays_train_loss_bg(_p(sigmas), _p(rgbs), _p(deltas), _p(rays), _u(M), _u(N), _f(T_thresh), _p(gt),
                                                       _p(bg), _p(grad_loss), _p(gt_depth), _f(depth_weight), _p(weights_sum), _p(depth),
                                                       _p(image), _p(grad_sigmas), _p(grad_rgbs), _p(grad_image), _p(grad_weights_sum),
@@ -549,6 +544,16 @@ class GridBackend:
                "grid_corner_indices")
 
     @staticmethod
+    def _backward_buffers(grad, offsets, B, D, Cc, L):
+        """(max_level_rows, workspace, control block or None) of a backward call; the control block from 8,192 points on"""
+        mlr = _max_level_rows(offsets)
+        ws = _ws.get(lib().s3d_grid_encode_backward_workspace_size(_u(B), _u(D), _u(Cc), _u(L), _u(mlr),
+                                                                   C.c_int(_dt(grad))), grad.device)
+        ctl = _ctl.get(lib().s3d_grid_encode_backward_control_size(_u(D), _u(Cc), _u(L), _u(mlr), C.c_int(_dt(grad))),
+                       grad.device) if B >= 8192 else None
+        return mlr, ws, ctl
+
+    @staticmethod
     def grid_encode_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, D, Cc, L, S, H, dy_dx,
                              grad_inputs, gridtype, align_corners, interp, bound=0.0, n_valid=None, found_inf=None):
         _need(inputs, torch.float32, "inputs")
@@ -556,11 +561,7 @@ class GridBackend:
             _need(found_inf, torch.float32, "found_inf")
         if grad_embeddings.dtype != grad.dtype:
             raise RuntimeError("grad_embeddings must have the dtype of grad")
-        mlr = _max_level_rows(offsets)
-        ws = _ws.get(lib().s3d_grid_encode_backward_workspace_size(_u(B), _u(D), _u(Cc), _u(L), _u(mlr),
-                                                                   C.c_int(_dt(grad))), grad.device)
-        ctl = _ctl.get(lib().s3d_grid_encode_backward_control_size(_u(D), _u(Cc), _u(L), _u(mlr), C.c_int(_dt(grad))),
-                       grad.device) if B >= 8192 else None
+        mlr, ws, ctl = GridBackend._backward_buffers(grad, offsets, B, D, Cc, L)
         _check(lib().s3d_grid_encode_backward(_p(grad), _p(inputs), _p(embeddings), _p(offsets),
                                               _p(grad_embeddings), _u(mlr), _u(B), _u(D),
                                               _u(Cc), _u(L), _f(S), _u(H), _p(dy_dx), _p(grad_inputs), _u(gridtype),
@@ -591,10 +592,7 @@ class GridBackend:
             _need(adam[k], torch.float32, k)
             if adam[k].shape != embeddings.shape or not adam[k].is_contiguous():
                 raise RuntimeError(f"adam[{k!r}] must be a contiguous fp32 tensor of the table's shape")
-        mlr = _max_level_rows(offsets)
-        ws = _ws.get(lib().s3d_grid_encode_backward_workspace_size(_u(B), _u(D), _u(Cc), _u(L), _u(mlr), C.c_int(_dt(grad))), grad.device)
-        ctl = _ctl.get(lib().s3d_grid_encode_backward_control_size(_u(D), _u(Cc), _u(L), _u(mlr), C.c_int(_dt(grad))),
-                       grad.device) if B >= 8192 else None
+        mlr, ws, ctl = GridBackend._backward_buffers(grad, offsets, B, D, Cc, L)
         ga = GridBackend._GridAdam()
         ga.param, ga.exp_avg, ga.exp_avg_sq = adam["param"].data_ptr(), adam["exp_avg"].data_ptr(), adam["exp_avg_sq"].data_ptr()
         ga.param_half = adam["param_half"].data_ptr() if adam.get("param_half") is not None else None
