@@ -587,6 +587,21 @@ int s3d_seal_bbox_map(const float* points, const float* dirs, uint32_t M, const 
 int s3d_seal_map_color(const void* rgbs, const uint8_t* mask, uint32_t M, int dtype, const float* hsv, const float* rgb_target,
                        float light_offset, void* out, void* stats, const int32_t* n_valid /* or NULL */, s3d_stream_t stream);
 
+/* Texture painting of the brush tool (`imageConfig`) on the samples the proxy moved — the `image` step of map_color,
+ * SealNeRF/seal_utils.py:58-79 with :753-769 (modify_rgb with a per-sample target), after the optional hsv step.  rgbs / out
+ * DEVICE [M,3] f32 or f16 (`dtype`; out may alias rgbs), points DEVICE [M,3] f32 (the MAPPED sample points), mask DEVICE [M] u8.
+ * hsv: HOST [3] or NULL.  texture: DEVICE [tex_h, tex_w, 4] f32, 16-byte aligned, one texel = (hue, saturation, value, alpha)
+ * of the image (rgb2hsv_torch of its RGB, done once by the caller).  quad: HOST [14] = v_image_o[3], v_image_w - v_image_o [3],
+ * v_image_h - v_image_o [3], v_image_norm[3], |ow|^2, |oh|^2.  A moved sample's point is projected onto the plane (o, norm);
+ * its texel is (clamp(floor(v_op . oh / |oh|^2 * tex_h), 0, tex_h - 1), clamp(floor(v_op . ow / |ow|^2 * tex_w), 0, tex_w - 1)):
+ * nearest texel, the edge texel outside the quad.  The sample takes the texel's hue and saturation and the value
+ * clamp(texel_v + (v_i - mean_moved(v)) + light_offset, 0, 1), blended over its colour by the texel's alpha; the mean is taken
+ * over the moved rows of THIS call in `stats` (DEVICE 16 bytes, cleared by the call), as in s3d_seal_map_color.  texel_out:
+ * DEVICE [M,2] i32 or NULL, receives (idx_h, idx_w) of the moved rows.  Rows where mask == 0 are copied. */
+int s3d_seal_map_color_image(const void* rgbs, const float* points, const uint8_t* mask, uint32_t M, int dtype, const float* hsv,
+                             const float* texture, uint32_t tex_h, uint32_t tex_w, const float* quad, float light_offset, void* out,
+                             void* stats, int32_t* texel_out, const int32_t* n_valid /* or NULL */, s3d_stream_t stream);
+
 /* Seal proxy mapper, brush tool — SealNeRF/seal_utils.py:282-453 (map_to_origin :408-453) with :132-153 (map_mask) and
  * :630-685 (inside test, ray direction = the UNnormalised normal_expand).  points / out_points DEVICE [M,3] f32, mask DEVICE
  * [M] u8.  triangles DEVICE [n_tris,3,3] (12 per stroke), bounds DEVICE [n_bounds,2,3] (min,max; one per stroke), border

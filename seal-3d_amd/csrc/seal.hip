@@ -360,6 +360,61 @@ __global__ void __launch_bounds__(256) k_seal_color_apply(const T* __restrict__ 
     }
 }
 
+// ---- texture painting of the brush tool (seal_utils.py:58-79 the `image` step of map_color, :753-769 modify_rgb with a
+// per-sample target).  A masked sample's MAPPED point is projected onto the plane of the image quad (o, w, h), its
+// coordinates along o->w and o->h pick one texel (nearest, floor; outside the quad the edge texel, as in the reference), the
+// sample takes that texel's hue and saturation and the value clamp(texel_v + (v_i - mean_moved(v)) + light, 0, 1), and the
+// result is blended over the sample's colour with the texel's alpha.  The mean is k_seal_color_stats' (the same batch
+// statistic as the `rgb` edit's).  Texture: [H, W] texels of 16 bytes (h, s, v, alpha) — the hsv of the texel is a constant
+// of the edit, converted once on the host, so a masked row costs one 16-byte load and no conversion of the target.
+struct SealImage {
+    float o[3], ow[3], oh[3], n[3], len_ow2, len_oh2;
+    uint32_t H, W;
+};
+template <typename T>
+__global__ void __launch_bounds__(256) k_seal_color_image(const T* __restrict__ rgb, const float* __restrict__ points,
+                                                          const uint8_t* __restrict__ mask, uint32_t M, SealColor c, SealImage im,
+                                                          const float4* __restrict__ tex, const int32_t* __restrict__ n_valid,
+                                                          const unsigned long long* __restrict__ stats, T* __restrict__ out,
+                                                          int32_t* __restrict__ texel_out) {
+    const uint32_t Mv = valid_rows(M, n_valid);
+    const long long sum = (long long)stats[0];
+    const unsigned long long cnt = stats[1];
+    const float mean = cnt ? (float)((double)sum / 1048576.0 / (double)cnt) : 0.0f;
+    const float nn = im.n[0] * im.n[0] + im.n[1] * im.n[1] + im.n[2] * im.n[2];
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < Mv; i += gridDim.x * 256) {
+        float r = color_ld(rgb + (size_t)i * 3), g = color_ld(rgb + (size_t)i * 3 + 1), b = color_ld(rgb + (size_t)i * 3 + 2);
+        if (!mask[i]) {
+            if (out != rgb) { out[(size_t)i * 3] = rgb[(size_t)i * 3]; out[(size_t)i * 3 + 1] = rgb[(size_t)i * 3 + 1]; out[(size_t)i * 3 + 2] = rgb[(size_t)i * 3 + 2]; }
+            continue;
+        }
+        // project_points(n, o, p) - o, then the two texel coordinates (seal_utils.py:66-75, same order)
+        const float px = points[(size_t)i * 3], py = points[(size_t)i * 3 + 1], pz = points[(size_t)i * 3 + 2];
+        const float s_ = ((px - im.o[0]) * im.n[0] + (py - im.o[1]) * im.n[1] + (pz - im.o[2]) * im.n[2]) / nn;
+        const float qx = (px - s_ * im.n[0]) - im.o[0], qy = (py - s_ * im.n[1]) - im.o[1], qz = (pz - s_ * im.n[2]) - im.o[2];
+        const float cw = (qx * im.ow[0] + qy * im.ow[1] + qz * im.ow[2]) / im.len_ow2 * (float)im.W;
+        const float ch = (qx * im.oh[0] + qy * im.oh[1] + qz * im.oh[2]) / im.len_oh2 * (float)im.H;
+        // (fmaxf / fminf drop a NaN: the index stays inside the texture whatever the point holds)
+        const uint32_t iw = (uint32_t)fminf(fmaxf(floorf(cw), 0.0f), (float)(im.W - 1));
+        const uint32_t ih = (uint32_t)fminf(fmaxf(floorf(ch), 0.0f), (float)(im.H - 1));
+        const float4 t = tex[(size_t)ih * im.W + iw];
+        float h, s, v;
+        rgb2hsv(r, g, b, h, s, v);
+        if (c.has_hsv) {  // the hsv step's RGB result is what the texture step converts again, and what it blends over
+            hsv2rgb(h + c.hsv[0], s + c.hsv[1], v + c.hsv[2], r, g, b);
+            rgb2hsv(r, g, b, h, s, v);
+        }
+        const float val = fminf(1.0f, fmaxf(0.0f, t.z + (v - mean) + c.light));
+        float mr, mg, mb;
+        hsv2rgb(t.x, t.y, val, mr, mg, mb);
+        const float keep = 1.0f - t.w;
+        out[(size_t)i * 3] = (T)(t.w * mr + keep * r);
+        out[(size_t)i * 3 + 1] = (T)(t.w * mg + keep * g);
+        out[(size_t)i * 3 + 2] = (T)(t.w * mb + keep * b);
+        if (texel_out) { texel_out[(size_t)i * 2] = (int32_t)ih; texel_out[(size_t)i * 2 + 1] = (int32_t)iw; }
+    }
+}
+
 }  // namespace
 }  // namespace s3d
 
@@ -434,6 +489,43 @@ S3D_EXPORT int s3d_seal_map_color(const void* rgbs, const uint8_t* mask, uint32_
     if (dtype == S3D_F32) hipLaunchKernelGGL(k_seal_color_apply<float>, grid, block, 0, st, (const float*)rgbs, mask, M, c, n_valid, sw, (float*)out);
     else hipLaunchKernelGGL(k_seal_color_apply<_Float16>, grid, block, 0, st, (const _Float16*)rgbs, mask, M, c, n_valid, sw, (_Float16*)out);
     return check_launch("seal_map_color");
+}
+
+S3D_EXPORT int s3d_seal_map_color_image(const void* rgbs, const float* points, const uint8_t* mask, uint32_t M, int dtype,
+                                        const float* hsv, const float* texture, uint32_t tex_h, uint32_t tex_w, const float* quad,
+                                        float light_offset, void* out, void* stats, int32_t* texel_out, const int32_t* n_valid,
+                                        s3d_stream_t stream) {
+    if (M == 0) return S3D_OK;
+    S3D_REQUIRE(rgbs && points && mask && out && texture && quad && stats, "seal_map_color_image: null pointer");
+    S3D_REQUIRE(dtype == S3D_F32 || dtype == S3D_F16, "seal_map_color_image: dtype must be f32 or f16");
+    S3D_REQUIRE(tex_h >= 1 && tex_w >= 1 && tex_h <= (1u << 15) && tex_w <= (1u << 15), "seal_map_color_image: texture of %u x %u texels",
+                tex_h, tex_w);
+    S3D_REQUIRE((reinterpret_cast<uintptr_t>(texture) & 15u) == 0, "seal_map_color_image: the texture must be 16-byte aligned");
+    SealColor c;
+    memset(&c, 0, sizeof(c));
+    if (hsv) { c.has_hsv = 1; for (int k = 0; k < 3; k++) c.hsv[k] = hsv[k]; }
+    c.has_rgb = 1;  // (k_seal_color_stats: the value channel AFTER the hsv step's round trip through RGB, as for the `rgb` edit)
+    c.light = light_offset;
+    SealImage im;
+    memset(&im, 0, sizeof(im));
+    for (int d = 0; d < 3; d++) { im.o[d] = quad[d]; im.ow[d] = quad[3 + d]; im.oh[d] = quad[6 + d]; im.n[d] = quad[9 + d]; }  // HOST [14]
+    im.len_ow2 = quad[12]; im.len_oh2 = quad[13];
+    im.H = tex_h; im.W = tex_w;
+    hipStream_t st = as_stream(stream);
+    const dim3 grid(std::min<uint32_t>(div_up<uint32_t>(M, 256), 2048u)), block(256);
+    auto* sw = reinterpret_cast<unsigned long long*>(stats);
+    const auto* tex = reinterpret_cast<const float4*>(texture);
+    hipLaunchKernelGGL(k_seal_zero2, dim3(1), dim3(64), 0, st, sw);  // (a kernel, not a memset node: see tensorf.hip's bins)
+    if (dtype == S3D_F32) {
+        hipLaunchKernelGGL(k_seal_color_stats<float>, grid, block, 0, st, (const float*)rgbs, mask, M, c, n_valid, sw);
+        hipLaunchKernelGGL(k_seal_color_image<float>, grid, block, 0, st, (const float*)rgbs, points, mask, M, c, im, tex, n_valid, sw,
+                           (float*)out, texel_out);
+    } else {
+        hipLaunchKernelGGL(k_seal_color_stats<_Float16>, grid, block, 0, st, (const _Float16*)rgbs, mask, M, c, n_valid, sw);
+        hipLaunchKernelGGL(k_seal_color_image<_Float16>, grid, block, 0, st, (const _Float16*)rgbs, points, mask, M, c, im, tex, n_valid,
+                           sw, (_Float16*)out, texel_out);
+    }
+    return check_launch("seal_map_color_image");
 }
 
 S3D_EXPORT int s3d_seal_brush_map(const float* points, uint32_t M, const float* triangles, uint32_t n_tris, const float* bounds,

@@ -42,7 +42,7 @@ EXPORTS = [
     "s3d_grads_nonfinite", "s3d_adam_step", "s3d_adam_step_multi", "s3d_adam_advance", "s3d_scaler_update", "s3d_step_ring_push", "s3d_step_epilogue",
     "s3d_ngp_mid_forward", "s3d_ngp_mid_backward", "s3d_ngp_mid2_forward", "s3d_ngp_mid2_backward", "s3d_ngp_rgb_forward", "s3d_ngp_rgb_backward",
     "s3d_bg_mse_forward", "s3d_bg_mse_backward", "s3d_bg_targets", "s3d_l1_pair_workspace_size", "s3d_l1_pair_loss",
-    "s3d_seal_bbox_map", "s3d_seal_map_color", "s3d_seal_brush_map", "s3d_seal_anchor_map", "s3d_grid_encode_backward_adam", "s3d_vm_features_forward",
+    "s3d_seal_bbox_map", "s3d_seal_map_color", "s3d_seal_map_color_image", "s3d_seal_brush_map", "s3d_seal_anchor_map", "s3d_grid_encode_backward_adam", "s3d_vm_features_forward",
     "s3d_aabb_normalize", "s3d_weighted_abs_sum_workspace_size", "s3d_weighted_abs_sum", "s3d_pack_linear_chain", "s3d_unpack_linear_chain",
     "s3d_vm_backward_max_bins", "s3d_vm_backward_keys", "s3d_vm_backward_bins_workspace_size", "s3d_vm_backward_bins",
     "s3d_vm_backward_stage_bytes", "s3d_vm_transpose_factors",
@@ -1230,6 +1230,37 @@ class SealBackend:
             stats = torch.empty(2, dtype=torch.int64, device=rgbs.device)
         _check(lib().s3d_seal_map_color(_p(rgbs), _p(mask), _u(rgbs.shape[0]), C.c_int(_dt(rgbs)), h, t, C.c_float(float(light_offset)),
                                         _p(out), _p(stats), _nv(n_valid), _stream()), "seal_map_color")
+
+    @staticmethod
+    def map_color_image(rgbs, points, mask, hsv, texture, quad, light_offset, out, stats=None, texel_out=None, n_valid=None):
+        """texture painting of the moved samples (include/seal3d_hip.h: s3d_seal_map_color_image); `texture`: fp32 GPU tensor
+        [H, W, 4] of (h, s, v, alpha) texels, `quad`: 14 host floats (o, ow, oh, normal, |ow|^2, |oh|^2), `hsv`: 3 floats or
+        None, `texel_out`: optional int32 GPU tensor [M, 2] for the (idx_h, idx_w) of the masked rows"""
+        import numpy as np
+        if rgbs.dtype not in (torch.float32, torch.float16) or out.dtype != rgbs.dtype or not rgbs.is_contiguous() or not out.is_contiguous():
+            raise RuntimeError("map_color_image: contiguous f32 / f16 colours")
+        if rgbs.dim() != 2 or rgbs.shape[1] != 3 or out.shape != rgbs.shape:
+            raise RuntimeError("map_color_image: colours [M, 3]")
+        _need(points, torch.float32, "points")
+        if tuple(points.shape) != tuple(rgbs.shape) or mask.numel() != rgbs.shape[0]:
+            raise RuntimeError("map_color_image: one point [3] and one mask byte per colour row")
+        if mask.dtype != torch.uint8:
+            raise RuntimeError("mask must be uint8")
+        _need(texture, torch.float32, "texture")
+        if texture.dim() != 3 or texture.shape[2] != 4:
+            raise RuntimeError("map_color_image: texture [H, W, 4] of (h, s, v, alpha)")
+        if texel_out is not None and (texel_out.dtype != torch.int32 or tuple(texel_out.shape) != (rgbs.shape[0], 2)):
+            raise RuntimeError("map_color_image: texel_out must be int32 [M, 2]")
+        q = np.ascontiguousarray(quad, dtype=np.float32)
+        if q.size != 14:
+            raise RuntimeError("map_color_image: quad [14]")
+        h = (C.c_float * 3)(*[float(v) for v in hsv]) if hsv is not None else None
+        if stats is None:
+            stats = torch.empty(2, dtype=torch.int64, device=rgbs.device)
+        _check(lib().s3d_seal_map_color_image(_p(rgbs), _p(points), _p(mask), _u(rgbs.shape[0]), C.c_int(_dt(rgbs)), h, _p(texture),
+                                              _u(texture.shape[0]), _u(texture.shape[1]), q.ctypes.data_as(C.POINTER(C.c_float)),
+                                              C.c_float(float(light_offset)), _p(out), _p(stats), _p(texel_out), _nv(n_valid),
+                                              _stream()), "seal_map_color_image")
 
 
 def _zeros_like_many(tensors, words=0):

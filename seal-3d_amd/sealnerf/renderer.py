@@ -64,15 +64,18 @@ class SealTeacherMixin:
         """nerf/renderer.py: may run_cuda skip the zero fills of the sample buffers?  Yes without a proxy (student), and with
         the native bbox mapper too: it takes the device-side sample count like every other per-sample kernel (rows behind
         the count are neither read nor written; the marcher keeps the pad rows up to the next 128 zero, the mapper maps them).
-        The bbox tool's colour edit runs on the device with the same count (csrc/seal.hip: s3d_seal_map_color); the brush
-        tool's image remap (torch ops over whole tensors) would keep the conservative path."""
+        The colour edits run on the device with the same count (csrc/seal.hip: s3d_seal_map_color, and
+        s3d_seal_map_color_image for the brush tool's texture); a texture together with an `rgb` target takes torch ops over
+        whole tensors and keeps the conservative path."""
         if self.seal_mapper is None or not self.proxy_enabled:
             return True
         m = self.seal_mapper
-        return bool(getattr(m, "native", False)) and "image" not in m.map_data
+        return bool(getattr(m, "native", False)) and not ("image" in m.map_data and "rgb" in m.map_data)
 
     def _batch_dependent_colors(self):
-        return self.seal_mapper is not None and self.proxy_enabled and "rgb" in self.seal_mapper.map_data
+        """an `rgb` target or a texture: each moved sample keeps its brightness offset from the mean of its network batch"""
+        md = self.seal_mapper.map_data if self.seal_mapper is not None else {}
+        return self.proxy_enabled and ("rgb" in md or "image" in md)
 
     # teacher only: proxy the samples
     def map_samples(self, xyzs, dirs):
@@ -87,7 +90,7 @@ class SealTeacherMixin:
         if mask is None or self.seal_mapper is None:
             return rgbs
         md = self.seal_mapper.map_data
-        if "hsv" not in md and "rgb" not in md:
+        if "hsv" not in md and "rgb" not in md and "image" not in md:
             return rgbs
         return self.seal_mapper.map_color_masked(xyzs, dirs, rgbs, mask)
 

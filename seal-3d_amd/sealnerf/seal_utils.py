@@ -8,7 +8,8 @@ Three tools, each a `SealMapper` with a torch op sequence and device kernels (cs
 No trimesh / pytorch3d / skspatial: the box meshes are built directly (12 triangles per box), the plane fit and the uv-sphere
 vertex set are restated, and the inside test is the reference's two-ray Moller-Trumbore parity test (seal_utils.py:630-685)
 in plain torch.  Colour remapping: the `hsv` / `rgb` options (seal_utils.py:48-58, 739-769, color_utils.py:33-66) of every
-tool; the brush tool's image remap (`imageConfig`), `curve` strokes and the `ease-in` / `ease-out` attenuation are refused.
+tool, and the brush tool's texture painting (`imageConfig`, seal_utils.py:58-79, 382-404: texels inline, from a `.npy`, or
+through an `image_loader`); `curve` strokes and the `ease-in` / `ease-out` attenuation are refused.
 """
 import json
 
@@ -173,6 +174,50 @@ def modify_rgb(rgb, modification, light_offset=0):
     return hsv_to_rgb(out)
 
 
+def pil_image_loader(path):
+    """a ready-made `image_loader` for get_seal_mapper: decode an image file with PIL (imported here only) to uint8
+    [H, W, 3] RGB or [H, W, 4] RGBA — what the reference gets from cv2.imread(IMREAD_UNCHANGED) after its BGR(A) -> RGB
+    swap.  A palette image is expanded (with its transparency); a grey image stays 2-D and is refused downstream; every
+    other mode (CMYK, LA, 16-bit, ...) is refused here: its channels are not RGB(A)."""
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode == "P":
+            im = im.convert("RGBA" if "transparency" in im.info else "RGB")
+        if im.mode not in ("RGB", "RGBA", "L"):
+            raise ValueError(f"pil_image_loader: `{path}` has mode {im.mode}; RGB, RGBA and palette images only")
+        return np.asarray(im).copy()
+
+
+def load_texture(image_conf, image_loader=None):
+    """the texels of an `imageConfig` as float32 (image [H, W, 3], alpha [H, W]) — seal_utils.py:385-394.  `pixels`: a
+    nested list / ndarray [H, W, 3 | 4] given inline; `path`: a `.npy` file of the same, or an encoded image file, which
+    `image_loader` (path -> ndarray [H, W, 3 | 4], RGB(A) order) decodes.  uint8 (any integer type: 0..255) is divided by 255,
+    floats are taken as they are; without an alpha channel alpha is 1."""
+    if "pixels" in image_conf:
+        arr = np.asarray(image_conf["pixels"])
+    else:
+        path = image_conf["path"]
+        if str(path).lower().endswith(".npy"):
+            arr = np.load(path)
+        elif image_loader is None:
+            raise NotImplementedError(f"imageConfig: `{path}` is an encoded image file and the core decodes none (torch and numpy "
+                                      "only): pass get_seal_mapper(..., image_loader=) a callable path -> ndarray [H, W, 3 | 4] "
+                                      "in RGB(A) order (sealnerf.pil_image_loader is one), or give the texels as a `.npy` file")
+        else:
+            arr = np.asarray(image_loader(path))
+    if arr.ndim != 3 or arr.shape[2] not in (3, 4) or arr.shape[0] < 1 or arr.shape[1] < 1:
+        raise ValueError(f"imageConfig: texels must be [H, W, 3] (RGB) or [H, W, 4] (RGBA), got {arr.shape}")
+    if arr.dtype.kind in "ui":  # uint8, or the integers of a JSON list: 0..255
+        if arr.min() < 0 or arr.max() > 255:
+            raise ValueError(f"imageConfig: integer texels must lie in 0..255, got {int(arr.min())}..{int(arr.max())}")
+        arr = arr.astype(np.float32) / np.float32(255)
+    elif arr.dtype.kind != "f":
+        raise ValueError(f"imageConfig: texels must be integers 0..255 or floating point, got {arr.dtype}")
+    arr = arr.astype(np.float32)
+    alpha = arr[:, :, 3] if arr.shape[2] == 4 else np.ones(arr.shape[:2], dtype=np.float32)
+    return np.ascontiguousarray(arr[:, :, :3]), np.ascontiguousarray(alpha)
+
+
 class SealMapper:
     """what every tool shares (seal_utils.py:18-153): the constants in `map_data` (float32 tensors) and `map_triangles`, their
     device, the `hsv` / `rgb` colour edit of the moved samples and the AABB + mesh `map_mask`.  `native = True`: GPU tensors go
@@ -213,20 +258,91 @@ class SealMapper:
 
     def map_color(self, points, dirs, colors):
         """seal_utils.py:48-81 (`hsv` / `rgb` of seal.json, :226-230, 389-393, 497-501): hue / saturation / value offsets, then
-        re-colouring towards a target RGB that keeps each sample's brightness offset from the batch mean.  The brush tool's
-        image remap (`imageConfig`) is not supported (get_seal_mapper refuses it)."""
+        re-colouring towards a target RGB that keeps each sample's brightness offset from the batch mean, then the brush
+        tool's texture painting (`imageConfig`, :58-79): the same re-colouring towards the texel under each of `points` (the
+        MAPPED sample points; the batch mean is that of all rows passed in), blended by the texel's alpha.  Torch ops on any
+        device and dtype; the constants follow `points`."""
         if "hsv" in self.map_data:
             colors = modify_hsv(colors, self.map_data["hsv"])
         if "rgb" in self.map_data:
             colors = modify_rgb(colors, self.map_data["rgb"], self.map_data.get("rgb_light_offset", 0))
+        if "image" in self.map_data:
+            k = self._image_twin(points.device, points.dtype)
+            idx_h, idx_w = self.texel_indices(points)
+            alpha = k["image_mask"][idx_h, idx_w].to(colors.dtype)[None].T
+            modified = modify_rgb(colors, k["image"][idx_h, idx_w].to(colors.dtype), self.map_data["rgb_light_offset"])
+            colors = alpha * modified + (1 - alpha) * colors
         return colors
+
+    def _image_twin(self, device, dtype):
+        """the texture's constants on `device` in `dtype` (one copy per device and dtype; a caller that edits map_data in
+        place clears `_dev`)"""
+        key = ("twin", device, dtype)
+        k = self._dev.get(key)
+        if k is None:
+            md = self.map_data
+            k = {n: md[n].to(device, dtype) for n in ("image", "image_mask", "v_image_norm", "v_image_o", "v_image_w", "v_image_h")}
+            self._dev[key] = k
+        return k
+
+    @torch.autocast("cuda", enabled=False)
+    def texel_indices(self, points):
+        """seal_utils.py:61-75: (idx_h, idx_w) of the texel under each point — the point projected onto the image plane, its
+        coordinate along o->w (o->h) as a share of that edge times W (H), floored; outside the quad the edge texel.  Like
+        map_to_origin it runs with autocast off: the dot products stay in the points' precision inside an fp16 render (half
+        precision would move a point by texels)"""
+        k = self._image_twin(points.device, points.dtype)
+        H, W = k["image"].shape[:2]
+        v_o = k["v_image_o"]
+        v_op = project_points(k["v_image_norm"], v_o, points) - v_o
+        v_ow, v_oh = k["v_image_w"] - v_o, k["v_image_h"] - v_o
+        len_ow, len_oh = torch.norm(v_ow, 2), torch.norm(v_oh, 2)
+        idx_w = torch.clamp(torch.floor(v_op @ v_ow / len_ow ** 2 * W), 0, W - 1).to(torch.long)
+        idx_h = torch.clamp(torch.floor(v_op @ v_oh / len_oh ** 2 * H), 0, H - 1).to(torch.long)
+        return idx_h, idx_w
+
+    def _image_native(self, device):
+        """what s3d_seal_map_color_image takes, uploaded once per device: the texture as [H, W, 4] float32 texels of
+        (h, s, v, alpha) — `rgb_to_hsv` of the image in float32 on the host, the conversion modify_rgb applies to its target,
+        so both routes see the same bits — and the quad's 14 host floats (o, ow, oh, normal, |ow|^2, |oh|^2).  The `hsv`
+        offsets and the light offset are taken along as host values (no read-back inside a captured render): like the
+        tensors they are those of the first call on the device until `_dev` is cleared"""
+        key = ("image", device)
+        k = self._dev.get(key)
+        if k is None:
+            md = {n: (v.detach().cpu() if torch.is_tensor(v) else v) for n, v in self.map_data.items()}
+            image = md["image"].float()
+            H, W = image.shape[:2]
+            texels = torch.cat([rgb_to_hsv(image.reshape(-1, 3)), md["image_mask"].float().reshape(-1, 1)], dim=1)
+            v_o = md["v_image_o"].float()
+            v_ow, v_oh = md["v_image_w"].float() - v_o, md["v_image_h"].float() - v_o
+            quad = torch.cat([v_o, v_ow, v_oh, md["v_image_norm"].float(),
+                              (torch.norm(v_ow, 2) ** 2)[None], (torch.norm(v_oh, 2) ** 2)[None]]).numpy().copy()
+            k = {"texture": texels.reshape(H, W, 4).contiguous().to(device), "quad": quad,
+                 "hsv": md["hsv"].tolist() if "hsv" in md else None, "light": float(md["rgb_light_offset"])}
+            self._dev[key] = k
+        return k
 
     def map_color_masked(self, points, dirs, colors, mask):
         """the renderers' use of map_color (SealNeRF/renderer.py:316, 396-399): `colors[mask] = map_color(points[mask],
-        dirs[mask], colors[mask])` — returns a new tensor, `colors` is left alone"""
+        dirs[mask], colors[mask])` — returns a new tensor, `colors` is left alone.  GPU tensors of a `native` mapper go through
+        the device kernels: `hsv` / `rgb` through s3d_seal_map_color, a texture (with or without `hsv`) through
+        s3d_seal_map_color_image; `rgb` together with a texture, and everything else, through map_color's torch ops."""
         md = self.map_data
-        if (self.native and colors.is_cuda and mask is not None and colors.dtype in (torch.float32, torch.float16) and colors.dim() == 2
-                and colors.shape[1] == 3 and "image" not in md and ("hsv" in md or "rgb" in md)):
+        on_device = (self.native and colors.is_cuda and mask is not None and colors.dtype in (torch.float32, torch.float16)
+                     and colors.dim() == 2 and colors.shape[1] == 3)
+        if on_device and "image" in md and "rgb" not in md and points is not None and points.is_cuda and points.shape == colors.shape:
+            # texture painting (with or without `hsv`): the batch mean, then one pass with one 16-byte texel load per moved
+            # sample (csrc/seal.hip: s3d_seal_map_color_image).  With `rgb` as well the texture step's batch mean depends on
+            # the `rgb` step's, a third pass: that combination takes the torch op sequence below, on the GPU.
+            import s3d_hip
+            k = self._image_native(colors.device)
+            src = colors.contiguous()
+            out = torch.empty_like(src)
+            s3d_hip.SealBackend.map_color_image(src, points.float().contiguous(), mask.view(torch.uint8), k["hsv"], k["texture"], k["quad"],
+                                                k["light"], out, n_valid=s3d_hip.active_row_limit(src.shape[0]))
+            return out
+        if on_device and "image" not in md and ("hsv" in md or "rgb" in md):
             # one or two passes on the device (csrc/seal.hip: s3d_seal_map_color) instead of a boolean gather (host sync), ~40
             # masked elementwise launches and a scatter back; the batch mean of the `rgb` edit is an order-independent sum
             import s3d_hip
@@ -245,7 +361,6 @@ class SealMapper:
             out[mask] = self.map_color(points[mask] if points is not None else None, dirs[mask] if dirs is not None else None,
                                        sel.float()).to(colors.dtype)
         return out
-
 
 
 class SealBBoxMapper(SealMapper):
@@ -289,6 +404,7 @@ class SealBBoxMapper(SealMapper):
             self.map_data["map_source"] = torch.tensor(seal_config["mapSource"], dtype=torch.float32)
         self.map_triangles = torch.tensor(tris, dtype=torch.float32)
         self.device = torch.device("cpu")
+        self._dev = {}  # (per-device constants of the shared colour routes; every tool has one)
         # the same constants as float32 host arrays for the device kernel (csrc/seal.hip)
         md = self.map_data
         self._host = {"triangles": self.map_triangles.numpy().copy(),
@@ -379,12 +495,14 @@ class SealBrushMapper(SealMapper):
     """brush tool (seal_utils.py:282-453): push (brushPressure > 0) or pull the surface under one or more `line` strokes along
     the strokes' plane normal.  Config keys: `raw` (one stroke [N, 3] or a list of strokes), `normal` (which side of the plane
     is positive), `brushType` ('line', or a list with one entry per stroke), `brushDepth`, `brushPressure`,
-    `attenuationDistance`, `attenuationMode` ('linear' | 'dry'), optional `hsv` / `rgb` / `rgbLightOffset`.
+    `attenuationDistance`, `attenuationMode` ('linear' | 'dry'), optional `hsv` / `rgb` / `rgbLightOffset`, optional
+    `imageConfig` (texture painting: `o`, `w`, `h` = origin, end of the width axis and end of the height axis of the image
+    quad, and the texels as `pixels` or `path`, see load_texture).
     Each stroke's edit region is the oriented box of its points lifted by 2 * normal_expand and sunk by brushDepth *
     normal_expand (12 triangles); a sample inside is moved back by normal_expand, less the part that attenuates linearly with
     the distance of its projection on the plane to the nearest border point of the strokes."""
 
-    def __init__(self, seal_config):
+    def __init__(self, seal_config, image_loader=None):
         self.config = seal_config
         strokes = seal_config["raw"]
         if np.asarray(strokes[0]).ndim == 1:
@@ -425,6 +543,16 @@ class SealBrushMapper(SealMapper):
             "attenuation_mode": mode,
         }
         self._color_options(seal_config)
+        if "imageConfig" in seal_config:  # seal_utils.py:382-404
+            conf = seal_config["imageConfig"]
+            image, alpha = load_texture(conf, image_loader)
+            quad = [np.asarray(conf[k], dtype=np.float64) for k in ("o", "w", "h")]
+            self.map_data["rgb_light_offset"] = float(seal_config.get("rgbLightOffset", 0))
+            self.map_data["image"] = torch.from_numpy(image)
+            self.map_data["image_mask"] = torch.from_numpy(alpha)
+            self.map_data["v_image_norm"] = torch.tensor(fit_plane(quad)[0], dtype=torch.float32)
+            for k, v in zip(("v_image_o", "v_image_w", "v_image_h"), quad):
+                self.map_data[k] = torch.tensor(v, dtype=torch.float32)
         self.map_triangles = torch.tensor(np.concatenate(tris), dtype=torch.float32)
         self.map_test_dir = self.map_data["normal_expand"][None].clone()  # the UNnormalised ray direction of the inside test
         self.device = torch.device("cpu")
@@ -572,18 +700,20 @@ class SealAnchorMapper(SealMapper):
         return out_p, dirs, valid
 
 
-def get_seal_mapper(config_dict=None, config_file=None):
-    """seal_utils.py:573-584 (plain JSON instead of json5)"""
+def get_seal_mapper(config_dict=None, config_file=None, image_loader=None):
+    """seal_utils.py:573-584 (plain JSON instead of json5).  `image_loader`: decoder of a brush `imageConfig` whose `path`
+    is an encoded image file, a callable path -> ndarray [H, W, 3 | 4] in RGB(A) order (e.g. pil_image_loader); inline
+    `pixels` and `.npy` paths need none."""
     if config_dict is None:
         with open(config_file) as f:
             config_dict = json.load(f)
     kind = config_dict["type"]
-    if "imageConfig" in config_dict:
-        raise NotImplementedError("imageConfig: the texture remap (seal_utils.py:394-416) needs cv2 and an image file")
+    if "imageConfig" in config_dict and kind != "brush":
+        raise NotImplementedError(f"imageConfig: only the brush tool paints a texture (seal_utils.py:382-404), not `{kind}`")
     if kind == "bbox":
         return SealBBoxMapper(config_dict)
     if kind == "brush":
-        return SealBrushMapper(config_dict)
+        return SealBrushMapper(config_dict, image_loader)
     if kind == "anchor":
         return SealAnchorMapper(config_dict)
     raise NotImplementedError(f"unknown seal tool `{kind}` (bbox, brush, anchor)")
