@@ -495,7 +495,8 @@ int s3d_ngp_mid2_forward(const uint16_t* h, const float* dirs, const uint16_t* e
 /* Build extension — s3d_composite_rays_train_loss with a PER-RAY background: bg [N,3] (device, fp32) replaces the 3 host floats,
  * and grad_bg [N,3] = d loss / d bg = (d loss / d pixel) * (1 - weights_sum) is written as well — the input of
  * s3d_background_backward (nerf/renderer.py:316 with `bg_color = self.background(sph, rays_d)`, :159-161).  Same launches, same
- * expressions as the constant form. */
+ * expressions as the constant form.  grad_bg NULL: a background that needs no gradient (the random background of RGBA
+ * frames, s3d_rgba_targets); that one store is skipped. */
 int s3d_composite_rays_train_loss_bg(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
                                      uint32_t M, uint32_t N, float T_thresh, const float* gt, const float* bg,
                                      const float* grad_loss, const float* gt_depth, float depth_weight,
@@ -701,6 +702,26 @@ int s3d_sample_train_rays(const float* error_map, const int64_t* index, uint32_t
                           const float* depths, uint32_t seed, int32_t* ctl, const float* u_keys, const float* u_fine,
                           float* rays_o, float* rays_d, float* gt, float* gt_depth, int64_t* inds, int64_t* inds_coarse,
                           int64_t* out_index, s3d_stream_t stream);
+/* s3d_sample_train_rays for RGBA frames, images [n_img,H,W,4]: the same draw (inds, inds_coarse and rays are those of
+ * s3d_sample_train_rays on the same arguments), and each winner's pixel is blended onto its background as s3d_rgba_targets
+ * does for row = b * N + n, in the same launch: gt [B,N,3] the blended target, bg [B,N,3] (optional) the background.  u_bg
+ * [B,N,3] in [0, 1) (test entry) replaces the background's hash; ctl is left alone only when every random number of the
+ * launch is explicit (u_keys, u_fine and — with random_bg — u_bg). */
+int s3d_sample_train_rays_rgba(const float* error_map, const int64_t* index, uint32_t B, uint32_t N, uint32_t n_img, uint32_t H,
+                               uint32_t W, const float* poses, const float* intrinsics, const void* images, int images_dtype,
+                               const float* depths, uint32_t seed, int32_t* ctl, const float* u_keys, const float* u_fine,
+                               int random_bg, const float* u_bg, float* rays_o, float* rays_d, float* gt, float* bg,
+                               float* gt_depth, int64_t* inds, int64_t* inds_coarse, int64_t* out_index, s3d_stream_t stream);
+/* Training targets of RGBA rows (nerf/utils.py:465-474; :549-554 with random_bg 0): images [R,4] fp32 / fp16 (aligned to one
+ * pixel; fp16 is widened to fp32 first) -> bg [R,3] and gt [R,3] = fl(fl(rgb * a) + fl(bg * fl(1 - a))), fp32, no contraction:
+ * with the same bg, bit for bit torch's expression on fp32 frames.  random_bg 0: bg = 1 (the bg pointer may be NULL).
+ * random_bg 1: bg[row, c] = (float)(hash_u32(bg_key, ctl[0], 3 * row + c) >> 8) * 2^-24 — 24 bits in [0, 1) — with
+ * bg_key = pcg_hash(seed ^ 0x3C6EF372), pcg_hash(v): v = v * 747796405 + 2891336453; w = ((v >> ((v >> 28) + 4)) ^ v) *
+ * 277803737; (w >> 22) ^ w, and hash_u32(key, step, n) = pcg_hash(pcg_hash(key ^ (step * 0x9E3779B9)) + n), all in uint32.
+ * ctl [2] int32 on the device = {step, 0}: the last workgroup advances ctl[0], so a captured launch draws a fresh
+ * background on every replay.  Test entry: u_bg [R,3] in [0, 1) replaces the hash and leaves ctl alone. */
+int s3d_rgba_targets(const void* images, int images_dtype, uint32_t R, int random_bg, uint32_t seed, int32_t* ctl,
+                     const float* u_bg, float* gt, float* bg, s3d_stream_t stream);
 /* Build extension — the error-map EMA of nerf/utils.py:506-528 after a step's loss: for ray r = (b, n) of the batch,
  * err = mean_c((image + (1 - weights_sum) * bg - gt)^2) (+ depth_weight * mean_r |nan_to_num(depth) - gt_depth|, reduced in a
  * fixed order inside the launch), then error_map[index[b], inds_coarse[r]] = 0.1 old + 0.9 err.  bg: 3 HOST floats bg_rgb or a

@@ -1706,7 +1706,7 @@ S3D_EXPORT int s3d_composite_rays_train_loss_bg(const float* sigmas, const float
                                                 float* grad_image, float* grad_weights_sum, float* grad_bg, float* loss, float* workspace,
                                                 s3d_stream_t stream) {
     if (N == 0) return S3D_OK;
-    S3D_REQUIRE(rays && weights_sum && depth && image && gt && bg && grad_bg && grad_loss && loss && workspace,
+    S3D_REQUIRE(rays && weights_sum && depth && image && gt && bg && grad_loss && loss && workspace,
                 "composite_rays_train_loss_bg: null pointer");
     S3D_REQUIRE(M == 0 || (sigmas && rgbs && deltas && grad_sigmas && grad_rgbs), "composite_rays_train_loss_bg: null sample buffer");
     S3D_REQUIRE((grad_image == nullptr) == (grad_weights_sum == nullptr), "composite_rays_train_loss_bg: grad_image and "

@@ -14,6 +14,13 @@
 //  * s3d_error_map_update: one workgroup; the depth term's batch mean is reduced first in a fixed order, then every ray's
 //    error (the torch route's float expressions) is folded into its cell as 0.1 old + 0.9 err.  A non-finite error leaves the
 //    cell's old value in place.
+//  * s3d_rgba_targets / s3d_sample_train_rays_rgba: training targets of RGBA frames (nerf/utils.py:465-474).  Each row's
+//    background is 1 or three uniforms in [0, 1), and gt = rgb * a + bg * (1 - a) in fp32 (fp16 frames are widened first).
+//    Keying of the uniforms: bg_key = pcg_hash(seed ^ 0x3C6EF372), u = (float)(hash_u32(bg_key, step, 3 * row + c) >> 8) * 2^-24
+//    for channel c of batch slot row = b * N + n (s3d_rgba_targets: the row itself), step = ctl[0] — a constant none of the
+//    sampler's other keys uses (pixels 0x5BD1E995, rows 0x632BE5AB, fine perturb 0xA511E9B3), so what they draw for a seed
+//    does not move.  The sampler's RGBA form is the same kernel body (template flag): one launch gathers four channels, blends,
+//    and writes gt and bg.
 #include "s3d_common.hpp"
 
 #include <math.h>
@@ -59,11 +66,65 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_wave
     return s_wave[kWaves + wave] + incl - v;
 }
 
+constexpr uint32_t kBgKeySalt = 0x3C6EF372u;
+constexpr uint32_t kTargetsBlock = 256;
+
+// one RGBA pixel (16-byte load of fp32 frames, 8-byte load of fp16 frames widened to fp32)
+__device__ __forceinline__ float4 load_rgba(const void* __restrict__ images, size_t pix, bool f16) {
+    if (f16) {
+        const uint2 raw = reinterpret_cast<const uint2*>(images)[pix];
+        const __half2 lo = *reinterpret_cast<const __half2*>(&raw.x), hi = *reinterpret_cast<const __half2*>(&raw.y);
+        return make_float4(__low2float(lo), __high2float(lo), __low2float(hi), __high2float(hi));
+    }
+    return reinterpret_cast<const float4*>(images)[pix];
+}
+
+// background and blended target of one row (nerf/utils.py:465-474): bg = 1, the caller's uniforms, or the counter hash;
+// gt = fl(fl(rgb * a) + fl(bg * fl(1 - a))) — torch's expression, no contraction
+__device__ __forceinline__ void rgba_target(float4 px, uint32_t random_bg, const float* __restrict__ u_bg, uint32_t bg_key,
+                                            uint32_t step, size_t row, float* __restrict__ gt, float* __restrict__ bg) {
+    const float rgb[3] = {px.x, px.y, px.z};
+    const float ia = 1.0f - px.w;
+#pragma unroll
+    for (uint32_t c = 0; c < 3; c++) {
+        float v = 1.0f;
+        if (random_bg) v = u_bg ? u_bg[row * 3 + c] : (float)(hash_u32(bg_key, step, 3u * (uint32_t)row + c) >> 8) * (1.0f / 16777216.0f);
+        const float fg = rgb[c] * px.w, back = v * ia;
+        gt[row * 3 + c] = fg + back;
+        if (bg) bg[row * 3 + c] = v;
+    }
+}
+
+// the last workgroup to finish advances the step number (every workgroup read it first); called by one thread per workgroup
+// behind a __syncthreads()
+__device__ __forceinline__ void advance_step(int32_t* ctl, uint32_t step) {
+    __threadfence();
+    const int32_t arrived = atomicAdd(&ctl[1], 1);
+    if (arrived == (int32_t)gridDim.x - 1) {
+        __threadfence();
+        ctl[1] = 0;
+        ctl[0] = (int32_t)(step + 1u);
+    }
+}
+
+__global__ void __launch_bounds__(kTargetsBlock)
+k_rgba_targets(const void* __restrict__ images, uint32_t f16, uint32_t R, uint32_t random_bg, uint32_t seed, int32_t* ctl,
+               const float* __restrict__ u_bg, float* __restrict__ gt, float* __restrict__ bg) {
+    const uint32_t step = ctl ? (uint32_t)ctl[0] : 0u;
+    const uint32_t bg_key = pcg_hash(seed ^ kBgKeySalt);
+    for (uint32_t r = blockIdx.x * kTargetsBlock + threadIdx.x; r < R; r += gridDim.x * kTargetsBlock)
+        rgba_target(load_rgba(images, r, f16 != 0), random_bg, u_bg, bg_key, step, r, gt, bg);
+    if (ctl) {
+        __syncthreads();
+        if (threadIdx.x == 0) advance_step(ctl, step);
+    }
+}
+
 struct SampleArgs {
     const float* error_map;  // [n_img, 16384] or NULL (uniform pixels)
     const int64_t* index;    // [B] image of each batch row
     const float* poses;      // [n_img, 4, 4]
-    const void* images;      // [n_img, H, W, 3] fp32 / fp16 or NULL
+    const void* images;      // [n_img, H, W, 3] (kRgba: 4) fp32 / fp16 or NULL
     const float* depths;     // [n_img, H * W] or NULL
     const float* u_keys;     // [B, 16384] or NULL (test entry: explicit uniforms of the keys)
     const float* u_fine;     // [B, N, 2] or NULL (test entry: explicit uniforms of the fine perturb)
@@ -75,13 +136,17 @@ struct SampleArgs {
     int64_t* inds;
     int64_t* inds_coarse;
     int64_t* out_index;      // [B] copy of index or NULL (the static index buffer of a captured step)
+    const float* u_bg;       // kRgba: [B, N, 3] or NULL (test entry: explicit uniforms of the background)
+    float* bg;               // kRgba: [B, N, 3] or NULL
+    uint32_t random_bg;      // kRgba: 0 = blend onto 1
     uint32_t N, n_img, H, W, seed, img_f16;
     float fx, fy, cx, cy, sx, sy;
 };
 
 // the ray of pixel `pix` into row b's slot n (get_rays: pixel centre, normalised direction, cam2world rotation) + targets
+template <bool kRgba>
 __device__ __forceinline__ void emit_ray(const SampleArgs& a, uint32_t b, uint32_t img, uint32_t n, uint32_t pix,
-                                         const float* __restrict__ pose) {
+                                         const float* __restrict__ pose, uint32_t step) {
     const size_t o = (size_t)b * a.N + n;
     const float i = (float)(pix % a.W) + 0.5f, j = (float)(pix / a.W) + 0.5f;
     const float x = (i - a.cx) / a.fx * 1.0f, y = (j - a.cy) / a.fy * 1.0f, z = 1.0f;
@@ -94,7 +159,10 @@ __device__ __forceinline__ void emit_ray(const SampleArgs& a, uint32_t b, uint32
     }
     a.inds[o] = (int64_t)pix;
     const size_t src = (size_t)img * a.H * a.W + pix;
-    if (a.images && a.gt) {
+    if (kRgba) {
+        if (a.images && a.gt)
+            rgba_target(load_rgba(a.images, src, a.img_f16 != 0), a.random_bg, a.u_bg, pcg_hash(a.seed ^ kBgKeySalt), step, o, a.gt, a.bg);
+    } else if (a.images && a.gt) {
         if (a.img_f16) {
             const __half* im = reinterpret_cast<const __half*>(a.images);
 #pragma unroll
@@ -108,6 +176,7 @@ __device__ __forceinline__ void emit_ray(const SampleArgs& a, uint32_t b, uint32
     if (a.depths && a.gt_depth) a.gt_depth[o] = a.depths[src];
 }
 
+template <bool kRgba>
 __global__ void __launch_bounds__(kSampleBlock) k_sample_train_rays(SampleArgs a) {
     __shared__ uint32_t s_hist[kWaves * 256];
     __shared__ uint32_t s_scan[2 * kWaves];
@@ -129,7 +198,7 @@ __global__ void __launch_bounds__(kSampleBlock) k_sample_train_rays(SampleArgs a
         const uint32_t key = pcg_hash(a.seed ^ 0x5BD1E995u), HW = a.H * a.W;
         for (uint32_t n = t; n < a.N; n += kSampleBlock) {
             const uint32_t pix = (uint32_t)(((uint64_t)hash_u32(key, step, n) * HW) >> 32);
-            emit_ray(a, b, img, n, pix, pose);
+            emit_ray<kRgba>(a, b, img, n, pix, pose, step);
         }
     } else {
         // keys of this thread's 16 consecutive cells, in registers
@@ -209,7 +278,7 @@ __global__ void __launch_bounds__(kSampleBlock) k_sample_train_rays(SampleArgs a
                     px = px < a.H - 1 ? px : a.H - 1;
                     py = py < a.W - 1 ? py : a.W - 1;
                     a.inds_coarse[(size_t)b * a.N + n] = (int64_t)c;
-                    emit_ray(a, b, img, n, px * a.W + py, pose);
+                    emit_ray<kRgba>(a, b, img, n, px * a.W + py, pose, step);
                 }
             }
             gt_before += gt;
@@ -219,15 +288,7 @@ __global__ void __launch_bounds__(kSampleBlock) k_sample_train_rays(SampleArgs a
     // the last workgroup to finish advances the step number (every workgroup read it above)
     if (a.ctl) {
         __syncthreads();
-        if (t == 0) {
-            __threadfence();
-            const int32_t arrived = atomicAdd(&a.ctl[1], 1);
-            if (arrived == (int32_t)gridDim.x - 1) {
-                __threadfence();
-                a.ctl[1] = 0;
-                a.ctl[0] = (int32_t)(step + 1u);
-            }
-        }
+        if (t == 0) advance_step(a.ctl, step);
     }
 }
 
@@ -289,11 +350,15 @@ k_error_map_update(float* __restrict__ error_map, const int64_t* __restrict__ in
 
 using namespace s3d;
 
-S3D_EXPORT int s3d_sample_train_rays(const float* error_map, const int64_t* index, uint32_t B, uint32_t N, uint32_t n_img,
-                                     uint32_t H, uint32_t W, const float* poses, const float* intrinsics, const void* images,
-                                     int images_dtype, const float* depths, uint32_t seed, int32_t* ctl, const float* u_keys,
-                                     const float* u_fine, float* rays_o, float* rays_d, float* gt, float* gt_depth, int64_t* inds,
-                                     int64_t* inds_coarse, int64_t* out_index, s3d_stream_t stream) {
+namespace s3d {
+namespace {
+
+// s3d_sample_train_rays and its RGBA form: one argument check, one launch
+int launch_sample(bool rgba, const float* error_map, const int64_t* index, uint32_t B, uint32_t N, uint32_t n_img, uint32_t H,
+                  uint32_t W, const float* poses, const float* intrinsics, const void* images, int images_dtype, const float* depths,
+                  uint32_t seed, int32_t* ctl, const float* u_keys, const float* u_fine, int random_bg, const float* u_bg,
+                  float* rays_o, float* rays_d, float* gt, float* bg, float* gt_depth, int64_t* inds, int64_t* inds_coarse,
+                  int64_t* out_index, s3d_stream_t stream) {
     S3D_REQUIRE(index && poses && intrinsics && rays_o && rays_d && inds, "s3d_sample_train_rays: null argument");
     S3D_REQUIRE(B > 0 && N > 0 && n_img > 0 && H > 0 && W > 0, "s3d_sample_train_rays: empty batch or frame");
     S3D_REQUIRE(images_dtype == S3D_F32 || images_dtype == S3D_F16, "s3d_sample_train_rays: images must be fp32 or fp16");
@@ -306,17 +371,66 @@ S3D_EXPORT int s3d_sample_train_rays(const float* error_map, const int64_t* inde
     } else {
         S3D_REQUIRE(ctl, "s3d_sample_train_rays: uniform pixels need ctl");
     }
+    const bool draws_bg = rgba && images && gt && random_bg && !u_bg;
+    const bool explicit_draw = error_map && u_keys && u_fine;
+    if (rgba) {
+        S3D_REQUIRE((uint64_t)B * N * 3 < (1ull << 32), "s3d_sample_train_rays_rgba: batch too large");
+        S3D_REQUIRE((reinterpret_cast<uintptr_t>(images) & (images_dtype == S3D_F16 ? 7u : 15u)) == 0,
+                    "s3d_sample_train_rays_rgba: images must be aligned to one RGBA pixel");
+        S3D_REQUIRE(!bg || (images && gt), "s3d_sample_train_rays_rgba: bg is written with gt");
+        S3D_REQUIRE(!draws_bg || ctl, "s3d_sample_train_rays_rgba: a random background needs ctl or u_bg");
+    }
     SampleArgs a;
     a.error_map = error_map; a.index = index; a.poses = poses; a.images = images; a.depths = depths;
     a.u_keys = error_map ? u_keys : nullptr; a.u_fine = error_map ? u_fine : nullptr;
-    a.ctl = (error_map && u_keys && u_fine) ? nullptr : ctl;
+    a.ctl = (explicit_draw && !draws_bg) ? nullptr : ctl;
     a.rays_o = rays_o; a.rays_d = rays_d; a.gt = gt; a.gt_depth = gt_depth; a.inds = inds; a.inds_coarse = inds_coarse;
     a.out_index = out_index;
+    a.u_bg = u_bg; a.bg = bg; a.random_bg = random_bg != 0;
     a.N = N; a.n_img = n_img; a.H = H; a.W = W; a.seed = seed; a.img_f16 = images_dtype == S3D_F16;
     a.fx = intrinsics[0]; a.fy = intrinsics[1]; a.cx = intrinsics[2]; a.cy = intrinsics[3];
     a.sx = (float)((double)H / 128.0); a.sy = (float)((double)W / 128.0);
-    hipLaunchKernelGGL(k_sample_train_rays, dim3(B), dim3(kSampleBlock), 0, as_stream(stream), a);
+    if (rgba) hipLaunchKernelGGL(k_sample_train_rays<true>, dim3(B), dim3(kSampleBlock), 0, as_stream(stream), a);
+    else hipLaunchKernelGGL(k_sample_train_rays<false>, dim3(B), dim3(kSampleBlock), 0, as_stream(stream), a);
     return check_launch("k_sample_train_rays");
+}
+
+}  // namespace
+}  // namespace s3d
+
+S3D_EXPORT int s3d_sample_train_rays(const float* error_map, const int64_t* index, uint32_t B, uint32_t N, uint32_t n_img,
+                                     uint32_t H, uint32_t W, const float* poses, const float* intrinsics, const void* images,
+                                     int images_dtype, const float* depths, uint32_t seed, int32_t* ctl, const float* u_keys,
+                                     const float* u_fine, float* rays_o, float* rays_d, float* gt, float* gt_depth, int64_t* inds,
+                                     int64_t* inds_coarse, int64_t* out_index, s3d_stream_t stream) {
+    return launch_sample(false, error_map, index, B, N, n_img, H, W, poses, intrinsics, images, images_dtype, depths, seed, ctl, u_keys,
+                         u_fine, 0, nullptr, rays_o, rays_d, gt, nullptr, gt_depth, inds, inds_coarse, out_index, stream);
+}
+
+S3D_EXPORT int s3d_sample_train_rays_rgba(const float* error_map, const int64_t* index, uint32_t B, uint32_t N, uint32_t n_img,
+                                          uint32_t H, uint32_t W, const float* poses, const float* intrinsics, const void* images,
+                                          int images_dtype, const float* depths, uint32_t seed, int32_t* ctl, const float* u_keys,
+                                          const float* u_fine, int random_bg, const float* u_bg, float* rays_o, float* rays_d,
+                                          float* gt, float* bg, float* gt_depth, int64_t* inds, int64_t* inds_coarse,
+                                          int64_t* out_index, s3d_stream_t stream) {
+    return launch_sample(true, error_map, index, B, N, n_img, H, W, poses, intrinsics, images, images_dtype, depths, seed, ctl, u_keys,
+                         u_fine, random_bg, u_bg, rays_o, rays_d, gt, bg, gt_depth, inds, inds_coarse, out_index, stream);
+}
+
+S3D_EXPORT int s3d_rgba_targets(const void* images, int images_dtype, uint32_t R, int random_bg, uint32_t seed, int32_t* ctl,
+                                const float* u_bg, float* gt, float* bg, s3d_stream_t stream) {
+    if (R == 0) return S3D_OK;
+    S3D_REQUIRE(images && gt, "s3d_rgba_targets: null argument");
+    S3D_REQUIRE(images_dtype == S3D_F32 || images_dtype == S3D_F16, "s3d_rgba_targets: images must be fp32 or fp16");
+    S3D_REQUIRE((reinterpret_cast<uintptr_t>(images) & (images_dtype == S3D_F16 ? 7u : 15u)) == 0,
+                "s3d_rgba_targets: images must be aligned to one RGBA pixel");
+    S3D_REQUIRE((uint64_t)R * 3 < (1ull << 32), "s3d_rgba_targets: too many rows");
+    S3D_REQUIRE(!random_bg || bg, "s3d_rgba_targets: a random background is handed out in bg");
+    S3D_REQUIRE(!random_bg || u_bg || ctl, "s3d_rgba_targets: a random background needs ctl or u_bg");
+    int32_t* step_ctl = (random_bg && !u_bg) ? ctl : nullptr;  // (explicit uniforms, constant background: ctl is left alone)
+    hipLaunchKernelGGL(k_rgba_targets, dim3(stream_grid(R, kTargetsBlock)), dim3(kTargetsBlock), 0, as_stream(stream), images,
+                       (uint32_t)(images_dtype == S3D_F16), R, (uint32_t)(random_bg != 0), seed, step_ctl, random_bg ? u_bg : nullptr, gt, bg);
+    return check_launch("k_rgba_targets");
 }
 
 S3D_EXPORT int s3d_error_map_update(float* error_map, uint32_t n_img, const int64_t* index, const int64_t* inds_coarse, uint32_t B,

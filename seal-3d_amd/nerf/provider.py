@@ -6,7 +6,8 @@ Two ways to draw a batch:
   * `collate(index)`: the reference's torch sequence (nerf/synthetic.get_rays, error-map weighted when the map is on), CPU or GPU;
   * `sample(index, out=...)`: one launch of s3d_sample_train_rays on the GPU (csrc/raysample.hip) — cells drawn from the map by
     a device-side RNG whose step number advances on the device, rays formed and targets gathered straight into the caller's
-    buffers (the static inputs of a graph-replayed step: GraphedTrainer.static_batch)."""
+    buffers (the static inputs of a graph-replayed step: GraphedTrainer.static_batch); RGBA frames are blended onto their
+    per-pixel random background in the same launch."""
 import torch
 
 from .synthetic import get_rays
@@ -40,14 +41,17 @@ class DeviceSampling:
         """the batch of `collate(index)` drawn on the GPU in one launch (s3d_sample_train_rays).  `out`: dict of caller buffers
         to fill (rays_o, rays_d [B,N,3], images [B,N,3] fp32, inds, inds_coarse [B,N] int64, index [B] int64, depths [B,N]);
         missing entries are allocated.  With the map on, cells are drawn from it (exponential race: the distribution of
-        torch.multinomial without replacement, winners in ascending cell order); otherwise pixels are uniform."""
+        torch.multinomial without replacement, winners in ascending cell order); otherwise pixels are uniform.  RGBA frames
+        (nerf/utils.py:465-474) are blended in the same launch: `images` is the target on a per-pixel random background, which
+        is returned as `bg_color` [B,N,3] (the dataset's `random_bg=False`, for a model with bg_radius > 0: blended onto 1, no
+        `bg_color`).  The background's draws are keyed by `seed`: ranks of a data-parallel run use different seeds."""
         import s3d_hip
         if not self.poses.is_cuda:
             raise RuntimeError("sample() runs on the GPU: the dataset's poses must live there (use collate() on the CPU)")
         if self.num_rays <= 0:
             raise RuntimeError("sample() draws training batches: num_rays must be > 0")
-        if self.images is not None and self.images.shape[-1] != 3:
-            raise ValueError("sample(): RGBA frames (the reference's per-pixel random background) are not supported")
+        rgba = self.images is not None and self.images.shape[-1] == 4
+        random_bg = rgba and getattr(self, "random_bg", True)
         idx = self._index_tensor(index)
         B, N, dev = idx.numel(), self.num_rays, self.poses.device
         if self.error_map is not None and N > MAP_CELLS:
@@ -61,6 +65,8 @@ class DeviceSampling:
         out.setdefault("inds", new(B, N, dtype=torch.int64))
         if self.images is not None:
             out.setdefault("images", new(B, N, 3))
+        if random_bg:
+            out.setdefault("bg_color", new(B, N, 3))
         if self.depths is not None:
             out.setdefault("depths", new(B, N, 1))
         if self.error_map is not None:
@@ -72,10 +78,13 @@ class DeviceSampling:
         s3d_hip.RaySampleBackend.sample_train_rays(
             self.error_map, idx, N, self.H, self.W, self.poses.float().contiguous(), self.intrinsics, out["rays_o"], out["rays_d"],
             out["inds"], out.get("inds_coarse"), images, depths, out.get("images"), out.get("depths"), self.seed, self._ctl,
-            out_index=out_index if out_index is not None and out_index.data_ptr() != idx.data_ptr() else None)
+            out_index=out_index if out_index is not None and out_index.data_ptr() != idx.data_ptr() else None,
+            **(dict(rgba=True, random_bg=random_bg, out_bg=out["bg_color"] if random_bg else None) if rgba else {}))
         res = {"H": self.H, "W": self.W, "rays_o": out["rays_o"], "rays_d": out["rays_d"], "inds": out["inds"]}
         if self.images is not None:
             res["images"] = out["images"]
+        if random_bg:
+            res["bg_color"] = out["bg_color"]
         if self.depths is not None:
             res["depths"] = out["depths"]
         if self.error_map is not None:
@@ -89,7 +98,8 @@ class NeRFDataset(DeviceSampling):
     [n, 4, 4] cam2world, intrinsics (fx, fy, cx, cy).  `error_map=True` (training only): torch.ones(n, 128*128) on the
     device, the reference's per-image map of recent per-pixel loss (nerf/provider.py:234-256)."""
 
-    def __init__(self, images, poses, intrinsics, num_rays=4096, error_map=False, device=None, training=True, fp16=False, seed=0):
+    def __init__(self, images, poses, intrinsics, num_rays=4096, error_map=False, device=None, training=True, fp16=False, seed=0,
+                 random_bg=True):
         self.device = torch.device(device) if device is not None else poses.device
         self.training = training
         self.poses = poses.to(self.device).float()
@@ -98,6 +108,7 @@ class NeRFDataset(DeviceSampling):
         if images is not None:
             self.H, self.W = int(images.shape[1]), int(images.shape[2])
             self.images = images.to(torch.half if fp16 else torch.float).to(self.device)
+        self.random_bg = random_bg  # RGBA frames: sample() blends onto a per-pixel random background (False: onto 1)
         self.num_rays = num_rays if training else -1
         self.error_map = torch.ones(len(self.poses), MAP_CELLS, dtype=torch.float, device=self.device) \
             if (training and error_map) else None
@@ -108,7 +119,8 @@ class NeRFDataset(DeviceSampling):
 
     def collate(self, index, generator=None):
         """nerf/provider.py:283-327 for dataset poses: rays of `num_rays` pixels of images `index` (error-map weighted when the
-        map is on), their colours, and — with the map — `index` and `inds_coarse` for the trainer's update"""
+        map is on), their colours, and — with the map — `index` and `inds_coarse` for the trainer's update.  RGBA frames come
+        back with four channels: the caller blends them with nerf.trainer.rgba_targets"""
         B = len(index)
         poses = self.poses[index].to(self.device)
         error_map = None if self.error_map is None else self.error_map[index]

@@ -197,9 +197,14 @@ class NeRFRenderer(nn.Module):
                 sigmas = self.density_scale * sigmas
             fused = kwargs.get("fused_loss")  # (nerf/trainer.py: the criterion and its gradient inside the compositing launch)
             # a background model's per-ray colours [N, 3] take the same launch in its per-ray form, which also hands out their
-            # gradient (raymarching.composite_rays_train_loss_bg)
-            bg_model = (self.bg_radius > 0 and torch.is_tensor(bg_color) and bg_color.shape == (N, 3)
-                        and hasattr(raymarching.raymarching._backend, "composite_rays_train_loss_bg"))
+            # gradient (raymarching.composite_rays_train_loss_bg); so do the per-pixel random backgrounds of RGBA frames
+            # (nerf/utils.py:471; fp32, on the device, no gradient), without that gradient
+            if (self.bg_radius <= 0 and torch.is_tensor(bg_color) and bg_color.is_cuda and bg_color.dtype == torch.float32
+                    and not bg_color.requires_grad and bg_color.numel() == N * 3):
+                bg_color = bg_color.reshape(N, 3)
+            per_ray = torch.is_tensor(bg_color) and bg_color.shape == (N, 3) and (
+                self.bg_radius > 0 or (bg_color.is_cuda and bg_color.dtype == torch.float32 and not bg_color.requires_grad))
+            bg_model = per_ray and hasattr(raymarching.raymarching._backend, "composite_rays_train_loss_bg")
             if (fused is not None and kwargs.get("defer_background", False) and bg_model and sigmas.is_cuda
                     and fused.get("expected_grad") is not None and getattr(raymarching.raymarching._backend, "_composite_path", 0) == 0):
                 results["loss"], weights_sum, depth, image = raymarching.composite_rays_train_loss_bg(

@@ -53,6 +53,37 @@ class _BgMse(torch.autograd.Function):
         return (g_image, g_ws) + (None,) * 6
 
 
+def rgba_targets(images, random_bg=True, generator=None, seed=None, ctl=None):
+    """Training targets of RGBA frames (nerf/utils.py:465-474): `images` [..., 4] -> (gt_rgb [..., 3], bg_color), with
+    gt_rgb = rgb * a + bg_color * (1 - a) and bg_color a per-pixel random colour [..., 3] (`random_bg`) or the number 1 (a model
+    with bg_radius > 0, and evaluation: nerf/utils.py:549-554).  Three-channel frames pass through with bg_color 1.
+    Torch route (CPU tensors, or no `seed`): the reference's lines in the frames' dtype — `torch.rand_like`, so that
+    torch.manual_seed reproduces the reference's draw (`generator`: torch.rand from it instead).  Native route (CUDA tensors
+    and a `seed`): one launch of s3d_rgba_targets, fp32 results; `ctl` is the device int32 {step, 0} the launch advances, so a
+    captured launch draws a fresh background on every replay.  Under data parallelism every rank passes its own seed."""
+    if images.shape[-1] == 3:
+        return images, 1
+    if images.shape[-1] != 4:
+        raise ValueError(f"rgba_targets: frames have 3 or 4 channels, got {images.shape[-1]}")
+    if images.is_cuda and seed is not None:
+        import s3d_hip
+        if random_bg and ctl is None:
+            raise ValueError("rgba_targets: the native route draws the background at step ctl[0] (a device int32 tensor {step, 0})")
+        images = images.contiguous()
+        gt = torch.empty(*images.shape[:-1], 3, dtype=torch.float32, device=images.device)
+        bg = torch.empty_like(gt) if random_bg else None
+        s3d_hip.RaySampleBackend.rgba_targets(images, gt, bg, random_bg=random_bg, seed=seed, ctl=ctl if random_bg else None)
+        return gt, (bg if random_bg else 1)
+    rgb, a = images[..., :3], images[..., 3:]
+    if not random_bg:
+        bg = 1
+    elif generator is None:
+        bg = torch.rand_like(rgb)
+    else:
+        bg = torch.rand(rgb.shape, generator=generator, dtype=rgb.dtype, device=rgb.device)
+    return rgb * a + bg * (1 - a), bg
+
+
 def update_error_map(out, gt_rgb, error_map, gt_depth=None, depth_weight=1.0):
     """nerf/utils.py:506-528: fold the step's per-ray error into the error map as 0.1 old + 0.9 err.  `error_map` =
     (map [n, 128*128], index [B], inds_coarse [B, N]); err = mean_c((pred - gt)^2) (+ depth_weight * the batch's mean L1 depth
@@ -206,14 +237,16 @@ class Trainer:
         return False
 
     def _error_map_batch(self, index, inds_coarse, gt_rgb):
-        """(map, index, inds_coarse) of this step's update, or None (no map, or the batch was not drawn from it)"""
+        """(map, index, inds_coarse) of this step's update, or None (no map, or the batch was not drawn from it).  Targets
+        arrive blended: RGBA frames go through one of the two producers first, with or without a map."""
+        if gt_rgb is not None and not isinstance(gt_rgb, tuple) and gt_rgb.shape[-1] != 3:
+            raise ValueError("train_step takes blended targets [N, 3]: RGBA frames (the reference's per-pixel random background) are "
+                             "blended by NeRFDataset.sample() or nerf.trainer.rgba_targets(), which return gt_rgb and bg_color")
         if self.error_map is None or inds_coarse is None or index is None:
             return None
         if self.dist is not None:
             raise NotImplementedError("error map: not supported with data parallelism (the ranks' rays update one map; "
                                       "keeping it consistent across ranks is not implemented)")
-        if gt_rgb is not None and not isinstance(gt_rgb, tuple) and gt_rgb.shape[-1] != 3:
-            raise ValueError("error map: RGBA targets (the reference's per-pixel random background) are not supported")
         return (self.error_map, index, inds_coarse)
 
     def _eager_step(self, rays_o, rays_d, gt_rgb, bg_color=1):
@@ -293,7 +326,8 @@ class Trainer:
 
     def train_step(self, rays_o, rays_d, gt_rgb, bg_color=1, index=None, inds_coarse=None):
         """rays_o/d [N,3], gt_rgb [N,3].  Returns the (detached) loss tensor; no host sync.  `index` / `inds_coarse` (a batch
-        of NeRFDataset.collate / sample with the error map on): the step updates `self.error_map`."""
+        of NeRFDataset.collate / sample with the error map on): the step updates `self.error_map`.  `bg_color`: a number, three
+        numbers, or the per-ray background [N,3] fp32 the targets were blended onto (NeRFDataset.sample / rgba_targets)."""
         self._em_batch = self._error_map_batch(index, inds_coarse, gt_rgb)
         try:
             self.model.train()
@@ -342,6 +376,7 @@ class GraphedTrainer(Trainer):
         self.s_ro = torch.zeros(num_rays, 3, device=dev)
         self.s_rd = torch.zeros(num_rays, 3, device=dev)
         self.s_gt = torch.zeros(num_rays, 3, device=dev)
+        self.s_bg = torch.ones(num_rays, 3, device=dev)  # per-ray background of RGBA batches (nerf/utils.py:471)
         self.budget_factor = budget_factor
         self.graph_extra_state = graph_extra_state
         self.ues_graph, self.ues_mean, self.ues_warm = None, None, False
@@ -365,18 +400,19 @@ class GraphedTrainer(Trainer):
         self.s_index = torch.zeros(1, dtype=torch.int64, device=dev)
         self.s_inds_coarse = torch.zeros(1, num_rays, dtype=torch.int64, device=dev)
         self._graph_em = None
+        self._graph_bg = False  # the step on hand / captured composites on s_bg (True) or on the constant 1
 
     def static_batch(self):
         """the step's static input buffers as a `sample(out=...)` target (one image of num_rays rays): the sampler's launch
         writes the batch where the captured step reads it"""
         n = self.s_ro.shape[0]
         return {"rays_o": self.s_ro.view(1, n, 3), "rays_d": self.s_rd.view(1, n, 3), "images": self.s_gt.view(1, n, 3),
-                "inds_coarse": self.s_inds_coarse, "index": self.s_index}
+                "bg_color": self.s_bg.view(1, n, 3), "inds_coarse": self.s_inds_coarse, "index": self.s_index}
 
     def _static_loss(self):
         """the step's loss on the static input buffers (subclasses: other criteria, e.g. Seal's depth term)"""
         with torch.autocast("cuda", dtype=torch.float16, enabled=self.fp16):
-            out = self.model.render(self.s_ro, self.s_rd, bg_color=1, perturb=True, force_all_rays=False,
+            out = self.model.render(self.s_ro, self.s_rd, bg_color=self.s_bg if self._graph_bg else 1, perturb=True, force_all_rays=False,
                                     defer_background=self.native_optim, fused_loss=self._fused_loss(self.s_gt), **self.render_kwargs)
             return self._regularized(render_loss(out, self.s_gt, self._expected_grad(), error_map=self._em_batch))
 
@@ -516,12 +552,14 @@ class GraphedTrainer(Trainer):
             self.dist.sync_extra_state(model)
         return True
 
-    def _stage_inputs(self, rays_o, rays_d, gt_rgb):
-        if rays_o.data_ptr() == self.s_ro.data_ptr() and rays_d.data_ptr() == self.s_rd.data_ptr() \
-                and gt_rgb.data_ptr() == self.s_gt.data_ptr():
+    def _stage_inputs(self, rays_o, rays_d, gt_rgb, bg=None):
+        dst, src = [self.s_ro, self.s_rd, self.s_gt], [rays_o, rays_d, gt_rgb]
+        if bg is not None:
+            dst.append(self.s_bg)
+            src.append(bg)
+        if all(a.data_ptr() == b.data_ptr() for a, b in zip(dst, src)):
             return  # (drawn into the static buffers by the sampler: static_batch)
-        torch._foreach_copy_([self.s_ro, self.s_rd, self.s_gt],
-                             [rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), gt_rgb.reshape(-1, 3)])  # one launch
+        torch._foreach_copy_(dst, [t.reshape(-1, 3) for t in src])  # one launch
 
     def _stage_error_map(self, em):
         """the static (map, index, inds_coarse) of the captured step; the batch's are copied in unless the sampler wrote them
@@ -573,10 +611,21 @@ class GraphedTrainer(Trainer):
             loss = self._eager_step(rays_o, rays_d, gt_rgb, bg_color)
             self._sched_step()
             return loss
-        if bg_color != 1:
+        per_ray = torch.is_tensor(bg_color)
+        if per_ray:
+            if type(self)._static_loss is not GraphedTrainer._static_loss:
+                raise ValueError("GraphedTrainer: this trainer's captured criterion composites on bg_color=1")
+            if not (bg_color.is_cuda and bg_color.dtype == torch.float32 and bg_color.numel() == self.s_bg.numel()):
+                raise ValueError("GraphedTrainer: a per-ray background is an fp32 device tensor [num_rays, 3]")
+            self._stage_inputs(rays_o, rays_d, gt_rgb, bg_color.detach())
+        elif bg_color != 1:
             raise ValueError("GraphedTrainer: the captured step composites on the white background (bg_color=1) of the "
-                             "BASELINE configs; use Trainer for per-batch background colours")
-        self._stage_inputs(rays_o, rays_d, gt_rgb)
+                             "BASELINE configs or on a per-ray background tensor; use Trainer for other background colours")
+        else:
+            self._stage_inputs(rays_o, rays_d, gt_rgb)
+        if self.graph is not None and per_ray != self._graph_bg:
+            self.graph = None  # (captured for the other kind of background: re-capture)
+        self._graph_bg = per_ray
         if self._em_batch is not None:
             self._em_batch = self._stage_error_map(self._em_batch)
         em_key = None if self._em_batch is None else self._em_batch[0].data_ptr()

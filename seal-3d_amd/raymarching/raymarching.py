@@ -306,7 +306,9 @@ class _CompositeRaysTrainLoss(Function):
 
 class _CompositeRaysTrainLossBg(Function):
     """_CompositeRaysTrainLoss with a per-ray background `bg` [N,3] — the output of a background model (nerf/renderer.py:159-161,
-    316) — that receives a gradient as well (seal3d_hip.h: s3d_composite_rays_train_loss_bg, same launches)."""
+    316) — that receives a gradient as well (seal3d_hip.h: s3d_composite_rays_train_loss_bg, same launches).  A `bg` that does
+    not require grad (the per-pixel random background of RGBA frames, nerf/utils.py:471) takes the same launch without
+    `grad_bg`."""
 
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -323,7 +325,7 @@ class _CompositeRaysTrainLossBg(Function):
         loss = torch.empty((), dtype=torch.float32, device=dev)
         flat = (torch.zeros if zero_grads else torch.empty)(4 * M, dtype=torch.float32, device=dev)
         grad_sigmas, grad_rgbs = flat[:M], flat[M:].view(M, 3)
-        grad_bg = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        grad_bg = torch.empty(N, 3, dtype=torch.float32, device=dev) if ctx.needs_input_grad[6] else None
         if workspace is None:
             workspace = torch.empty(4 * N, dtype=torch.float32, device=dev)
         if gt_depth is not None:

@@ -49,7 +49,7 @@ EXPORTS = [
     "s3d_vm_features_backward", "s3d_vm_color_forward", "s3d_vm_color_backward",
     "s3d_composite_rays_train_loss_bg", "s3d_bg_targets_rays",
     "s3d_background_forward", "s3d_background_backward_workspace_size", "s3d_background_backward",
-    "s3d_sample_train_rays", "s3d_error_map_update",
+    "s3d_sample_train_rays", "s3d_error_map_update", "s3d_sample_train_rays_rgba", "s3d_rgba_targets",
 ]
 
 
@@ -431,11 +431,13 @@ class RaymarchingBackend:
     def composite_rays_train_loss_bg(sigmas, rgbs, deltas, rays, M, N, T_thresh, gt, bg, grad_loss, weights_sum, depth, image,
                                      grad_sigmas, grad_rgbs, grad_bg, loss, workspace, gt_depth=None, depth_weight=1.0,
                                      grad_image=None, grad_weights_sum=None):
-        """composite_rays_train_loss with a per-ray background bg [N,3] (device) and its gradient grad_bg [N,3] (seal3d_hip.h)"""
+        """composite_rays_train_loss with a per-ray background bg [N,3] (device) and its gradient grad_bg [N,3] (seal3d_hip.h);
+        grad_bg None: a background that needs no gradient (the random background of RGBA frames)"""
+        with_grad = {} if grad_bg is None else {"grad_bg": grad_bg}
         RaymarchingBackend._check_train_loss(
-            "composite_rays_train_loss_bg", M, N, gt_depth, grad_image, grad_weights_sum, ("gt", "bg", "grad_bg"), sigmas=sigmas,
-            rgbs=rgbs, deltas=deltas, gt=gt, bg=bg, grad_bg=grad_bg, grad_loss=grad_loss, loss=loss, workspace=workspace,
-            grad_sigmas=grad_sigmas, grad_rgbs=grad_rgbs)
+            "composite_rays_train_loss_bg", M, N, gt_depth, grad_image, grad_weights_sum, ("gt", "bg") + tuple(with_grad), sigmas=sigmas,
+            rgbs=rgbs, deltas=deltas, gt=gt, bg=bg, grad_loss=grad_loss, loss=loss, workspace=workspace,
+            grad_sigmas=grad_sigmas, grad_rgbs=grad_rgbs, **with_grad)
         _check(lib().s3d_composite_rays_train_loss_bg(_p(sigmas), _p(rgbs), _p(deltas), _p(rays), _u(M), _u(N), _f(T_thresh), _p(gt),
                                                       _p(bg), _p(grad_loss), _p(gt_depth), _f(depth_weight), _p(weights_sum), _p(depth),
                                                       _p(image), _p(grad_sigmas), _p(grad_rgbs), _p(grad_image), _p(grad_weights_sum),
@@ -1090,12 +1092,15 @@ class RaySampleBackend:
 
     @staticmethod
     def sample_train_rays(error_map, index, N, H, W, poses, intrinsics, rays_o, rays_d, inds, inds_coarse=None, images=None,
-                          depths=None, gt=None, gt_depth=None, seed=0, ctl=None, u_keys=None, u_fine=None, out_index=None):
-        """seal3d_hip.h: s3d_sample_train_rays.  index [B] int64; outputs [B, N, ...] preallocated by the caller"""
+                          depths=None, gt=None, gt_depth=None, seed=0, ctl=None, u_keys=None, u_fine=None, out_index=None,
+                          rgba=False, random_bg=True, u_bg=None, out_bg=None):
+        """seal3d_hip.h: s3d_sample_train_rays.  index [B] int64; outputs [B, N, ...] preallocated by the caller.  `rgba`:
+        images are [n_images, H, W, 4] and s3d_sample_train_rays_rgba blends them into gt (onto `random_bg`: a per-pixel
+        random background, handed out in out_bg [B, N, 3]; False: onto 1); u_bg [B, N, 3]: explicit uniforms (test entry)"""
         B = index.numel()
         _need(index, torch.int64, "index"); _need(poses, torch.float32, "poses"); _need(inds, torch.int64, "inds")
         for t, n in ((rays_o, "rays_o"), (rays_d, "rays_d"), (gt, "gt"), (gt_depth, "gt_depth"), (error_map, "error_map"),
-                     (depths, "depths"), (u_keys, "u_keys"), (u_fine, "u_fine")):
+                     (depths, "depths"), (u_keys, "u_keys"), (u_fine, "u_fine"), (u_bg, "u_bg"), (out_bg, "out_bg")):
             if t is not None:
                 _need(t, torch.float32, n)
         for t, n in ((inds_coarse, "inds_coarse"), (out_index, "out_index")):
@@ -1106,7 +1111,7 @@ class RaySampleBackend:
         if ctl is not None:
             _need(ctl, torch.int32, "ctl")
         for t, n, w in ((rays_o, "rays_o", 3), (rays_d, "rays_d", 3), (inds, "inds", 1), (inds_coarse, "inds_coarse", 1),
-                        (gt, "gt", 3), (gt_depth, "gt_depth", 1), (u_fine, "u_fine", 2)):
+                        (gt, "gt", 3), (gt_depth, "gt_depth", 1), (u_fine, "u_fine", 2), (u_bg, "u_bg", 3), (out_bg, "out_bg", 3)):
             if t is not None and t.numel() != B * N * w:
                 raise RuntimeError(f"sample_train_rays: {n} must hold {B} x {N} x {w} values")
         n_img = poses.shape[0]
@@ -1114,18 +1119,47 @@ class RaySampleBackend:
             raise RuntimeError("sample_train_rays: error_map must be [n_images, 128 * 128]")
         if u_keys is not None and u_keys.numel() != B * 128 * 128:
             raise RuntimeError("sample_train_rays: u_keys must be [B, 128 * 128]")
-        dt = F32
+        dt, ch = F32, 4 if rgba else 3
+        if not rgba and (u_bg is not None or out_bg is not None):
+            raise RuntimeError("sample_train_rays: u_bg / out_bg belong to RGBA frames (rgba=True)")
         if images is not None:
-            if images.dtype not in (torch.float32, torch.float16) or images.shape[-1] != 3 or images.numel() != n_img * H * W * 3:
-                raise RuntimeError("sample_train_rays: images must be [n_images, H, W, 3] fp32 / fp16")
+            if images.dtype not in (torch.float32, torch.float16) or images.shape[-1] != ch or images.numel() != n_img * H * W * ch:
+                raise RuntimeError(f"sample_train_rays: images must be [n_images, H, W, {ch}] fp32 / fp16")
             dt = F16 if images.dtype == torch.float16 else F32
         if depths is not None and depths.numel() != n_img * H * W:
             raise RuntimeError("sample_train_rays: depths must hold one value per pixel")
         intr = (C.c_float * 4)(*[float(v) for v in intrinsics])
+        if rgba:
+            _check(lib().s3d_sample_train_rays_rgba(_p(error_map), _p(index), _u(B), _u(N), _u(n_img), _u(H), _u(W), _p(poses), intr,
+                                                    _p(images), C.c_int(dt), _p(depths), _u(int(seed) & 0xFFFFFFFF), _p(ctl),
+                                                    _p(u_keys), _p(u_fine), C.c_int(1 if random_bg else 0), _p(u_bg), _p(rays_o),
+                                                    _p(rays_d), _p(gt), _p(out_bg), _p(gt_depth), _p(inds), _p(inds_coarse),
+                                                    _p(out_index), _stream()), "s3d_sample_train_rays_rgba")
+            return
         _check(lib().s3d_sample_train_rays(_p(error_map), _p(index), _u(B), _u(N), _u(n_img), _u(H), _u(W), _p(poses), intr,
                                            _p(images), C.c_int(dt), _p(depths), _u(int(seed) & 0xFFFFFFFF), _p(ctl), _p(u_keys),
                                            _p(u_fine), _p(rays_o), _p(rays_d), _p(gt), _p(gt_depth), _p(inds), _p(inds_coarse),
                                            _p(out_index), _stream()), "s3d_sample_train_rays")
+
+    @staticmethod
+    def rgba_targets(images, gt, bg=None, random_bg=True, seed=0, ctl=None, u_bg=None):
+        """seal3d_hip.h: s3d_rgba_targets.  images [..., 4] fp32 / fp16 -> gt [..., 3] fp32 blended onto bg [..., 3] fp32 (random_bg:
+        the per-pixel random background, drawn at step ctl[0] or taken from u_bg; False: 1, bg may be None)"""
+        if images.dtype not in (torch.float32, torch.float16) or images.dim() < 1 or images.shape[-1] != 4:
+            raise RuntimeError("rgba_targets: images must be [..., 4] fp32 / fp16")
+        R = images.numel() // 4
+        for t, n in ((gt, "gt"), (bg, "bg"), (u_bg, "u_bg")):
+            if t is not None:
+                _need(t, torch.float32, n)
+                if t.numel() != R * 3:
+                    raise RuntimeError(f"rgba_targets: {n} must hold {R} x 3 values")
+        if ctl is not None:
+            _need(ctl, torch.int32, "ctl")
+        if random_bg and bg is None:
+            raise RuntimeError("rgba_targets: a random background is handed out in bg")
+        _check(lib().s3d_rgba_targets(_p(images), C.c_int(F16 if images.dtype == torch.float16 else F32), _u(R),
+                                      C.c_int(1 if random_bg else 0), _u(int(seed) & 0xFFFFFFFF), _p(ctl), _p(u_bg), _p(gt), _p(bg),
+                                      _stream()), "s3d_rgba_targets")
 
     @staticmethod
     def error_map_update(error_map, index, inds_coarse, image, gt, weights_sum=None, bg=None, depth=None, gt_depth=None,
