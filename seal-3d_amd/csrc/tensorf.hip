@@ -1441,15 +1441,16 @@ __global__ void __launch_bounds__(256) k_vm_flush_reduce(VmFactors f, VmBackward
     }
 }
 
+// `planes` / `lines` null: the geometry alone (the keys / bins passes read no factor value)
 int fill_factors(VmFactors& f, const float* const* planes, const float* const* lines, const uint32_t* rank,
                  const uint32_t* resolution, uint32_t& rows) {
     static const uint32_t mat_ids[3][2] = {{0, 1}, {0, 2}, {1, 2}};  // tensoRF/network.py:37-38
     static const uint32_t vec_ids[3] = {2, 1, 0};
     rows = 0;
     for (uint32_t i = 0; i < 3; i++) {
-        S3D_REQUIRE(planes[i] && lines[i] && rank[i] > 0 && resolution[i] > 0, "vm features: empty factor %u", i);
-        f.plane[i] = planes[i];
-        f.line[i] = lines[i];
+        S3D_REQUIRE((!planes || planes[i]) && (!lines || lines[i]) && rank[i] > 0 && resolution[i] > 0, "vm features: empty factor %u", i);
+        f.plane[i] = planes ? planes[i] : nullptr;
+        f.line[i] = lines ? lines[i] : nullptr;
         f.plane_t[i] = nullptr;
         f.line_t[i] = nullptr;
         f.rank[i] = rank[i];
@@ -1464,6 +1465,10 @@ int fill_factors(VmFactors& f, const float* const* planes, const float* const* l
     }
     return S3D_OK;
 }
+int fill_geometry(VmFactors& f, const uint32_t* rank, const uint32_t* resolution) {
+    uint32_t rows;
+    return fill_factors(f, nullptr, nullptr, rank, resolution, rows);
+}
 
 // the optional rank-fastest shadows of a call (s3d_vm_transpose_factors): taken when every rank is a multiple of four (16-byte loads)
 static void vm_set_shadows(VmFactors& f, const float* const* planes_t, const float* const* lines_t) {
@@ -1471,6 +1476,12 @@ static void vm_set_shadows(VmFactors& f, const float* const* planes_t, const flo
     for (uint32_t i = 0; i < 3; i++)
         if (!planes_t[i] || !lines_t[i] || f.rank[i] % 4 != 0 || (reinterpret_cast<uintptr_t>(planes_t[i]) | reinterpret_cast<uintptr_t>(lines_t[i])) & 15u) return;
     for (uint32_t i = 0; i < 3; i++) { f.plane_t[i] = planes_t[i]; f.line_t[i] = lines_t[i]; }
+}
+// the factor backward takes the planes' shadows alone (the tile loads of the plane passes), at any rank
+static void vm_set_plane_shadows(VmFactors& f, const float* const* planes_t) {
+    if (!planes_t || !planes_t[0] || !planes_t[1] || !planes_t[2]) return;
+    if ((reinterpret_cast<uintptr_t>(planes_t[0]) | reinterpret_cast<uintptr_t>(planes_t[1]) | reinterpret_cast<uintptr_t>(planes_t[2])) & 15u) return;
+    for (uint32_t i = 0; i < 3; i++) f.plane_t[i] = planes_t[i];
 }
 // [rank][cells] -> [cells][rank] for the three planes (cells = H * W) and the three lines (cells = Dn) of a factor set: a
 // workgroup moves 64 cells x all ranks through LDS (reads: 256-byte runs per rank, writes: 64 runs of rank x 4 bytes, contiguous)
@@ -1593,15 +1604,16 @@ __global__ void __launch_bounds__(256) k_weighted_abs_final(const float* __restr
 
 using namespace s3d;
 
-S3D_EXPORT uint32_t s3d_vm_backward_max_bins(const uint32_t* resolution) {
+// largest plane tile count over the three axis pairs
+static uint32_t vm_max_tiles(const uint32_t* resolution) {
     uint32_t m = 0;
     for (uint32_t a = 0; a < 3; a++)
-        for (uint32_t c = 0; c < 3; c++) {
-            if (a == c) continue;
-            const uint32_t t = div_up<uint32_t>(resolution[a], kVmTile) * div_up<uint32_t>(resolution[c], kVmTile);
-            m = t > m ? t : m;
-        }
-    return m;  // (>= the number of line chunks of any axis as well: ceil(res / 64) <= ceil(res / 8)^2)
+        for (uint32_t c = a + 1; c < 3; c++)
+            m = std::max(m, div_up<uint32_t>(resolution[a], kVmTile) * div_up<uint32_t>(resolution[c], kVmTile));
+    return m;
+}
+S3D_EXPORT uint32_t s3d_vm_backward_max_bins(const uint32_t* resolution) {
+    return vm_max_tiles(resolution);  // (>= the number of line chunks of any axis as well: ceil(res / 64) <= ceil(res / 8)^2)
 }
 
 S3D_EXPORT int s3d_vm_backward_keys(const float* x, uint32_t N, const uint32_t* rank, const uint32_t* resolution, int32_t* keys,
@@ -1609,9 +1621,7 @@ S3D_EXPORT int s3d_vm_backward_keys(const float* x, uint32_t N, const uint32_t* 
     if (N == 0) return S3D_OK;
     S3D_REQUIRE(x && rank && resolution && keys, "vm_backward_keys: null pointer");
     VmFactors f;
-    uint32_t rows;
-    const float* dummy[3] = {x, x, x};  // (only the geometry is used)
-    if (int rc = fill_factors(f, dummy, dummy, rank, resolution, rows)) return rc;
+    if (int rc = fill_geometry(f, rank, resolution)) return rc;
     hipLaunchKernelGGL(k_vm_keys, dim3(div_up<uint32_t>(N, 256)), dim3(256), 0, as_stream(stream), x, N, f, keys);
     return check_launch("vm_backward_keys");
 }
@@ -1629,9 +1639,7 @@ S3D_EXPORT int s3d_vm_backward_bins(const float* x, uint32_t N, const uint32_t* 
     S3D_REQUIRE((uint64_t)6 * N < (1ull << 31), "vm_backward_bins: batch too large");
     S3D_REQUIRE(workspace_bytes >= s3d_vm_backward_bins_workspace_size(N, n_bounds), "vm_backward_bins: workspace too small");
     VmFactors f;
-    uint32_t rows;
-    const float* dummy[3] = {x, x, x};  // (only the geometry is used)
-    if (int rc = fill_factors(f, dummy, dummy, rank, resolution, rows)) return rc;
+    if (int rc = fill_geometry(f, rank, resolution)) return rc;
     uint32_t* keys = reinterpret_cast<uint32_t*>(workspace);
     uint32_t* counts = keys + (size_t)6 * N;
     uint32_t* cursors = counts + (size_t)6 * n_bounds;
@@ -1649,24 +1657,19 @@ S3D_EXPORT int s3d_vm_backward_bins(const float* x, uint32_t N, const uint32_t* 
     return check_launch("vm_backward_bins");
 }
 
-// nominal sorted positions per workgroup, {plane, plane at rank <= 16, line, line at rank <= 16}: of the lane-per-rank passes
-// (same-box sweep, profiles/r11_tensorf_vm.md) and of the 32-points-per-trip passes (those serve ranks 32 .. 64 only: entries 0
-// and 2; line: 2,048 without the staged flush, 1,024 with it)
+// nominal sorted positions per workgroup of the lane-per-rank passes, {plane, plane at rank <= 16, line, line at rank <= 16}
+// (same-box sweep, profiles/r11_tensorf_vm.md), and of the 32-points-per-trip passes, which serve ranks 32 .. 64 only (line:
+// 2,048 without the staged flush, 1,024 with it)
 constexpr std::array<uint32_t, 4> kVmLanePts = {256u, 512u, 1024u, 1024u};
-constexpr std::array<uint32_t, 4> kVmMmPts = {512u, 512u, 1024u, 1024u};
-static_assert(kVmMmPts[0] <= kVmMaxPts && kVmMmPts[2] <= kVmMaxPts, "the accumulators' headroom: kVmMaxPts contributions per cell");
+constexpr uint32_t kVmMmPlanePts = 512, kVmMmLinePts = 1024;
+static_assert(kVmMmPlanePts <= kVmMaxPts && kVmMmLinePts <= kVmMaxPts, "the accumulators' headroom: kVmMaxPts contributions per cell");
 // staging rows of the flushes (VmBackward::stage_*): flags | plane rows | line rows
 struct VmStage { uint32_t tiles, lslots, R; size_t flag_words, plane_floats, line_floats, bytes; };
 static VmStage vm_stage_layout(uint32_t N, const uint32_t* rank, const uint32_t* resolution) {
     VmStage v{};
-    for (uint32_t i = 0; i < 3; i++) {
-        v.R = rank[i] > v.R ? rank[i] : v.R;
-        for (uint32_t j = i + 1; j < 3; j++) {
-            const uint32_t t = div_up<uint32_t>(resolution[i], kVmTile) * div_up<uint32_t>(resolution[j], kVmTile);
-            v.tiles = t > v.tiles ? t : v.tiles;
-        }
-    }
-    constexpr uint32_t min_line = std::min(std::min(std::min(kVmLanePts[2], kVmLanePts[3]), kVmMaxPts), kVmMmPts[2]);  // whichever line kernel runs
+    v.R = std::max(std::max(rank[0], rank[1]), rank[2]);
+    v.tiles = vm_max_tiles(resolution);
+    constexpr uint32_t min_line = std::min(std::min(std::min(kVmLanePts[2], kVmLanePts[3]), kVmMaxPts), kVmMmLinePts);  // whichever line kernel runs
     v.lslots = 2 * div_up<uint32_t>(N, min_line);
     v.flag_words = ((size_t)3 * v.tiles + (size_t)3 * v.lslots + 63) & ~(size_t)63;
     v.plane_floats = (size_t)3 * v.tiles * 32 * v.R;
@@ -1726,13 +1729,13 @@ static int launch_plane_mm_t(const float* x, uint32_t N, const VmFactors& f, VmB
         S3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vm_plane_backward_mm<RB, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
         device_setup_done(attr_devs, dev);
     }
-    b.pts_plane = kVmMmPts[0];
+    b.pts_plane = kVmMmPlanePts;
     hipLaunchKernelGGL((k_vm_plane_backward_mm<RB, MODE>), dim3(div_up<uint32_t>(N, b.pts_plane), 3), dim3(kVmMmThreads), smem, st, x, N, f, b);
     return S3D_OK;
 }
 template <int RB>
 static void launch_line_mm_t(const float* x, uint32_t N, const VmFactors& f, VmBackward& b, hipStream_t st) {
-    b.pts_line = kVmMmPts[2];
+    b.pts_line = kVmMmLinePts;
     const size_t smem = (size_t)(kVmZChunk + 1) * 16 * RB * sizeof(long long) + (size_t)kVmMmWaves * 32 * sizeof(uint4);
     hipLaunchKernelGGL((k_vm_line_backward_mm<RB>), dim3(div_up<uint32_t>(N, b.pts_line), 3), dim3(kVmMmThreads), smem, st, x, N, f, b);
 }
@@ -1761,6 +1764,93 @@ static int launch_plane_mm(const float* x, uint32_t N, const VmFactors& f, VmBac
     }
 }
 
+// one factor backward: what s3d_vm_features_backward (fp32 `grad`, `reduce`) and s3d_vm_color_backward (`basis`, fp16 `grad_out`,
+// `grad_basis`: the BASIS kernels) do not share, then everything they do
+struct VmBwdCall {
+    const char* name;  // the entry point, for the messages
+    bool reduce;
+    const float* grad;
+    const _Float16 *basis, *grad_out;
+    uint32_t basis_rows;
+    float* grad_basis;
+    const float* x;
+    uint32_t N, n_bounds;
+    const uint32_t *rank, *resolution;
+    const int32_t *perm, *start, *n_valid;
+    float *gm, *line_scratch, *found_inf;
+    float *const *grad_planes, *const *grad_lines;
+    const float* const* planes_t;
+    uint32_t* bound_words;
+    void* stage;
+    size_t stage_bytes;
+    hipStream_t stream;
+};
+
+// the plane and the line pass at RP lanes per point: the 32-points-per-trip kernels where the call is one of theirs
+template <int RP>
+static int vm_backward_passes(const VmBwdCall& c, const VmFactors& f, VmBackward& b, uint32_t max_rank) {
+    const float* x = c.x;
+    const uint32_t N = c.N;
+    hipStream_t st = c.stream;
+    dim3 gp, gl;
+    size_t smem_p, smem_l;
+    vm_backward_geometry(b, N, max_rank, c.basis != nullptr, gp, gl, smem_p, smem_l);
+    const dim3 block(kVmBwdThreads);
+    bool mm;
+    if (int rc = c.basis ? launch_plane_mm<2>(x, N, f, b, st, mm) : c.reduce ? launch_plane_mm<0>(x, N, f, b, st, mm) : launch_plane_mm<1>(x, N, f, b, st, mm))
+        return rc;
+    if (mm) {}
+    else if (c.basis) hipLaunchKernelGGL((k_vm_plane_backward<64, false, true>), gp, block, smem_p, st, x, N, f, b);  // (RP = 64 only)
+    else if (c.reduce) hipLaunchKernelGGL((k_vm_plane_backward<RP, true>), gp, block, smem_p, st, x, N, f, b);
+    else hipLaunchKernelGGL((k_vm_plane_backward<RP, false>), gp, block, smem_p, st, x, N, f, b);
+    if (!launch_line_mm(x, N, f, b, st)) hipLaunchKernelGGL((k_vm_line_backward<RP>), gl, block, smem_l, st, x, N, f, b);
+    return S3D_OK;
+}
+
+// `f`, `rows`: the call's factors (fill_factors)
+static int vm_factor_backward(const VmBwdCall& c, VmFactors& f, uint32_t rows) {
+    VmBackward b;
+    b.rows = rows;
+    vm_set_plane_shadows(f, c.planes_t);
+    uint32_t max_rank = 0, max_chunks = 0;
+    for (uint32_t i = 0; i < 3; i++) {
+        S3D_REQUIRE(c.grad_planes[i] && c.grad_lines[i], "%s: null gradient buffer %u", c.name, i);
+        b.d_plane[i] = c.grad_planes[i];
+        b.d_line[i] = c.grad_lines[i];
+        max_rank = std::max(max_rank, c.rank[i]);
+        max_chunks = std::max(max_chunks, div_up<uint32_t>(f.Dn[i], kVmZChunk));
+    }
+    const uint32_t max_tiles = vm_max_tiles(c.resolution);
+    S3D_REQUIRE(max_rank <= 64, "%s: rank %u > 64 not supported", c.name, max_rank);
+    S3D_REQUIRE(c.n_bounds > max_tiles && c.n_bounds > max_chunks, "%s: `start` needs more than %u columns", c.name, max_tiles);
+    b.g = c.grad;
+    b.gm = c.gm;
+    b.perm = c.perm;
+    b.start = c.start;
+    b.n_bounds = c.n_bounds;
+    b.basis = c.basis;
+    b.g_out = c.grad_out;
+    b.d_basis = c.grad_basis;
+    b.Cb = c.basis_rows;
+    b.bound = c.bound_words;
+    b.found_inf = c.found_inf;
+    b.line_t = c.line_scratch;
+    for (uint32_t i = 0, off = 0; i < 3; off += f.rank[i] * f.Dn[i], i++) b.line_t_off[i] = off;
+    uint32_t* stage_flags;
+    const uint32_t n_stage_flags = vm_stage_arm(b, c.N, c.rank, c.resolution, c.stage, c.stage_bytes, stage_flags);
+    // the gradient's bound: fp32 words four to a thread, fp16 rows (kVmBasisPad columns) eight to a thread
+    const size_t n_g = c.basis ? 0 : c.reduce ? (size_t)c.N : (size_t)c.N * b.rows;
+    const size_t n_g16 = c.basis ? (size_t)c.N * kVmBasisPad : 0;
+    hipLaunchKernelGGL(k_vm_bound, dim3(std::min<uint32_t>(stream_grid((c.basis ? n_g16 / 8 : n_g / 4) + 1, 256), 512u)), dim3(256), 0, c.stream,
+                       c.grad, n_g, c.grad_out, n_g16, f, c.basis, c.basis_rows, b.rows, c.bound_words, c.line_scratch, stage_flags,
+                       n_stage_flags, c.N, c.n_valid);
+    const uint32_t lane_rank = c.basis ? 64u : max_rank;  // (the BASIS kernel: 64 lanes per point whatever the rank)
+    if (int rc = lane_rank <= 16 ? vm_backward_passes<16>(c, f, b, lane_rank) : vm_backward_passes<64>(c, f, b, lane_rank)) return rc;
+    if (b.stage_line)
+        hipLaunchKernelGGL(k_vm_flush_reduce, dim3(div_up<uint32_t>(b.stage_tiles, kVmReduceTiles) + kVmLineParts * max_chunks, 3), dim3(256), 0, c.stream, f, b);
+    return check_launch(c.name);
+}
+
 S3D_EXPORT int s3d_vm_features_backward(const float* x, uint32_t N, const float* const* planes, const float* const* lines,
                                         const uint32_t* rank, const uint32_t* resolution, int reduce, const float* grad,
                                         const int32_t* perm, const int32_t* start, uint32_t n_bounds, float* gm,
@@ -1771,59 +1861,11 @@ S3D_EXPORT int s3d_vm_features_backward(const float* x, uint32_t N, const float*
     S3D_REQUIRE(x && planes && lines && rank && resolution && grad && perm && start && gm && grad_planes && grad_lines && bound_words &&
                 line_scratch, "vm_features_backward: null pointer");
     VmFactors f;
-    VmBackward b;
-    if (int rc = fill_factors(f, planes, lines, rank, resolution, b.rows)) return rc;
-    if (planes_t && planes_t[0] && planes_t[1] && planes_t[2] &&
-        !((reinterpret_cast<uintptr_t>(planes_t[0]) | reinterpret_cast<uintptr_t>(planes_t[1]) | reinterpret_cast<uintptr_t>(planes_t[2])) & 15u))
-        for (uint32_t i = 0; i < 3; i++) f.plane_t[i] = planes_t[i];  // (the tile loads of the plane passes; any rank)
-    uint32_t max_rank = 0, max_tiles = 0, max_chunks = 0;
-    for (uint32_t i = 0; i < 3; i++) {
-        S3D_REQUIRE(grad_planes[i] && grad_lines[i], "vm_features_backward: null gradient buffer %u", i);
-        b.d_plane[i] = grad_planes[i];
-        b.d_line[i] = grad_lines[i];
-        max_rank = rank[i] > max_rank ? rank[i] : max_rank;
-        const uint32_t tiles = div_up<uint32_t>(f.W[i], kVmTile) * div_up<uint32_t>(f.H[i], kVmTile);
-        max_tiles = tiles > max_tiles ? tiles : max_tiles;
-        const uint32_t chunks = div_up<uint32_t>(f.Dn[i], kVmZChunk);
-        max_chunks = chunks > max_chunks ? chunks : max_chunks;
-    }
-    S3D_REQUIRE(max_rank <= 64, "vm_features_backward: rank %u > 64 not supported", max_rank);
-    S3D_REQUIRE(n_bounds > max_tiles && n_bounds > max_chunks, "vm_features_backward: `start` needs more than %u columns", max_tiles);
-    b.g = grad;
-    b.gm = gm;
-    b.perm = perm;
-    b.start = start;
-    b.n_bounds = n_bounds;
-    b.basis = nullptr; b.g_out = nullptr; b.d_basis = nullptr; b.Cb = 0;
-    b.bound = bound_words;
-    b.found_inf = found_inf;
-    b.line_t = line_scratch;
-    for (uint32_t i = 0, off = 0; i < 3; off += f.rank[i] * f.Dn[i], i++) b.line_t_off[i] = off;
-    hipStream_t st = as_stream(stream);
-    dim3 gp, gl;
-    size_t smem_p, smem_l;
-    vm_backward_geometry(b, N, max_rank, false, gp, gl, smem_p, smem_l);
-    const dim3 block(kVmBwdThreads);
-    const size_t n_g = reduce ? (size_t)N : (size_t)N * b.rows;
-    uint32_t* stage_flags;
-    const uint32_t n_stage_flags = vm_stage_arm(b, N, rank, resolution, stage, stage_bytes, stage_flags);
-    hipLaunchKernelGGL(k_vm_bound, dim3(std::min<uint32_t>(stream_grid(n_g / 4 + 1, 256), 512u)), dim3(256), 0, st, grad, n_g, (const _Float16*)nullptr, (size_t)0, f,
-                       (const _Float16*)nullptr, 0u, b.rows, bound_words, line_scratch, stage_flags, n_stage_flags, N, n_valid);
-    bool mm;
-    if (int rc = reduce ? launch_plane_mm<0>(x, N, f, b, st, mm) : launch_plane_mm<1>(x, N, f, b, st, mm)) return rc;
-    if (max_rank <= 16) {
-        if (mm) {}
-        else if (reduce) hipLaunchKernelGGL((k_vm_plane_backward<16, true>), gp, block, smem_p, st, x, N, f, b);
-        else hipLaunchKernelGGL((k_vm_plane_backward<16, false>), gp, block, smem_p, st, x, N, f, b);
-        if (!launch_line_mm(x, N, f, b, st)) hipLaunchKernelGGL((k_vm_line_backward<16>), gl, block, smem_l, st, x, N, f, b);
-    } else {
-        if (mm) {}
-        else if (reduce) hipLaunchKernelGGL((k_vm_plane_backward<64, true>), gp, block, smem_p, st, x, N, f, b);
-        else hipLaunchKernelGGL((k_vm_plane_backward<64, false>), gp, block, smem_p, st, x, N, f, b);
-        if (!launch_line_mm(x, N, f, b, st)) hipLaunchKernelGGL((k_vm_line_backward<64>), gl, block, smem_l, st, x, N, f, b);
-    }
-    if (b.stage_line) hipLaunchKernelGGL(k_vm_flush_reduce, dim3(div_up<uint32_t>(b.stage_tiles, kVmReduceTiles) + kVmLineParts * max_chunks, 3), dim3(256), 0, st, f, b);
-    return check_launch("vm_features_backward");
+    uint32_t rows;
+    if (int rc = fill_factors(f, planes, lines, rank, resolution, rows)) return rc;
+    const VmBwdCall c{"vm_features_backward", reduce != 0, grad, nullptr, nullptr, 0, nullptr, x, N, n_bounds, rank, resolution, perm, start,
+                      n_valid, gm, line_scratch, found_inf, grad_planes, grad_lines, planes_t, bound_words, stage, stage_bytes, as_stream(stream)};
+    return vm_factor_backward(c, f, rows);
 }
 
 S3D_EXPORT int s3d_vm_color_forward(const float* x, uint32_t N, const float* const* planes, const float* const* lines,
@@ -1854,55 +1896,14 @@ S3D_EXPORT int s3d_vm_color_backward(const float* x, uint32_t N, const float* co
     S3D_REQUIRE(x && planes && lines && rank && resolution && basis && grad_out && perm && start && gm && grad_planes && grad_lines &&
                 grad_basis && bound_words && line_scratch, "vm_color_backward: null pointer");
     VmFactors f;
-    VmBackward b;
-    if (int rc = fill_factors(f, planes, lines, rank, resolution, b.rows)) return rc;
+    uint32_t rows;
+    if (int rc = fill_factors(f, planes, lines, rank, resolution, rows)) return rc;
     S3D_REQUIRE(basis_rows >= 1 && basis_rows <= kVmBasisPad, "vm_color_backward: basis_mat with %u outputs (1 .. %u supported)",
                 basis_rows, kVmBasisPad);
-    if (planes_t && planes_t[0] && planes_t[1] && planes_t[2] &&
-        !((reinterpret_cast<uintptr_t>(planes_t[0]) | reinterpret_cast<uintptr_t>(planes_t[1]) | reinterpret_cast<uintptr_t>(planes_t[2])) & 15u))
-        for (uint32_t i = 0; i < 3; i++) f.plane_t[i] = planes_t[i];  // (the tile loads of the plane passes; any rank)
-    uint32_t max_rank = 0, max_tiles = 0, max_chunks = 0;
-    for (uint32_t i = 0; i < 3; i++) {
-        S3D_REQUIRE(grad_planes[i] && grad_lines[i], "vm_color_backward: null gradient buffer %u", i);
-        b.d_plane[i] = grad_planes[i];
-        b.d_line[i] = grad_lines[i];
-        max_rank = rank[i] > max_rank ? rank[i] : max_rank;
-        const uint32_t tiles = div_up<uint32_t>(f.W[i], kVmTile) * div_up<uint32_t>(f.H[i], kVmTile);
-        max_tiles = tiles > max_tiles ? tiles : max_tiles;
-        const uint32_t chunks = div_up<uint32_t>(f.Dn[i], kVmZChunk);
-        max_chunks = chunks > max_chunks ? chunks : max_chunks;
-    }
-    S3D_REQUIRE(max_rank <= 64, "vm_color_backward: rank %u > 64 not supported", max_rank);
-    S3D_REQUIRE(n_bounds > max_tiles && n_bounds > max_chunks, "vm_color_backward: `start` needs more than %u columns", max_tiles);
-    b.g = nullptr;
-    b.gm = gm;
-    b.perm = perm;
-    b.start = start;
-    b.n_bounds = n_bounds;
-    b.basis = (const _Float16*)basis;
-    b.g_out = (const _Float16*)grad_out;
-    b.d_basis = grad_basis;
-    b.Cb = basis_rows;
-    b.bound = bound_words;
-    b.found_inf = found_inf;
-    b.line_t = line_scratch;
-    for (uint32_t i = 0, off = 0; i < 3; off += f.rank[i] * f.Dn[i], i++) b.line_t_off[i] = off;
-    hipStream_t st = as_stream(stream);
-    dim3 gp, gl;
-    size_t smem_p, smem_l;
-    vm_backward_geometry(b, N, 64, true, gp, gl, smem_p, smem_l);  // (the BASIS kernel: 64 lanes per point whatever the rank)
-    const dim3 block(kVmBwdThreads);
-    const size_t n_g16 = (size_t)N * kVmBasisPad;
-    uint32_t* stage_flags;
-    const uint32_t n_stage_flags = vm_stage_arm(b, N, rank, resolution, stage, stage_bytes, stage_flags);
-    hipLaunchKernelGGL(k_vm_bound, dim3(std::min<uint32_t>(stream_grid(n_g16 / 8 + 1, 256), 512u)), dim3(256), 0, st, (const float*)nullptr, (size_t)0,
-                       (const _Float16*)grad_out, n_g16, f, (const _Float16*)basis, basis_rows, b.rows, bound_words, line_scratch, stage_flags, n_stage_flags, N, n_valid);
-    bool mm;
-    if (int rc = launch_plane_mm<2>(x, N, f, b, st, mm)) return rc;
-    if (!mm) hipLaunchKernelGGL((k_vm_plane_backward<64, false, true>), gp, block, smem_p, st, x, N, f, b);
-    if (!launch_line_mm(x, N, f, b, st)) hipLaunchKernelGGL((k_vm_line_backward<64>), gl, block, smem_l, st, x, N, f, b);
-    if (b.stage_line) hipLaunchKernelGGL(k_vm_flush_reduce, dim3(div_up<uint32_t>(b.stage_tiles, kVmReduceTiles) + kVmLineParts * max_chunks, 3), dim3(256), 0, st, f, b);
-    return check_launch("vm_color_backward");
+    const VmBwdCall c{"vm_color_backward", false, nullptr, (const _Float16*)basis, (const _Float16*)grad_out, basis_rows, grad_basis, x, N, n_bounds,
+                      rank, resolution, perm, start, n_valid, gm, line_scratch, found_inf, grad_planes, grad_lines, planes_t, bound_words, stage,
+                      stage_bytes, as_stream(stream)};
+    return vm_factor_backward(c, f, rows);
 }
 
 S3D_EXPORT int s3d_vm_transpose_factors(const float* const* planes, const float* const* lines, const uint32_t* rank,

@@ -1313,22 +1313,26 @@ class VmBackend:
     """csrc/tensorf.hip — TensoRF vector-matrix features (tensoRF/network.py:112-153 of the reference)"""
 
     @staticmethod
+    def _factors(planes, lines, resolution, what="vm features"):
+        """a factor set as the C calls take it: (planes pointers, lines pointers, rank, res, sum of the ranks).  The factors are
+        fp32 contiguous GPU tensors (`what` names the caller in the message); `lines` is None where only the geometry is read."""
+        for t in list(planes) + list(lines or ()):
+            _need(t, torch.float32, "factor")
+            if not t.is_cuda or not t.is_contiguous():
+                raise RuntimeError(f"{what}: factors must be contiguous GPU tensors")
+        ptr3, u3 = C.c_void_p * 3, C.c_uint32 * 3
+        ranks = [int(t.shape[1]) for t in planes]
+        return (ptr3(*[t.data_ptr() for t in planes]), None if lines is None else ptr3(*[t.data_ptr() for t in lines]),
+                u3(*ranks), u3(*[int(r) for r in resolution]), sum(ranks))
+
+    @staticmethod
     def features_forward(x, planes, lines, resolution, reduce, out, n_valid=None, shadows=None):
         """x [N,3] fp32; planes[i] [1,R_i,H,W] / lines[i] [1,R_i,D,1] fp32 (the reference's parameter shapes);
         out [N] (reduce) or [sum R_i, N]"""
         _need(x, torch.float32, "x"); _need(out, torch.float32, "out")
-        for t in list(planes) + list(lines):
-            _need(t, torch.float32, "factor")
-            if not t.is_cuda or not t.is_contiguous():
-                raise RuntimeError("vm features: factors must be contiguous GPU tensors")
+        pl, ln, rank, res, _ = VmBackend._factors(planes, lines, resolution)
         if not x.is_contiguous() or x.shape[-1] != 3:
             raise RuntimeError("vm features: x must be contiguous [N,3]")
-        ptr3 = C.c_void_p * 3
-        u3 = C.c_uint32 * 3
-        pl = ptr3(*[t.data_ptr() for t in planes])
-        ln = ptr3(*[t.data_ptr() for t in lines])
-        rank = u3(*[int(t.shape[1]) for t in planes])
-        res = u3(*[int(r) for r in resolution])
         _check(lib().s3d_vm_features_forward(_p(x), _u(x.shape[0]), pl, ln, rank, res, C.c_int(int(bool(reduce))), _p(out),
                                              *_shadow2(shadows), _nv(n_valid), _stream()), "vm_features_forward")
 
@@ -1392,9 +1396,7 @@ class VmBackend:
         """(perm [6,N] i32, start [6,n_bounds] i32, n_bounds): the points sorted by plane tile / line chunk, as the backward
         kernels want them.  Depends on x and the resolution only — the density and the colour factors of one network share it."""
         N, dev = x.shape[0], x.device
-        u3 = C.c_uint32 * 3
-        rank = u3(*[int(t.shape[1]) for t in planes])
-        res = u3(*[int(r) for r in resolution])
+        _, _, rank, res, _ = VmBackend._factors(planes, None, resolution)
         n_bounds = int(lib().s3d_vm_backward_max_bins(res)) + 2
         if VmBackend.native_bins:
             perm = torch.empty(6, N, dtype=torch.int32, device=dev)
@@ -1423,45 +1425,42 @@ class VmBackend:
     def transpose_factors(planes, lines, resolution):
         """rank-fastest shadows of a factor set (s3d_vm_transpose_factors): ([H, W, R_i] x 3, [Dn, R_i] x 3) fp32, from the CURRENT
         values of the parameters — the caller takes them afresh whenever the parameters may have changed"""
-        for t in list(planes) + list(lines):
-            _need(t, torch.float32, "factor")
-            if not t.is_cuda or not t.is_contiguous():
-                raise RuntimeError("vm transpose: factors must be contiguous GPU tensors")
-        ptr3, u3 = C.c_void_p * 3, C.c_uint32 * 3
+        pl, ln, rank, res, _ = VmBackend._factors(planes, lines, resolution, "vm transpose")
+        ptr3 = C.c_void_p * 3
         pt = [torch.empty(t.shape[2], t.shape[3], t.shape[1], dtype=torch.float32, device=t.device) for t in planes]
         lt = [torch.empty(t.shape[2], t.shape[1], dtype=torch.float32, device=t.device) for t in lines]
-        _check(lib().s3d_vm_transpose_factors(ptr3(*[t.data_ptr() for t in planes]), ptr3(*[t.data_ptr() for t in lines]),
-                                              u3(*[int(t.shape[1]) for t in planes]), u3(*[int(r) for r in resolution]),
-                                              ptr3(*[t.data_ptr() for t in pt]), ptr3(*[t.data_ptr() for t in lt]), _stream()),
-               "vm_transpose_factors")
+        _check(lib().s3d_vm_transpose_factors(pl, ln, rank, res, ptr3(*[t.data_ptr() for t in pt]), ptr3(*[t.data_ptr() for t in lt]),
+                                              _stream()), "vm_transpose_factors")
         return pt, lt
 
     @staticmethod
-    def _stage(N, rank, res, dev):
-        """staging rows of the factor backward's flushes (s3d_vm_backward_stage_bytes; uint8, no initialisation)"""
-        return torch.empty(int(lib().s3d_vm_backward_stage_bytes(_u(N), rank, res)), dtype=torch.uint8, device=dev)
+    def _backward_buffers(x, planes, lines, resolution, rank, res, rows, bins, n_valid, extra=()):
+        """what a factor backward allocates: (perm, start, n_bounds, gm, gs, bound_words, line_scratch, stage).  `bins`: a
+        backward_bins() result or None (taken here); gs: zeroed gradients shaped like planes + lines + extra, in one buffer with
+        the 4 bound words; stage: staging rows of the flushes (s3d_vm_backward_stage_bytes; uint8, no initialisation).
+        The callers keep every one of them in a named local until the call has returned: temporaries created inside the
+        argument list would be freed one by one and handed the SAME block."""
+        N, dev = x.shape[0], x.device
+        perm, start, n_bounds = bins if bins is not None else VmBackend.backward_bins(x, planes, resolution, n_valid)
+        gm = torch.empty(N, rows, dtype=torch.float32, device=dev)  # (written by the plane pass for every point the line pass reads)
+        gs, bound_words = _zeros_like_many(list(planes) + list(lines) + list(extra), 4)
+        line_scratch = torch.empty(sum(t.numel() for t in lines), dtype=torch.float32, device=dev)
+        stage = torch.empty(int(lib().s3d_vm_backward_stage_bytes(_u(N), rank, res)), dtype=torch.uint8, device=dev)
+        return perm, start, n_bounds, gm, gs, bound_words, line_scratch, stage
 
     @staticmethod
     def features_backward(x, planes, lines, resolution, reduce, grad, bins=None, found_inf=None, n_valid=None, shadows=None):
         """gradients of features_forward w.r.t. planes / lines (lists shaped like the factors).  grad: [N] (reduce) or
         [N, sum R_i] point-major.  `bins`: a backward_bins() result for the same x / resolution."""
         _need(x, torch.float32, "x"); _need(grad, torch.float32, "grad")
-        N, dev = x.shape[0], x.device
-        ptr3, u3 = C.c_void_p * 3, C.c_uint32 * 3
-        rank = u3(*[int(t.shape[1]) for t in planes])
-        res = u3(*[int(r) for r in resolution])
-        rows = sum(int(t.shape[1]) for t in planes)
+        N, ptr3 = x.shape[0], C.c_void_p * 3
+        pl, ln, rank, res, rows = VmBackend._factors(planes, lines, resolution)
         if not grad.is_contiguous() or grad.numel() != (N if reduce else N * rows):
             raise RuntimeError("vm features backward: grad must be contiguous [N] / [N, sum rank]")
-        perm, start, n_bounds = bins if bins is not None else VmBackend.backward_bins(x, planes, resolution, n_valid)
-        gm = torch.empty(N, rows, dtype=torch.float32, device=dev)  # (written by the plane pass for every point the line pass reads)
-        # (named locals: temporaries created inside the argument list would be freed one by one and handed the SAME block)
-        gs, bound_words = _zeros_like_many(list(planes) + list(lines), 4)
+        perm, start, n_bounds, gm, gs, bound_words, line_scratch, stage = VmBackend._backward_buffers(
+            x, planes, lines, resolution, rank, res, rows, bins, n_valid)
         g_planes, g_lines = gs[:3], gs[3:]
-        line_scratch = torch.empty(sum(t.numel() for t in lines), dtype=torch.float32, device=dev)
-        stage = VmBackend._stage(N, rank, res, dev)
-        _check(lib().s3d_vm_features_backward(_p(x), _u(N), ptr3(*[t.data_ptr() for t in planes]),
-                                              ptr3(*[t.data_ptr() for t in lines]), rank, res, C.c_int(int(bool(reduce))),
+        _check(lib().s3d_vm_features_backward(_p(x), _u(N), pl, ln, rank, res, C.c_int(int(bool(reduce))),
                                               _p(grad), _p(perm), _p(start), _u(n_bounds), _p(gm),
                                               ptr3(*[t.data_ptr() for t in g_planes]), ptr3(*[t.data_ptr() for t in g_lines]),
                                               _p(bound_words), _p(line_scratch), _p(stage), C.c_size_t(stage.numel()), _p(found_inf),
@@ -1472,28 +1471,20 @@ class VmBackend:
     def color_forward(x, planes, lines, resolution, basis, out, n_valid=None, shadows=None):
         """colour products with basis_mat applied in the kernel: basis fp16 [Cb, sum R_i] (the Linear's weight), out fp16 [N, Cb]"""
         _need(x, torch.float32, "x"); _need(basis, torch.float16, "basis"); _need(out, torch.float16, "out")
-        for t in list(planes) + list(lines):
-            _need(t, torch.float32, "factor")
-            if not t.is_cuda or not t.is_contiguous():
-                raise RuntimeError("vm features: factors must be contiguous GPU tensors")
-        rows = sum(int(t.shape[1]) for t in planes)
+        pl, ln, rank, res, rows = VmBackend._factors(planes, lines, resolution)
         if not x.is_contiguous() or x.shape[-1] != 3 or not basis.is_contiguous() or basis.shape[1] != rows:
             raise RuntimeError("vm color: x must be contiguous [N,3], basis contiguous [Cb, sum rank]")
         if not out.is_contiguous() or out.numel() != x.shape[0] * basis.shape[0]:
             raise RuntimeError("vm color: out must be contiguous [N, Cb]")
-        ptr3, u3 = C.c_void_p * 3, C.c_uint32 * 3
-        _check(lib().s3d_vm_color_forward(_p(x), _u(x.shape[0]), ptr3(*[t.data_ptr() for t in planes]),
-                                          ptr3(*[t.data_ptr() for t in lines]), u3(*[int(t.shape[1]) for t in planes]),
-                                          u3(*[int(r) for r in resolution]), _p(basis), _u(basis.shape[0]), _p(out),
+        _check(lib().s3d_vm_color_forward(_p(x), _u(x.shape[0]), pl, ln, rank, res, _p(basis), _u(basis.shape[0]), _p(out),
                                           *_shadow2(shadows), _nv(n_valid), _stream()), "vm_color_forward")
 
     @staticmethod
     def color_backward(x, planes, lines, resolution, basis, grad_out, bins=None, found_inf=None, n_valid=None, shadows=None):
         """gradients of color_forward w.r.t. planes / lines / basis from grad_out fp16 [N, Cb]: (g_planes, g_lines, g_basis fp32)"""
         _need(x, torch.float32, "x"); _need(basis, torch.float16, "basis"); _need(grad_out, torch.float16, "grad_out")
-        N, dev = x.shape[0], x.device
-        ptr3, u3 = C.c_void_p * 3, C.c_uint32 * 3
-        rows = sum(int(t.shape[1]) for t in planes)
+        N, ptr3 = x.shape[0], C.c_void_p * 3
+        pl, ln, rank, res, rows = VmBackend._factors(planes, lines, resolution)
         if grad_out.shape != (N, basis.shape[0]) or not basis.is_contiguous() or basis.shape[1] != rows or basis.shape[0] > 32:
             raise RuntimeError("vm color backward: grad_out must be [N, Cb <= 32], basis contiguous [Cb, sum rank]")
         # the kernel reads a point's gradients as four 16-byte words: rows padded to 32 columns (a [:, :Cb] view of a zero-padded
@@ -1504,15 +1495,10 @@ class VmBackend:
             grad_out = base
         else:
             grad_out = torch.nn.functional.pad(grad_out, (0, 32 - basis.shape[0])).contiguous()
-        perm, start, n_bounds = bins if bins is not None else VmBackend.backward_bins(x, planes, resolution, n_valid)
-        gm = torch.empty(N, rows, dtype=torch.float32, device=dev)  # (written by the plane pass for every point the line pass reads)
-        gs, bound_words = _zeros_like_many(list(planes) + list(lines) + [basis], 4)
+        perm, start, n_bounds, gm, gs, bound_words, line_scratch, stage = VmBackend._backward_buffers(
+            x, planes, lines, resolution, rank, res, rows, bins, n_valid, extra=[basis])
         g_planes, g_lines, g_basis = gs[:3], gs[3:6], gs[6]
-        line_scratch = torch.empty(sum(t.numel() for t in lines), dtype=torch.float32, device=dev)
-        rank, res = u3(*[int(t.shape[1]) for t in planes]), u3(*[int(r) for r in resolution])
-        stage = VmBackend._stage(N, rank, res, dev)
-        _check(lib().s3d_vm_color_backward(_p(x), _u(N), ptr3(*[t.data_ptr() for t in planes]),
-                                           ptr3(*[t.data_ptr() for t in lines]), rank, res, _p(basis), _u(basis.shape[0]), _p(grad_out),
+        _check(lib().s3d_vm_color_backward(_p(x), _u(N), pl, ln, rank, res, _p(basis), _u(basis.shape[0]), _p(grad_out),
                                            _p(perm), _p(start), _u(n_bounds), _p(gm), ptr3(*[t.data_ptr() for t in g_planes]),
                                            ptr3(*[t.data_ptr() for t in g_lines]), _p(g_basis),
                                            _p(bound_words), _p(line_scratch), _p(stage), C.c_size_t(stage.numel()), _p(found_inf),
