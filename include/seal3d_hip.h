@@ -552,6 +552,24 @@ int s3d_background_backward(const float* grad_rgb, const float* rgb, const float
                             const int32_t* offsets, uint32_t table_rows, uint32_t N, float S, uint32_t H, int dtype,
                             const float* w0, const float* w1, void* grad_table, float* grad_w0, float* grad_w1,
                             float* found_inf, void* workspace, size_t workspace_bytes, s3d_stream_t stream);
+/* Build extension — the TensoRF background model, tensoRF/network.py:201-218 `background(x, d)` of the reference (parameters
+ * built at :69-96): rgb [N,3] = sigmoid(W1 relu(W0 [freq_2(dirs) | grid_sample(bg_mat, sph)])).  plane = `bg_mat` [R,H,W] fp32
+ * with R = 8, H, W >= 2 (sph[:,0] runs along W, sph[:,1] along H), sampled as F.grid_sample does (bilinear, zeros padding,
+ * align_corners=True; a coordinate outside [-1,1] or not finite contributes no corner); freq_2 = the 15 columns of
+ * s3d_freq_encode_forward (D = 3, degree 2); W0 [64,23], W1 [3,64] fp32, rounded to fp16 as they are read.  One launch, the
+ * arithmetic of s3d_background_forward's MLP.  features [N,R] fp32 (optional): the plane samples, bit for bit F.grid_sample's. */
+int s3d_vm_background_forward(const float* sph, const float* dirs, const float* plane, uint32_t R, uint32_t H, uint32_t W,
+                              const float* w0, const float* w1, uint32_t N, float* rgb, float* features, s3d_stream_t stream);
+/* Backward of s3d_vm_background_forward from grad_rgb [N,3] (fp32) and the forward's rgb: the hidden layer is recomputed, the
+ * sample gradient (fp16-rounded) times each in-range corner's weight is ADDED into grad_plane [R,H,W] fp32 with one atomic per
+ * corner and rank (NULL: a frozen plane, no scatter), grad_w0 [64,23] / grad_w1 [3,64] (fp32) are overwritten.  Two launches, as
+ * s3d_background_backward: per-wave partials in `workspace` (s3d_vm_background_backward_workspace_size(N) bytes), summed in wave
+ * order.  found_inf (optional): set to 1 when a weight gradient or an entry of grad_plane is not finite. */
+size_t s3d_vm_background_backward_workspace_size(uint32_t N);
+int s3d_vm_background_backward(const float* grad_rgb, const float* rgb, const float* sph, const float* dirs, const float* plane,
+                               uint32_t R, uint32_t H, uint32_t W, const float* w0, const float* w1, uint32_t N,
+                               float* grad_plane, float* grad_w0, float* grad_w1, float* found_inf, void* workspace,
+                               size_t workspace_bytes, s3d_stream_t stream);
 /* Build extension — Seal-3D's local-pretraining loss on one point chunk (SealNeRF/trainer.py:455-469: L1Loss(sigma) +
  * L1Loss(colour), means): loss = sum|sigma - gt_sigma| / n_total + sum|color - gt_color| / (3 n_total); n_total >= n is the
  * size of the whole chunk when the call sees one rank's shard of it; sigma / color (and the gradients) hold n_rows >= n rows,

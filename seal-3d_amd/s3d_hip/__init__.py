@@ -49,6 +49,7 @@ EXPORTS = [
     "s3d_vm_features_backward", "s3d_vm_color_forward", "s3d_vm_color_backward",
     "s3d_composite_rays_train_loss_bg", "s3d_bg_targets_rays",
     "s3d_background_forward", "s3d_background_backward_workspace_size", "s3d_background_backward",
+    "s3d_vm_background_forward", "s3d_vm_background_backward_workspace_size", "s3d_vm_background_backward",
     "s3d_sample_train_rays", "s3d_error_map_update", "s3d_sample_train_rays_rgba", "s3d_rgba_targets",
 ]
 
@@ -79,7 +80,8 @@ def lib():
                      "s3d_ffmlp_backward_workspace_size", "s3d_grid_encode_backward_workspace_size",
                      "s3d_grid_encode_backward_control_size", "s3d_l1_pair_workspace_size",
                      "s3d_sweep_update_workspace_size", "s3d_vm_backward_bins_workspace_size", "s3d_vm_backward_stage_bytes",
-                     "s3d_weighted_abs_sum_workspace_size", "s3d_background_backward_workspace_size"):
+                     "s3d_weighted_abs_sum_workspace_size", "s3d_background_backward_workspace_size",
+                     "s3d_vm_background_backward_workspace_size"):
             getattr(l, name).restype = C.c_size_t
         l.s3d_vm_backward_max_bins.restype = C.c_uint32
         l.s3d_grid_level_scales.restype = None
@@ -1335,6 +1337,45 @@ class VmBackend:
             raise RuntimeError("vm features: x must be contiguous [N,3]")
         _check(lib().s3d_vm_features_forward(_p(x), _u(x.shape[0]), pl, ln, rank, res, C.c_int(int(bool(reduce))), _p(out),
                                              *_shadow2(shadows), _nv(n_valid), _stream()), "vm_features_forward")
+
+    @staticmethod
+    def _background_args(sph, dirs, plane, w0, w1, rgb, what):
+        """shape / dtype checks shared by background_forward and background_backward; returns (N, R, H, W)"""
+        for t, n in ((sph, "sph"), (dirs, "dirs"), (plane, "plane"), (w0, "w0"), (w1, "w1"), (rgb, "rgb")):
+            _need(t, torch.float32, n)
+        N = sph.shape[0]
+        if (sph.shape != (N, 2) or dirs.shape != (N, 3) or rgb.shape != (N, 3) or plane.dim() != 4 or plane.shape[0] != 1
+                or plane.shape[1] != 8 or min(plane.shape[2:]) < 2 or w0.shape != (64, 23) or w1.shape != (3, 64)):
+            raise RuntimeError(f"{what}: sph [N,2], dirs / rgb [N,3], plane [1,8,H,W] with H, W >= 2, w0 [64,23], w1 [3,64]")
+        return N, 8, int(plane.shape[2]), int(plane.shape[3])
+
+    @staticmethod
+    def background_forward(sph, dirs, plane, w0, w1, rgb, features=None):
+        """the TensoRF background model (seal3d_hip.h: s3d_vm_background_forward): sph [N,2], dirs [N,3], plane `bg_mat` [1,8,H,W],
+        w0 [64,23] / w1 [3,64] fp32 (read as fp16) -> rgb [N,3] fp32 (+ the plane samples [N,8] fp32)"""
+        N, R, H, W = VmBackend._background_args(sph, dirs, plane, w0, w1, rgb, "vm background_forward")
+        if features is not None and (features.dtype != torch.float32 or features.shape != (N, R)):
+            raise RuntimeError("vm background_forward: features [N,8] fp32")
+        _check(lib().s3d_vm_background_forward(_p(sph), _p(dirs), _p(plane), _u(R), _u(H), _u(W), _p(w0), _p(w1), _u(N), _p(rgb),
+                                               _p(features), _stream()), "vm_background_forward")
+
+    @staticmethod
+    def background_backward(grad_rgb, rgb, sph, dirs, plane, w0, w1, grad_plane, grad_w0, grad_w1, found_inf=None):
+        """backward of background_forward: ADDS the plane gradient into grad_plane (fp32, the plane's shape; None: no plane
+        gradient), overwrites grad_w0 [64,23] / grad_w1 [3,64] (fp32); found_inf (optional fp32 [1]) raised for a non-finite gradient"""
+        N, R, H, W = VmBackend._background_args(sph, dirs, plane, w0, w1, rgb, "vm background_backward")
+        for t, n in ((grad_rgb, "grad_rgb"), (grad_w0, "grad_w0"), (grad_w1, "grad_w1")):
+            _need(t, torch.float32, n)
+        if (grad_rgb.shape != (N, 3) or grad_w0.shape != (64, 23) or grad_w1.shape != (3, 64)
+                or (grad_plane is not None and (grad_plane.shape != plane.shape or grad_plane.dtype != torch.float32))):
+            raise RuntimeError("vm background_backward: grad_rgb [N,3], grad_plane like plane, grad_w0 [64,23], grad_w1 [3,64]")
+        if found_inf is not None:
+            _need(found_inf, torch.float32, "found_inf")
+        nb = int(lib().s3d_vm_background_backward_workspace_size(_u(N)))
+        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=sph.device)
+        _check(lib().s3d_vm_background_backward(_p(grad_rgb), _p(rgb), _p(sph), _p(dirs), _p(plane), _u(R), _u(H), _u(W), _p(w0), _p(w1),
+                                                _u(N), _p(grad_plane), _p(grad_w0), _p(grad_w1), _p(found_inf), _p(ws),
+                                                C.c_size_t(nb), _stream()), "vm_background_backward")
 
     @staticmethod
     def aabb_normalize(x, aabb, out):

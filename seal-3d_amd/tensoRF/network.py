@@ -10,7 +10,11 @@ On the GPU the twelve grid_sample calls + stack / cat / mul / sum of `get_sigma_
 per call (`s3d_vm_features_forward`, csrc/tensorf.hip), and so do their parameter gradients
 (`s3d_vm_features_backward`: points binned by plane tile / line chunk, LDS accumulation, instead of the ~2.8e8 global
 fp32 atomics per step grid_sample's backward issues at the Lego sample count).  A gradient w.r.t. the coordinates (not
-needed by any trainer of the reference) falls back to the grid_sample sequence under autograd."""
+needed by any trainer of the reference) falls back to the grid_sample sequence under autograd.
+
+The background model (`bg_radius > 0`, tensoRF/network.py:69-96, :201-218: a dense plane `bg_mat` sampled at the ray's sphere
+coordinates + FreqEncoder(3, deg 2) -> 23 -> 64 -> 3) runs as one forward and two backward launches under fp16 autocast
+(`s3d_vm_background_forward` / `_backward`, csrc/background.hip)."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -143,6 +147,41 @@ class _VmColorBasis(torch.autograd.Function):
         return (None, None, gw) + tuple(gp) + tuple(gl)
 
 
+class _VmBackground(torch.autograd.Function):
+    """`background(x, d)` of tensoRF/network.py:201-218 (reference) on the fused kernels (csrc/background.hip): plane sample,
+    frequency encoding, 23 -> 64 -> 3 MLP and sigmoid as ONE forward launch; backward = one launch (plane gradient by fp32
+    atomics + per-wave weight-gradient partials, the hidden layer recomputed) + one small reduce.  The plane gradient goes through
+    autograd in fp32 like the other factors of this backbone."""
+
+    @staticmethod
+    def forward(ctx, sph, dirs, net, plane, w0, w1):
+        sph, dirs = sph.float().contiguous(), dirs.float().contiguous()
+        rgb = torch.empty(sph.shape[0], 3, dtype=torch.float32, device=sph.device)
+        s3d_hip.VmBackend.background_forward(sph, dirs, plane.detach().contiguous(), w0.detach().contiguous(),
+                                             w1.detach().contiguous(), rgb)
+        ctx.save_for_backward(sph, dirs, plane, w0, w1, rgb)
+        ctx.net = net
+        return rgb
+
+    @staticmethod
+    def backward(ctx, g_rgb):
+        sph, dirs, plane, w0, w1, rgb = ctx.saved_tensors
+        want_plane = ctx.needs_input_grad[3]
+        grad_plane = torch.zeros_like(plane, memory_format=torch.contiguous_format) if want_plane else None  # (frozen plane: no scatter)
+        gw0, gw1 = torch.empty_like(w0, memory_format=torch.contiguous_format), torch.empty_like(w1, memory_format=torch.contiguous_format)
+        # (the trainer's scaler flag: the reduce launch raises it itself, and the scaler's pass skips these three gradients)
+        net, flag = ctx.net, getattr(ctx.net, "_s3d_found_inf", None)
+        mine = (plane is net.bg_mat and w0 is net.bg_net[0].weight and w1 is net.bg_net[1].weight
+                and want_plane and ctx.needs_input_grad[4] and ctx.needs_input_grad[5])
+        flag = flag if mine else None
+        s3d_hip.VmBackend.background_backward(g_rgb.float().contiguous(), rgb, sph, dirs, plane.detach().contiguous(),
+                                              w0.detach().contiguous(), w1.detach().contiguous(), grad_plane, gw0, gw1, flag)
+        if flag is not None:
+            for p in (plane, w0, w1):
+                p._s3d_grad_checked = flag
+        return (None, None, None, grad_plane, gw0 if ctx.needs_input_grad[4] else None, gw1 if ctx.needs_input_grad[5] else None)
+
+
 class _MlpInput(torch.autograd.Function):
     """cat([encoder(feat), encoder_dir(d)]) of tensoRF/network.py:160-166 as the fp16 autocast Linear sees it, in one launch per
     direction (s3d_freq_encode_pack_forward / _backward): fp16 features in, one fp16 [N, ld] row out (ld = the MLP kernels' padded
@@ -256,8 +295,8 @@ class _MeanAbsSum(torch.autograd.Function):
 
 
 class NeRFNetwork(NeRFRenderer):
-    def __init__(self, resolution=(128, 128, 128), sigma_rank=(16, 16, 16), color_rank=(48, 48, 48), color_feat_dim=27,
-                 num_layers=3, hidden_dim=128, bound=1, **kwargs):
+    def __init__(self, resolution=(128, 128, 128), sigma_rank=(16, 16, 16), color_rank=(48, 48, 48), bg_resolution=(512, 512), bg_rank=8,
+                 color_feat_dim=27, num_layers=3, hidden_dim=128, num_layers_bg=2, hidden_dim_bg=64, bound=1, **kwargs):
         super().__init__(bound, **kwargs)
         self.resolution = list(resolution)
         self.sigma_rank, self.color_rank, self.color_feat_dim = list(sigma_rank), list(color_rank), color_feat_dim
@@ -273,7 +312,14 @@ class NeRFNetwork(NeRFRenderer):
         dims = [self.in_dim] + [hidden_dim] * (num_layers - 1) + [3]
         self.color_net = nn.ModuleList([nn.Linear(i, o, bias=False) for i, o in zip(dims[:-1], dims[1:])])
         if self.bg_radius > 0:
-            raise NotImplementedError("background model is outside the BASELINE configs")
+            # background model (tensoRF/network.py:69-96): a dense plane on the ray's sphere coordinates + the direction encoding
+            self.num_layers_bg, self.hidden_dim_bg = num_layers_bg, hidden_dim_bg
+            self.bg_resolution, self.bg_rank = list(bg_resolution), bg_rank
+            self.bg_mat = nn.Parameter(0.1 * torch.randn((1, bg_rank, bg_resolution[0], bg_resolution[1])))  # [1, R, H, W]
+            dims = [bg_rank + enc_dim_dir] + [hidden_dim_bg] * (num_layers_bg - 1) + [3]
+            self.bg_net = nn.ModuleList([nn.Linear(i, o, bias=False) for i, o in zip(dims[:-1], dims[1:])])
+        else:
+            self.bg_net = None
 
     def __getstate__(self):
         """copy.deepcopy (teacher creation, EMA) and pickling leave the backward's sorted-point cache behind"""
@@ -395,6 +441,30 @@ class NeRFNetwork(NeRFRenderer):
     def density(self, x):
         return {"sigma": trunc_exp(self.get_sigma_feat(self._normalize(x)))}
 
+    fused_background = True  # False (test reference): the reference's op sequence
+
+    def _can_fuse_bg(self, x):
+        return (self.fused_background and x.is_cuda and x.dim() == 2 and x.shape[1] == 2 and x.shape[0] > 0
+                and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.float16
+                and self.bg_rank == 8 and self.hidden_dim_bg == 64 and self.num_layers_bg == 2
+                and getattr(self.encoder_dir, "degree", None) == 2 and getattr(self.encoder_dir, "input_dim", None) == 3
+                and self.bg_mat.dtype == torch.float32 and min(self.bg_mat.shape[2:]) >= 2
+                and all(l.bias is None and l.weight.dtype == torch.float32 for l in self.bg_net))
+
+    def background(self, x, d):
+        """x [N, 2]: the ray's sphere coordinates in [-1, 1] (raymarching.sph_from_ray; x[:, 0] runs along the last axis of
+        bg_mat), d [N, 3] -> rgb [N, 3]"""
+        if self._can_fuse_bg(x):
+            return _VmBackground.apply(x, d, self, self.bg_mat, self.bg_net[0].weight, self.bg_net[1].weight)
+        N = x.shape[0]
+        h = F.grid_sample(self.bg_mat, x.view(1, N, 1, 2), align_corners=True).view(-1, N).T.contiguous()  # [R, N] -> [N, R]
+        h = torch.cat([self.encoder_dir(d), h], dim=-1)
+        for k, layer in enumerate(self.bg_net):
+            h = layer(h)
+            if k != self.num_layers_bg - 1:
+                h = F.relu(h, inplace=True)
+        return torch.sigmoid(h)
+
     def density_loss(self):
         """L1 penalty on the density factors (tensoRF/network.py:259-263): sum over the three plane / line pairs of
         mean|sigma_mat| + mean|sigma_vec|; the trainer adds it times `l1_reg_weight` (tensoRF/utils.py:42-49)"""
@@ -423,9 +493,12 @@ class NeRFNetwork(NeRFRenderer):
 
     def get_params(self, lr1, lr2=None):
         lr2 = lr1 if lr2 is None else lr2
-        return [{"params": self.sigma_mat, "lr": lr1}, {"params": self.sigma_vec, "lr": lr1},
-                {"params": self.color_mat, "lr": lr1}, {"params": self.color_vec, "lr": lr1},
-                {"params": self.basis_mat.parameters(), "lr": lr2}, {"params": self.color_net.parameters(), "lr": lr2}]
+        params = [{"params": self.sigma_mat, "lr": lr1}, {"params": self.sigma_vec, "lr": lr1},
+                  {"params": self.color_mat, "lr": lr1}, {"params": self.color_vec, "lr": lr1},
+                  {"params": self.basis_mat.parameters(), "lr": lr2}, {"params": self.color_net.parameters(), "lr": lr2}]
+        if self.bg_radius > 0:
+            params += [{"params": self.bg_mat, "lr": lr1}, {"params": self.bg_net.parameters(), "lr": lr2}]
+        return params
 
     @torch.no_grad()
     def upsample_model(self, resolution):

@@ -1,0 +1,425 @@
+"""The TensoRF background model on the MI355X: the fused kernels (csrc/background.hip: k_vm_bg_forward / k_vm_bg_backward) against
+the reference fixture (tests/golden/tensorf_background.npz) and against the network's own torch path, the plane's edges, and the
+model inside the eager and graph-replayed training steps, Seal fine-tuning and rendering."""
+import os
+import zlib
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from conftest import GOLDEN, REPO
+
+pytestmark = pytest.mark.gpu
+
+NET = dict(resolution=[24, 28, 32], sigma_rank=[4, 5, 6], color_rank=[6, 7, 8], bound=1, cuda_ray=True, density_scale=1,
+           min_near=0.2, density_thresh=10)
+
+
+@pytest.fixture(scope="module")
+def G():
+    return np.load(os.path.join(GOLDEN, "tensorf_background.npz"))
+
+
+def _seeded(shape, seed, lo=0.0, hi=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return torch.rand(*shape, generator=g) * (hi - lo) + lo
+
+
+def _net(bg_resolution=(20, 12), seeded=True, **kw):
+    from tensoRF.network import NeRFNetwork
+    torch.manual_seed(0)
+    net = NeRFNetwork(**dict(NET, bg_radius=32, bg_resolution=list(bg_resolution), **kw))
+    if seeded:
+        for k, p in net.named_parameters():
+            p.data.copy_(_seeded(p.shape, zlib.crc32(k.encode()) % 1000, -0.5, 0.5))
+    return net.cuda()
+
+
+class _Count:
+    """counts the fused background launches (VmBackend.background_forward / _backward) while active"""
+
+    def __init__(self, monkeypatch, hip):
+        self.fwd = self.bwd = 0
+        V = hip.VmBackend
+        f, b = V.background_forward, V.background_backward
+
+        def fwd(*a, **k):
+            self.fwd += 1
+            return f(*a, **k)
+
+        def bwd(*a, **k):
+            self.bwd += 1
+            return b(*a, **k)
+        monkeypatch.setattr(V, "background_forward", staticmethod(fwd))
+        monkeypatch.setattr(V, "background_backward", staticmethod(bwd))
+
+
+def _bg(net, sph, rd, fused):
+    net.fused_background = fused
+    try:
+        with torch.autocast("cuda", dtype=torch.float16):
+            return net.background(sph, rd)
+    finally:
+        net.fused_background = True
+
+
+def _bg_params(net):
+    return net.bg_net[0].weight, net.bg_net[1].weight, net.bg_mat
+
+
+def _both_paths(net, sph, rd, g):
+    """(rgb, dW0, dW1, d bg_mat) of the fused path and of the torch op sequence under the same fp16 autocast"""
+    outs = {}
+    for fused in (True, False):
+        net.zero_grad()
+        rgb = _bg(net, sph, rd, fused)
+        rgb.float().backward(g)
+        outs[fused] = (rgb.detach().float(),) + tuple(p.grad.float().clone() for p in _bg_params(net))
+    return outs
+
+
+def _assert_paths_agree(outs, what=""):
+    """the two paths share their fp16 roundings and differ in summation order only: at most one fp16 ulp of a unit on the colour
+    (1e-3), 1 % of the largest entry on each gradient (the bounds of tests/test_gpu_background.py)"""
+    rgb, r2 = outs[True][0], outs[False][0]
+    print(what, "colour max diff", (rgb - r2).abs().max().item())
+    for name, a, b in zip(("dW0", "dW1", "d bg_mat"), outs[True][1:], outs[False][1:]):
+        print(what, name, "max diff", (a - b).abs().max().item(), "of max", b.abs().max().item())
+    assert (rgb - r2).abs().max().item() <= 1e-3
+    for a, b in zip(outs[True][1:], outs[False][1:]):
+        assert (a - b).abs().max().item() <= 1e-2 * b.abs().max().item() + 1e-4
+
+
+def test_fused_forward_backward_vs_fixture_and_torch_path(hip, monkeypatch, G):
+    net = _net()
+    cnt = _Count(monkeypatch, hip)
+    sph, rd = torch.from_numpy(G["bg_sph"]).cuda(), torch.from_numpy(G["bg_rays_d"]).cuda()
+    g = torch.from_numpy(G["bg_grad_rgb"]).cuda()
+    outs = _both_paths(net, sph, rd, g)
+    assert (cnt.fwd, cnt.bwd) == (1, 1), "the fused path ran exactly once, the torch path not at all"
+    _assert_paths_agree(outs, "fixture rays:")
+    # fp16 tolerance against the reference's fp32 run: the colour per element; the gradients as a whole (relative norm of the
+    # difference: a hidden unit within an fp16 rounding of zero switches its ReLU in one run and not in the other)
+    rgb, gw0, gw1, gm = outs[True]
+    print("vs fp32 reference: colour", (rgb.cpu() - torch.from_numpy(G["bg_rgb"])).abs().max().item())
+    torch.testing.assert_close(rgb.cpu(), torch.from_numpy(G["bg_rgb"]), rtol=0, atol=4e-3)
+    for a, key in ((gw0, "bg_grad_bg_net_0_weight"), (gw1, "bg_grad_bg_net_1_weight"), (gm, "bg_grad_bg_mat")):
+        ref = torch.from_numpy(G[key]).double()
+        rel = ((a.cpu().double() - ref).norm() / ref.norm()).item()
+        print("vs fp32 reference:", key, rel)
+        assert rel < 2e-2, key
+
+
+# coordinates on the border exactly, at the centre, outside by up to 0.05 on one axis or both — with zeros padding such a point
+# still interpolates between the border cell and the zero beside it: on a plane of W cells it loses its last in-range corner only
+# (W - 1) (c - 1) / 2 >= 1 beyond the border, i.e. never on these small planes — and two rows far enough outside (more than a cell
+# on the 2 x 2 plane) that no corner is in range on any of them
+_SPECIAL = [[1.0, -1.0], [-1.0, 1.0], [0.0, 0.0], [1.05, -1.02], [-1.0, -1.0], [1.0, 1.0], [1.0, 0.0], [0.0, -1.0], [1.01, 0.3],
+            [-0.2, -1.05], [-1.03, 1.04], [1.0, 1.05], [-1.05, -1.0], [0.999, 1.0], [1.02, 1.0], [3.0, -3.5], [-3.25, 0.5]]
+
+
+def _no_corner(sph, H, W):
+    """[N] mask of the rays none of whose four corners is in range (the sampler's index arithmetic in fp32)"""
+    x0 = torch.floor(((sph[:, 0] + 1.0) / 2.0) * (W - 1)).long()
+    y0 = torch.floor(((sph[:, 1] + 1.0) / 2.0) * (H - 1)).long()
+    return ((x0 + 1 < 0) | (x0 >= W)) | ((y0 + 1 < 0) | (y0 >= H))
+
+
+def _touched_cells(sph, H, W):
+    """[H, W] mask of the cells an in-range corner of some ray lands on (the sampler's index arithmetic in fp32)"""
+    ix = ((sph[:, 0] + 1.0) / 2.0) * (W - 1)
+    iy = ((sph[:, 1] + 1.0) / 2.0) * (H - 1)
+    x0, y0 = torch.floor(ix).long(), torch.floor(iy).long()
+    mask = torch.zeros(H, W, dtype=torch.bool)
+    for dx in (0, 1):
+        for dy in (0, 1):
+            x, y = x0 + dx, y0 + dy
+            ok = (x >= 0) & (x < W) & (y >= 0) & (y < H)
+            mask[y[ok], x[ok]] = True
+    return mask
+
+
+@pytest.mark.parametrize("plane", [(2, 2), (5, 7), (20, 12)], ids=["2x2", "5x7", "20x12"])
+def test_edge_shapes_against_the_torch_path(hip, plane):
+    """N around the wave and block sizes on three planes, coordinates on and around the border: the fused pair against the torch
+    path, guard rows around the plane and its gradient, exactly zero gradient where no in-range corner lands, and exactly the
+    colour of zero plane features for a ray none of whose corners is in range.  (Both coordinates outside [-1, 1] is not enough
+    for that: F.grid_sample's zeros padding still gives such a ray the border cell's share, see _SPECIAL — the torch-path
+    comparison covers those rays.)"""
+    H, W = plane
+    net = _net(plane)
+    w0, w1 = net.bg_net[0].weight.detach(), net.bg_net[1].weight.detach()
+    n_plane, guard = 8 * H * W, 256
+    for N in (1, 63, 64, 65, 257):
+        sph = _seeded((N, 2), 10 + N, -1.05, 1.05)
+        k = min(N, len(_SPECIAL))
+        sph[:k] = torch.tensor(_SPECIAL[:k])
+        rd = F.normalize(_seeded((N, 3), 20 + N, -1, 1), dim=-1).cuda()
+        g = _seeded((N, 3), 30 + N, -1, 1).cuda()
+        outs = _both_paths(net, sph.cuda(), rd, g)
+        _assert_paths_agree(outs, f"plane {plane} N {N}:")
+        # the same launches on buffers with guard rows around the plane and around its gradient
+        buf = torch.full((guard + n_plane + guard,), 12345.0, device="cuda")
+        gbuf = torch.full((guard + n_plane + guard,), 12345.0, device="cuda")
+        pl, gpl = buf[guard:guard + n_plane].view(1, 8, H, W), gbuf[guard:guard + n_plane].view(1, 8, H, W)
+        pl.copy_(net.bg_mat.detach())
+        gpl.zero_()
+        rgb = torch.empty(N, 3, device="cuda")
+        gw0, gw1 = torch.empty(64, 23, device="cuda"), torch.empty(3, 64, device="cuda")
+        hip.VmBackend.background_forward(sph.cuda(), rd, pl, w0, w1, rgb)
+        hip.VmBackend.background_backward(g, rgb, sph.cuda(), rd, pl, w0, w1, gpl, gw0, gw1)
+        torch.cuda.synchronize()
+        for b in (buf, gbuf):
+            assert bool((b[:guard] == 12345.0).all()) and bool((b[guard + n_plane:] == 12345.0).all()), (plane, N)
+        assert torch.equal(rgb, outs[True][0]) and torch.equal(gw0, outs[True][1]) and torch.equal(gw1, outs[True][2])
+        # no in-range corner: the cell's gradient is exactly zero
+        mask = _touched_cells(sph, H, W).cuda()
+        assert bool((gpl[0][:, ~mask] == 0).all()) and float(gpl.abs().sum()) > 0
+        # no corner in range: exactly the colour of zero plane features
+        outside = _no_corner(sph, H, W).cuda()
+        assert int(outside.sum()) >= (2 if N > len(_SPECIAL) else 0)
+        rgb0 = torch.empty(N, 3, device="cuda")
+        hip.VmBackend.background_forward(sph.cuda(), rd, torch.zeros_like(pl), w0, w1, rgb0)
+        assert torch.equal(rgb[outside], rgb0[outside])
+        assert N == 1 or not torch.equal(rgb[~outside], rgb0[~outside])
+
+
+def test_default_size_plane(hip):
+    net = _net((512, 512), seeded=False)
+    N = 4096
+    sph = _seeded((N, 2), 1, -1.02, 1.02).cuda()
+    rd = F.normalize(_seeded((N, 3), 2, -1, 1), dim=-1).cuda()
+    outs = _both_paths(net, sph, rd, _seeded((N, 3), 3, -1, 1).cuda())
+    _assert_paths_agree(outs, "512x512:")
+    # at this size 1.02 is five cells outside: those rays see no corner and get exactly the colour of zero plane features
+    outside = _no_corner(sph.cpu(), 512, 512).cuda()
+    assert 50 < int(outside.sum()) < N // 2
+    rgb0 = torch.empty(N, 3, device="cuda")
+    hip.VmBackend.background_forward(sph, rd, torch.zeros_like(net.bg_mat), net.bg_net[0].weight.detach(), net.bg_net[1].weight.detach(), rgb0)
+    assert torch.equal(outs[True][0][outside], rgb0[outside])
+
+
+def test_plane_sample_bit_equal_to_grid_sample(hip):
+    net = _net((20, 12))
+    N = 5000
+    sph = _seeded((N, 2), 3, -1.05, 1.05)
+    sph[:len(_SPECIAL)] = torch.tensor(_SPECIAL)
+    sph = sph.cuda()
+    rd = F.normalize(_seeded((N, 3), 4, -1, 1), dim=-1).cuda()
+    feat, rgb = torch.empty(N, 8, device="cuda"), torch.empty(N, 3, device="cuda")
+    hip.VmBackend.background_forward(sph, rd, net.bg_mat.detach(), net.bg_net[0].weight.detach(), net.bg_net[1].weight.detach(), rgb, feat)
+    ref = F.grid_sample(net.bg_mat.detach(), sph.view(1, N, 1, 2), align_corners=True).view(-1, N).T.contiguous()
+    torch.cuda.synchronize()
+    print("plane sample: max diff", (feat - ref).abs().max().item(), "rows differing", int((feat != ref).any(1).sum()))
+    assert torch.equal(feat, ref)
+
+
+def test_frozen_plane_gets_no_scatter(hip, monkeypatch):
+    net = _net()
+    sph = _seeded((300, 2), 5, -1.05, 1.05).cuda()
+    rd = F.normalize(_seeded((300, 3), 6, -1, 1), dim=-1).cuda()
+    g = _seeded((300, 3), 7, -1, 1).cuda()
+    _bg(net, sph, rd, True).float().backward(g)
+    want = [p.grad.clone() for p in _bg_params(net)]
+    net.zero_grad()
+    net.bg_mat.requires_grad_(False)
+    seen = []
+    real = hip.VmBackend.background_backward
+    monkeypatch.setattr(hip.VmBackend, "background_backward", staticmethod(lambda *a, **k: (seen.append(a[7]), real(*a, **k))[1]))
+    _bg(net, sph, rd, True).float().backward(g)
+    assert seen == [None] and net.bg_mat.grad is None
+    assert torch.equal(net.bg_net[0].weight.grad, want[0]) and torch.equal(net.bg_net[1].weight.grad, want[1])
+
+
+# ------------------------------------------------------------------------------------------------ trainers
+def _density(net):
+    from nerf import synthetic as syn
+    dens, bits = syn.lego_like_density_grid(seed=0)
+    net.density_grid.copy_(torch.from_numpy(dens).to(net.density_grid.device))
+    net.density_bitfield.copy_(torch.from_numpy(bits).to(net.density_bitfield.device))
+
+
+def test_executed_train_step_with_background_vs_fixture(hip, monkeypatch, G):
+    """the reference's executed tensoRF Trainer.train_step with bg_radius = 32 (fixture part b) through the build's trainer on
+    the HIP path in fp32, at the bounds of tests/test_gpu_configs.py::test_tensorf_train_step_with_l1_term_vs_the_reference_trainer:
+    loss 1e-5, every recorded gradient within 2e-4 of its largest element"""
+    import nerf.renderer as rend
+    import raymarching.raymarching as rm
+    from tensoRF.utils import Trainer
+    from test_gpu_golden import _CpuRandom
+    net = _net((32, 32))
+    _density(net)
+    net.mean_count = int(G["ts_mean_count"])
+    tr = Trainer(net, lr0=2e-2, lr1=1e-3, l1_reg_weight=float(G["ts_l1_weight"]), fp16=False, update_extra_interval=10 ** 9)
+    assert [g["lr"] for g in tr.optimizer.param_groups] == [2e-2] * 4 + [1e-3] * 2 + [2e-2, 1e-3]
+    tr.global_step = 1
+    net.train()
+    proxy = _CpuRandom()
+    monkeypatch.setattr(rm, "torch", proxy)
+    monkeypatch.setattr(rend, "torch", proxy)
+    torch.manual_seed(5)
+    seen = {}
+    monkeypatch.setattr(tr, "_reduce_and_step", lambda: seen.update(
+        {k: (p.grad if p.grad is not None else getattr(p, "_s3d_grad", None)).detach().float().clone() for k, p in net.named_parameters()}))
+    ro, rd, gt = (torch.from_numpy(G[k]).cuda() for k in ("ts_rays_o", "ts_rays_d", "ts_images"))
+    loss = tr.train_step(ro[0].contiguous(), rd[0].contiguous(), gt[0].contiguous())
+    assert np.array_equal(net.step_counter[0].cpu().numpy(), G["ts_counter"])
+    print("train step: loss", float(loss), "fixture", float(G["ts_loss"]))
+    assert abs(float(loss) - float(G["ts_loss"])) <= 1e-5 * float(G["ts_loss"])
+    scale = float(tr.scaler.get_scale()) if hasattr(tr.scaler, "get_scale") else 1.0
+    for k, g in seen.items():
+        key = "ts_grad_" + k.replace(".", "_")
+        g = (g / scale).reshape(-1).cpu()
+        ref = float(G[key + "_norm"])
+        assert abs(float(g.double().norm()) - ref) <= 2e-4 * ref, k
+        if key in G.files:
+            want = torch.from_numpy(G[key])
+            assert float((g - want).abs().max()) <= 2e-4 * float(want.abs().max()) + 1e-9, k
+
+
+def _scene_rays(n, seed=0):
+    from nerf import synthetic as syn
+    poses = syn.orbit_poses(2, seed=0)
+    r = syn.get_rays(poses[:1], syn.lego_intrinsics(), 800, 800, N=n, generator=torch.Generator().manual_seed(seed))
+    return r["rays_o"][0].cuda().contiguous(), r["rays_d"][0].cuda().contiguous()
+
+
+def _graphed_run(recapture, steps=3, n=512):
+    from tensoRF.utils import GraphedTrainer
+    ro, rd = _scene_rays(n)
+    gt = _seeded((n, 3), 9).cuda()
+    net = _net((32, 32), resolution=[32, 32, 32])
+    _density(net)
+    net.iter_density = 100
+    tr = GraphedTrainer(net, n, lr0=2e-2, lr1=1e-3, l1_reg_weight=1e-4, fp16=True, update_extra_interval=10 ** 9)
+    tr.global_step = 1
+    net.mean_count = n * 40
+    losses = []
+    for _ in range(steps):
+        if recapture:
+            tr.graph = None  # every step is the capture's eager step (the same body, run on the stream instead of replayed)
+        losses.append(float(tr.train_step(ro, rd, gt)))
+    torch.cuda.synchronize()
+    return net, tr, losses
+
+
+def test_graphed_replay_equals_the_eager_step_with_background(hip, monkeypatch):
+    """GraphedTrainer with the background model: 3 steps replayed from the graph vs the same 3 steps each run eagerly (the
+    capture's warm-up step: same body, same jitter from the device step counter).  Tolerance, not bit equality: the plane and
+    factor gradients are summed by atomics, whose order differs between runs.  Adam moves an entry by up to ~lr per step whatever
+    its gradient's size, so single entries whose gradient is at the level of the atomics' rounding may differ by a few lr; a
+    missing, doubled or wrongly scaled update of a parameter (a `grad_bg_mat` that is not re-zeroed inside the capture: the second
+    replay would step on twice the gradient) moves the tensor's mean by ~lr."""
+    cnt = _Count(monkeypatch, hip)
+    net_r, tr_r, l_r = _graphed_run(False)
+    assert tr_r.n_captures == 1 and cnt.fwd >= 2 and cnt.bwd >= 2  # the capture's eager step + the recorded one, then replays
+    net_e, tr_e, l_e = _graphed_run(True)
+    assert tr_e.n_captures == 3
+    print("graphed losses", l_r, "eager", l_e)
+    assert np.isfinite(l_r).all() and np.isfinite(l_e).all()
+    np.testing.assert_allclose(l_r, l_e, rtol=1e-3)
+    for (k, a), b in zip(net_r.named_parameters(), net_e.parameters()):
+        diff = (a.detach() - b.detach()).abs()
+        print("graphed vs eager", k, "max", diff.max().item(), "mean", diff.mean().item())
+        lr = 2e-2 if ("mat" in k and "basis" not in k) or "vec" in k else 1e-3
+        assert diff.max().item() <= 3 * lr and diff.mean().item() <= 1e-3 * lr, (k, diff.max().item(), diff.mean().item())
+    moved = (net_r.bg_mat.detach() - _net((32, 32), resolution=[32, 32, 32]).bg_mat.detach()).abs()
+    assert moved.mean().item() > 1e-3  # (the plane did move: three Adam steps of 2e-2 on the cells the rays reach)
+
+
+def test_render_with_background_matches_torch_path(hip, monkeypatch):
+    from nerf import synthetic as syn
+    net = _net((32, 32))
+    cnt = _Count(monkeypatch, hip)
+    _density(net)
+    net.eval()
+    r = syn.get_rays(syn.orbit_poses(2, seed=0)[1:2], syn.lego_intrinsics(64, 64), 64, 64)
+    ro, rd = r["rays_o"].cuda().contiguous(), r["rays_d"].cuda().contiguous()
+    imgs = []
+    for fused in (True, False):
+        net.fused_background = fused
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
+            imgs.append(net.render(ro, rd, staged=False, perturb=False, max_steps=1024)["image"].float())
+    net.fused_background = True
+    assert cnt.fwd == 1  # once per frame, before the march loop; the torch-path frame launched none
+    assert imgs[0].shape == (1, 4096, 3)
+    print("render: max diff", (imgs[0] - imgs[1]).abs().max().item())
+    assert (imgs[0] - imgs[1]).abs().max().item() <= 2e-3
+
+
+def test_graphed_seal_bbox_finetune_and_proxy_truth_with_background(hip):
+    from nerf import synthetic as syn
+    from sealnerf import get_seal_mapper, get_trainer, make_student, make_teacher
+    from tensoRF import network as trf
+    from test_seal_golden import case_config
+    torch.manual_seed(0)
+    kw = dict(resolution=[64] * 3, bound=1, cuda_ray=True, density_scale=1, min_near=0.2, density_thresh=10, bg_radius=32,
+              bg_resolution=[32, 32])
+    teacher = make_teacher(trf.NeRFNetwork, **kw).cuda()
+    student = make_student(trf.NeRFNetwork, **kw).cuda()
+    grid, bits = syn.lego_like_density_grid(seed=0)
+    for net in (teacher, student):
+        net.density_grid.copy_(torch.from_numpy(grid))
+        net.density_bitfield.copy_(torch.from_numpy(bits))
+        net.iter_density = 100
+    student.load_state_dict(teacher.state_dict())
+    m = get_seal_mapper(case_config("both", np.load(os.path.join(REPO, "tests", "golden", "seal_bbox.npz"))))
+    teacher.init_mapper(m)
+    student.init_mapper(m)
+    tr = get_trainer("tensorf", graphed=True)(student, teacher, 1024, lr0=2e-2, lr1=1e-3, l1_reg_weight=1e-4, fp16=True,
+                                              update_extra_interval=16)
+    assert [g["lr"] for g in tr.optimizer.param_groups] == [2e-2] * 4 + [1e-3] * 2 + [2e-2, 1e-3]
+    poses = syn.orbit_poses(1, seed=0).cuda()
+    r = syn.get_rays(poses, syn.lego_intrinsics(), 800, 800, N=1024, generator=torch.Generator().manual_seed(0))
+    ro, rd = r["rays_o"][0].contiguous(), r["rays_d"][0].contiguous()
+    # proxy targets with the teacher's background model: the per-ray target kernel == the torch composite
+    rgb, dep = tr.proxy_truth(ro, rd)
+    with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
+        teacher.train()
+        out = teacher.render(ro, rd, staged=True, bg_color=None, perturb=False, force_all_rays=True, max_steps=1024)
+    torch.testing.assert_close(rgb.reshape(-1, 3), torch.nan_to_num(out["image"].reshape(-1, 3).float()), rtol=0, atol=1e-6)
+    bg0 = student.bg_mat.detach().clone()
+    hist = [float(tr.train_step(ro, rd)) for _ in range(24)]
+    assert tr.n_captures >= 1 and np.isfinite(hist).all(), hist
+    assert not torch.equal(student.bg_mat.detach(), bg0)
+
+
+# measured on an MI355X: 300 steps of 4,096 rays, error on 8,192 held-out rays / error of the best constant background = 0.096
+# (err 1.2e-4, constant 1.25e-3; profiles/tensorf_background.md).  The bound is that ratio plus the headroom
+# tests/test_gpu_background.py gives itself for the run-to-run variation of the atomics (0.54 -> 0.75: + 0.21).
+SMOOTH_RATIO_BOUND = 0.31
+
+
+def _smooth_target(d):
+    """a smooth colour of the ray direction (the scene holds nothing else: every ray misses)"""
+    return torch.stack([0.5 + 0.35 * d[:, 0], 0.5 + 0.3 * d[:, 1] * d[:, 2], 0.4 + 0.4 * d[:, 2] ** 2], 1).clamp(0, 1)
+
+
+def smooth_background_run(steps=300):
+    from nerf import synthetic as syn
+    from tensoRF.utils import Trainer
+    net = _net((64, 64), seeded=False)
+    net.density_grid.zero_()
+    net.density_bitfield.zero_()  # empty scene: the pixel is the background
+    tr = Trainer(net, lr0=2e-2, lr1=1e-3, l1_reg_weight=1e-4, fp16=True, update_extra_interval=10 ** 9)
+    poses = syn.orbit_poses(16, seed=1)
+    for it in range(steps):
+        r = syn.get_rays(poses[it % 16:it % 16 + 1], syn.lego_intrinsics(), 800, 800, N=4096,
+                         generator=torch.Generator().manual_seed(it))
+        ro, rd = r["rays_o"][0].cuda().contiguous(), r["rays_d"][0].cuda().contiguous()
+        tr.train_step(ro, rd, _smooth_target(rd))
+    r = syn.get_rays(syn.orbit_poses(1, seed=9), syn.lego_intrinsics(), 800, 800, N=8192, generator=torch.Generator().manual_seed(999))
+    ro, rd = r["rays_o"][0].cuda().contiguous(), r["rays_d"][0].cuda().contiguous()
+    gt = _smooth_target(rd)
+    img = tr.render_image(ro, rd)["image"].reshape(-1, 3).float()
+    err = float(((img - gt) ** 2).mean())
+    const = float(((gt - gt.mean(0)) ** 2).mean())
+    return err, const
+
+
+def test_background_model_learns_a_smooth_background(hip):
+    err, const = smooth_background_run()
+    print("smooth background: err", err, "constant", const, "ratio", err / const)
+    assert err < SMOOTH_RATIO_BOUND * const, (err, const, err / const)
