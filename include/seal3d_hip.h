@@ -92,6 +92,29 @@ int s3d_sweep_update(float* density_grid, uint32_t n_cells, const int32_t* cells
                      uint32_t n, float density_scale, float decay, void* workspace, size_t workspace_bytes,
                      float* grid_sum, int32_t* step_counter, s3d_stream_t stream);
 
+/* The same sweep without a host value between its launches (what a graph-replayed trainer runs).
+ * s3d_sweep_draw_native: s3d_sweep_draw without the [H^3] prefix array.  Three launches: per block of 1,024 cells the count and
+ *   the bit mask of the cells with density > 0, and tmp[H^3] = -1; a one-workgroup scan of the block counts; the draw (cells
+ *   [2N], xyzs [2N, 3], jitter as in s3d_sweep_draw).  The occupied half is searchsorted(cumsum(grid > 0),
+ *   floor(u_occupied * #occupied), right=True) clamped to H^3 - 1, found in the scanned block counts and the block's mask.
+ * s3d_sweep_scatter_update: tmp (filled by the draw) <- max over the samples, density_grid <- EMA-max; partial
+ *   [s3d_sweep_partial_stride()] receives the per-block sums of max(density_grid, 0); sigma is read `sigma_stride` elements apart.
+ * s3d_sweep_tail: one workgroup; partial [cascades, s3d_sweep_partial_stride()] -> record = {float mean(max(grid, 0)), float
+ *   min(mean, density_thresh), uint32 lo, hi of the int64 sum of step_ring[r, 0], r < min(16, *local_step)} (16 bytes);
+ *   *sweep_step (optional) += 1.
+ * s3d_packbits_record: s3d_packbits with the threshold taken from such a record. */
+size_t s3d_sweep_draw_native_workspace_size(uint32_t H);
+int s3d_sweep_draw_native(const double* u_uniform, const double* u_occupied, const float* density_grid, uint32_t N, uint32_t H,
+                          float bound, float half_cell, uint32_t noise_key, const int32_t* noise_step, float* tmp, int32_t* cells,
+                          float* xyzs, void* workspace, size_t workspace_bytes, s3d_stream_t stream);
+uint32_t s3d_sweep_partial_stride(void);
+int s3d_sweep_scatter_update(float* density_grid, uint32_t n_cells, const int32_t* cells, const void* sigma, int sigma_dtype,
+                             uint32_t sigma_stride, uint32_t n, float density_scale, float decay, float* tmp, float* partial,
+                             s3d_stream_t stream);
+int s3d_sweep_tail(const float* partial, uint32_t cascades, uint32_t n_cells, float density_thresh, const int32_t* step_ring,
+                   const int32_t* local_step, int32_t* sweep_step, void* record, s3d_stream_t stream);
+int s3d_packbits_record(const float* grid, uint32_t N, const void* record, uint8_t* bitfield, s3d_stream_t stream);
+
 /* raymarching.h:13 void march_rays_train(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M,
  *                                        nears, fars, xyzs, dirs, deltas, rays, counter, noises)
  * Spans are packed in RAY ORDER (deterministic; one valid outcome of the reference's atomic

@@ -153,7 +153,7 @@ __global__ void k_morton3d_invert(const int32_t* __restrict__ indices, uint32_t 
 }
 
 // one lane = one output byte = 8 cells = two float4 loads (32 B/lane, 2 KiB contiguous per wave)
-__global__ void k_packbits(const float* __restrict__ grid, uint32_t N, float thresh, uint8_t* __restrict__ bitfield) {
+__device__ __forceinline__ void packbits_rows(const float* __restrict__ grid, uint32_t N, float thresh, uint8_t* __restrict__ bitfield) {
     const float4* g4 = reinterpret_cast<const float4*>(grid);
     for (uint32_t n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x) {
         const float4 a = g4[n * 2], b = g4[n * 2 + 1];
@@ -165,6 +165,22 @@ __global__ void k_packbits(const float* __restrict__ grid, uint32_t N, float thr
         bitfield[n] = (uint8_t)bits;
     }
 }
+__global__ void k_packbits(const float* __restrict__ grid, uint32_t N, float thresh, uint8_t* __restrict__ bitfield) {
+    packbits_rows(grid, N, thresh, bitfield);
+}
+
+// The record the occupancy sweep's tail launch leaves on the device (seal3d_hip.h: s3d_sweep_tail): 16 bytes
+struct SweepRecord {
+    float mean;         // mean(clamp(density_grid, 0))
+    float thresh;       // min(mean, density_thresh): what the bitfield is packed with
+    uint32_t count_lo;  // sum of the first min(16, local_step) rows of step_counter[:, 0], as an int64 in two words
+    uint32_t count_hi;
+};
+// the same, with the threshold read from the sweep's record: no host value between the update and the re-pack
+__global__ void k_packbits_record(const float* __restrict__ grid, uint32_t N, const SweepRecord* __restrict__ record,
+                                  uint8_t* __restrict__ bitfield) {
+    packbits_rows(grid, N, record->thresh, bitfield);
+}
 
 // ---------------------------------------------------------------- occupancy sweep (density-grid maintenance)
 // The steady-state update of the reference (nerf/renderer.py:497-538) as three launches around the density query instead of
@@ -172,6 +188,22 @@ __global__ void k_packbits(const float* __restrict__ grid, uint32_t N, float thr
 //   draw:   i <  N: cell = floor(u_uniform[i] * H^3)                         (uniform cells; morton index = cell id)
 //           i >= N: cell = the floor(u_occupied[i-N] * #occupied)-th cell with density > 0   (binary search in the prefix counts)
 //           xyz = (2 c / (H-1) - 1) * (bound - half_cell) + (2 r - 1) * half_cell,  r = counter-based u01(key, step, 3 i + d)
+__device__ __forceinline__ uint32_t sweep_uniform_cell(double u, uint32_t H3) {
+    const double v = u * (double)H3;
+    return v >= (double)(H3 - 1) ? H3 - 1 : (uint32_t)v;
+}
+// sample i of the sweep: its cell and the jittered position inside it
+__device__ __forceinline__ void sweep_emit(uint32_t i, uint32_t cell, uint32_t H, float bound, float half_cell, uint32_t noise_key,
+                                           uint32_t step, int32_t* __restrict__ cells, float* __restrict__ xyzs) {
+    cells[i] = (int32_t)cell;
+    const float inv = 2.0f / (float)(H - 1), span = bound - half_cell;
+#pragma unroll
+    for (uint32_t d = 0; d < 3; d++) {
+        const float c = (float)morton3d_invert(cell >> d);
+        const float r = ray_noise(noise_key, step, 3u * i + d);
+        xyzs[(size_t)i * 3 + d] = __builtin_fmaf(__builtin_fmaf(2.0f, r, -1.0f), half_cell, (c * inv - 1.0f) * span);
+    }
+}
 __global__ void __launch_bounds__(256) k_sweep_draw(const double* __restrict__ u_uniform, const double* __restrict__ u_occupied,
                                                     const int32_t* __restrict__ occ_csum, uint32_t N, uint32_t H, float bound,
                                                     float half_cell, uint32_t noise_key, const int32_t* __restrict__ noise_step,
@@ -181,8 +213,7 @@ __global__ void __launch_bounds__(256) k_sweep_draw(const double* __restrict__ u
     const uint32_t H3 = H * H * H;
     uint32_t cell;
     if (i < N) {
-        const double v = u_uniform[i] * (double)H3;
-        cell = v >= (double)(H3 - 1) ? H3 - 1 : (uint32_t)v;
+        cell = sweep_uniform_cell(u_uniform[i], H3);
     } else {
         const int32_t total = occ_csum[H3 - 1];
         const int32_t pick = (int32_t)(u_occupied[i - N] * (double)total);
@@ -194,14 +225,149 @@ __global__ void __launch_bounds__(256) k_sweep_draw(const double* __restrict__ u
         }
         cell = lo < H3 ? lo : H3 - 1;
     }
-    cells[i] = (int32_t)cell;
     const uint32_t step = noise_step ? (uint32_t)*noise_step : 0u;
-    const float inv = 2.0f / (float)(H - 1), span = bound - half_cell;
+    sweep_emit(i, cell, H, bound, half_cell, noise_key, step, cells, xyzs);
+}
+
+// ---- the same draw without the 2 M-entry prefix array (s3d_sweep_draw_native): three launches per cascade.  The cells with
+// density > 0 are counted per block of 1,024 cells (and kept as a bit mask, which also leaves tmp = -1 for the scatter), one
+// workgroup scans the block counts, and the draw finds the pick-th occupied cell in the scanned counts and the block's mask.
+constexpr uint32_t kScanBlock = 1024;
+constexpr uint32_t kSweepCntLds = 4096;  // block counts the draw kernel keeps in LDS (16 KiB)
+
+// exclusive prefix of `mine` over the 256 threads of the block and the block's total; `sh` holds 4 values
+template <typename T>
+__device__ __forceinline__ T block_scan_exclusive(T mine, T* sh, T& total) {
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    T incl = mine;
 #pragma unroll
-    for (uint32_t d = 0; d < 3; d++) {
-        const float c = (float)morton3d_invert(cell >> d);
-        const float r = ray_noise(noise_key, step, 3u * i + d);
-        xyzs[(size_t)i * 3 + d] = __builtin_fmaf(__builtin_fmaf(2.0f, r, -1.0f), half_cell, (c * inv - 1.0f) * span);
+    for (int d = 1; d < 64; d <<= 1) {
+        const T up = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl = incl + up;
+    }
+    if (lane == 63u) sh[w] = incl;
+    __syncthreads();
+    const T w0 = sh[0], w1 = sh[1], w2 = sh[2], w3 = sh[3];
+    __syncthreads();
+    const T before = __shfl_up(incl, 1, 64);
+    const T lanes = lane == 0u ? T(0) : before;
+    total = ((w0 + w1) + w2) + w3;
+    const T off = w == 0 ? T(0) : (w == 1 ? w0 : (w == 2 ? w0 + w1 : (w0 + w1) + w2));
+    return off + lanes;
+}
+
+// Partials: per block of 1,024 cells the number of cells with density > 0 and their bit mask (32 words), and tmp = -1 for
+// those cells (the scatter's start value).
+__global__ void __launch_bounds__(256) k_sweep_partials(const float* __restrict__ grid, uint32_t H3, float* __restrict__ tmp,
+                                                        int32_t* __restrict__ cnt, uint32_t* __restrict__ occ_bits, uint32_t nbc) {
+    __shared__ int32_t shi[4];
+    __shared__ uint32_t words[32];
+    const uint32_t t = threadIdx.x;
+    for (uint32_t b = blockIdx.x; b < nbc; b += gridDim.x) {  // (b is the same for the whole workgroup: barriers are uniform)
+        const uint32_t c0 = b * kScanBlock + 4u * t;
+        uint32_t nib = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < 4; q++)
+            if (c0 + q < H3) {
+                nib |= grid[c0 + q] > 0.0f ? (1u << q) : 0u;
+                tmp[c0 + q] = -1.0f;
+            }
+        if (t < 32) words[t] = 0;
+        __syncthreads();
+        if (nib) atomicOr(&words[t >> 3], nib << (4u * (t & 7u)));
+        __syncthreads();
+        if (t < 32) occ_bits[b * 32u + t] = words[t];
+        int32_t total;
+        (void)block_scan_exclusive((int32_t)__popc(nib), shi, total);
+        if (t == 0) cnt[b] = total;
+    }
+}
+
+// in-place inclusive scan of a[0 .. n) by ONE workgroup, in passes of 1,024 (fixed order, see above)
+template <typename T>
+__device__ __forceinline__ void scan_inclusive_in_place(T* __restrict__ a, uint32_t n, T* sh) {
+    T carry = T(0);
+    for (uint32_t base = 0; base < n; base += kScanBlock) {
+        const uint32_t j0 = base + 4u * threadIdx.x;
+        T l[4], acc = T(0);
+#pragma unroll
+        for (uint32_t q = 0; q < 4; q++) {
+            const T v = (j0 + q < n) ? a[j0 + q] : T(0);
+            acc = q == 0 ? v : acc + v;
+            l[q] = acc;
+        }
+        T total;
+        const T pre = carry + block_scan_exclusive(acc, sh, total);
+#pragma unroll
+        for (uint32_t q = 0; q < 4; q++)
+            if (j0 + q < n) a[j0 + q] = pre + l[q];
+        carry = carry + total;
+    }
+}
+__global__ void __launch_bounds__(256) k_sweep_scan(int32_t* __restrict__ cnt, uint32_t nbc) {
+    __shared__ int32_t shi[4];
+    scan_inclusive_in_place(cnt, nbc, shi);
+}
+
+// the pick-th (0-based) cell with density > 0 out of the scanned block counts and the blocks' bit masks; == searchsorted(cumsum(grid
+// > 0), pick, right=True) clamped to the last cell (no occupied cell, or pick == #occupied: the last cell)
+__device__ __forceinline__ uint32_t sweep_occupied_cell(int32_t pick, const int32_t* __restrict__ incl_cnt,
+                                                        const uint32_t* __restrict__ occ_bits, uint32_t nbc, uint32_t H3) {
+    uint32_t lo = 0, hi = nbc;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (incl_cnt[mid] > pick) hi = mid; else lo = mid + 1;
+    }
+    if (lo >= nbc) return H3 - 1;
+    const int32_t r = pick - (lo ? incl_cnt[lo - 1] : 0);  // 0 <= r < cells occupied in block lo
+    // the block's 32 mask words in eight independent 16-byte loads (one cache line), then registers only
+    const uint4* __restrict__ w4 = reinterpret_cast<const uint4*>(occ_bits + (size_t)lo * 32u);
+    uint4 v[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) v[k] = w4[k];
+    uint32_t word = 0, at = 32;
+    int32_t rest = 0, before = 0;
+#pragma unroll
+    for (int w = 0; w < 32; w++) {
+        const uint4 q = v[w >> 2];
+        const uint32_t x = (w & 3) == 0 ? q.x : ((w & 3) == 1 ? q.y : ((w & 3) == 2 ? q.z : q.w));
+        const int32_t c = (int32_t)__popc(x);
+        if (at == 32 && r < before + c) { at = (uint32_t)w; word = x; rest = r - before; }
+        before += c;
+    }
+    if (at == 32) return H3 - 1;
+    for (; rest > 0; rest--) word &= word - 1u;  // drop the `rest` lowest set bits
+    const uint32_t cell = lo * kScanBlock + at * 32u + (uint32_t)(__ffs((int)word) - 1);
+    return cell < H3 ? cell : H3 - 1;
+}
+
+// Draw: thread t of workgroup b takes elements 1,024 b + 4 t .. + 3 of both sorted streams; the cells and positions follow
+// exactly as in k_sweep_draw (element j of the uniform stream is sample j, of the occupied stream sample N + j).
+__global__ void __launch_bounds__(256) k_sweep_draw_native(const double* __restrict__ u_uniform, const double* __restrict__ u_occupied,
+                                                           const int32_t* __restrict__ incl_cnt, const uint32_t* __restrict__ occ_bits,
+                                                           uint32_t nbc, uint32_t N, uint32_t H, float bound, float half_cell,
+                                                           uint32_t noise_key, const int32_t* __restrict__ noise_step,
+                                                           int32_t* __restrict__ cells, float* __restrict__ xyzs) {
+    const uint32_t H3 = H * H * H;
+    const uint32_t step = noise_step ? (uint32_t)*noise_step : 0u;
+    // the scanned block counts go to LDS when they fit (the Lego grid: 2,048): the search's dependent probes stay on chip
+    __shared__ int32_t sh_cnt[kSweepCntLds];
+    const int32_t* cnt = incl_cnt;
+    if (nbc <= kSweepCntLds) {
+        for (uint32_t i = threadIdx.x; i < nbc; i += 256) sh_cnt[i] = incl_cnt[i];
+        __syncthreads();
+        cnt = sh_cnt;
+    }
+    const int32_t occupied = cnt[nbc - 1];
+    const uint32_t j0 = blockIdx.x * kScanBlock + 4u * threadIdx.x;
+#pragma unroll
+    for (uint32_t q = 0; q < 4; q++) {
+        const uint32_t j = j0 + q;
+        if (j < N) {
+            sweep_emit(j, sweep_uniform_cell(u_uniform[j], H3), H, bound, half_cell, noise_key, step, cells, xyzs);
+            const int32_t pick = (int32_t)(u_occupied[j] * (double)occupied);
+            sweep_emit(N + j, sweep_occupied_cell(pick, cnt, occ_bits, nbc, H3), H, bound, half_cell, noise_key, step, cells, xyzs);
+        }
     }
 }
 
@@ -213,11 +379,11 @@ __global__ void __launch_bounds__(256) k_sweep_fill(float* __restrict__ tmp, uin
 // of its outcomes and does not depend on the order).  Densities are >= 0 or NaN: as int32 patterns non-negative floats order
 // like the floats and lie above -1.0f; a NaN (0x7fc00000) wins, i.e. poisons the cell exactly like in the reference.
 template <typename T>
-__global__ void __launch_bounds__(256) k_sweep_scatter(const int32_t* __restrict__ cells, const T* __restrict__ sigma, uint32_t n,
-                                                       float scale, float* __restrict__ tmp) {
+__global__ void __launch_bounds__(256) k_sweep_scatter(const int32_t* __restrict__ cells, const T* __restrict__ sigma, uint32_t stride,
+                                                       uint32_t n, float scale, float* __restrict__ tmp) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float v = (float)sigma[i] * scale;
+    const float v = (float)sigma[(size_t)i * stride] * scale;
     atomicMax(reinterpret_cast<int32_t*>(tmp) + cells[i], __float_as_int(v));
 }
 // grid = max(grid * decay, tmp) where both are >= 0 (renderer.py:529-531); per-block sums of clamp(grid, 0) for the mean
@@ -237,18 +403,51 @@ __global__ void __launch_bounds__(256) k_sweep_update(float* __restrict__ grid, 
     __syncthreads();
     if (threadIdx.x == 0) partial[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
 }
-__global__ void __launch_bounds__(256) k_sweep_mean(const float* __restrict__ partial, uint32_t nblocks, float inv_n, float* __restrict__ mean,
-                                                    int32_t* __restrict__ step_counter) {
-    __shared__ float wsum[4];
+// sum of the per-block sums of k_sweep_update by one workgroup, the same value on every thread (fixed order)
+__device__ __forceinline__ float sweep_sum_partials(const float* __restrict__ partial, uint32_t nblocks, float* wsum) {
     float acc = 0.0f;
     for (uint32_t i = threadIdx.x; i < nblocks; i += 256) acc += partial[i];
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
     __syncthreads();
+    const float s = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    __syncthreads();
+    return s;
+}
+__global__ void __launch_bounds__(256) k_sweep_mean(const float* __restrict__ partial, uint32_t nblocks, float inv_n, float* __restrict__ mean,
+                                                    int32_t* __restrict__ step_counter) {
+    __shared__ float wsum[4];
+    const float s = sweep_sum_partials(partial, nblocks, wsum);
     if (threadIdx.x == 0) {
-        *mean = ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])) * inv_n;
+        *mean = s * inv_n;
         if (step_counter) *step_counter += 1;
+    }
+}
+// The update's tail in one launch: mean over all cascades (each cascade's sum as k_sweep_mean forms it, the cascades added in
+// order, times inv_n: torch's `total / numel` with a host scalar multiplies by its fp32 reciprocal too), the packing threshold min(mean, density_thresh) as the host's min() would return it, and the sample
+// count of the last min(16, *local_step) training steps out of the counter ring [16, 2]; *sweep_step += 1.
+__global__ void __launch_bounds__(256) k_sweep_tail(const float* __restrict__ partial, uint32_t cascades, uint32_t stride,
+                                                    uint32_t nblocks, float inv_n, float density_thresh,
+                                                    const int32_t* __restrict__ step_ring, const int32_t* __restrict__ local_step,
+                                                    int32_t* __restrict__ sweep_step, SweepRecord* __restrict__ record) {
+    __shared__ float wsum[4];
+    float total = 0.0f;
+    for (uint32_t c = 0; c < cascades; c++) {
+        const float s = sweep_sum_partials(partial + (size_t)c * stride, nblocks, wsum);
+        total = c == 0 ? s : total + s;
+    }
+    if (threadIdx.x == 0) {
+        const float mean = total * inv_n;
+        record->mean = mean;
+        record->thresh = density_thresh < mean ? density_thresh : mean;  // Python's min(mean, density_thresh), NaN included
+        int32_t rows = *local_step;
+        rows = rows < 0 ? 0 : (rows > 16 ? 16 : rows);
+        int64_t count = 0;
+        for (int32_t r = 0; r < rows; r++) count += step_ring[2 * r];
+        record->count_lo = (uint32_t)((uint64_t)count & 0xFFFFFFFFull);
+        record->count_hi = (uint32_t)((uint64_t)count >> 32);
+        if (sweep_step) *sweep_step += 1;
     }
 }
 
@@ -1803,6 +2002,18 @@ S3D_EXPORT int s3d_compact_alive(const int32_t* in, uint32_t n, int32_t* out, in
 }
 
 constexpr uint32_t kSweepBlocks = 1024;
+static uint32_t sweep_update_blocks(uint32_t n_cells) { return std::min<uint32_t>(kSweepBlocks, div_up<uint32_t>(n_cells, 256)); }
+// sigma [n] in its own dtype, `stride` elements apart (a column of the density head's output needs no copy)
+static void launch_sweep_scatter(const int32_t* cells, const void* sigma, int sigma_dtype, uint32_t stride, uint32_t n, float scale,
+                                 float* tmp, hipStream_t st) {
+    if (n == 0) return;
+    if (sigma_dtype == S3D_F16)
+        hipLaunchKernelGGL(k_sweep_scatter<_Float16>, dim3(div_up<uint32_t>(n, 256)), dim3(256), 0, st, cells, (const _Float16*)sigma,
+                           stride, n, scale, tmp);
+    else
+        hipLaunchKernelGGL(k_sweep_scatter<float>, dim3(div_up<uint32_t>(n, 256)), dim3(256), 0, st, cells, (const float*)sigma, stride,
+                           n, scale, tmp);
+}
 
 S3D_EXPORT int s3d_sweep_draw(const double* u_uniform, const double* u_occupied, const int32_t* occ_csum, uint32_t N, uint32_t H,
                               float bound, float half_cell, uint32_t noise_key, const int32_t* noise_step, int32_t* cells,
@@ -1827,16 +2038,67 @@ S3D_EXPORT int s3d_sweep_update(float* density_grid, uint32_t n_cells, const int
     float* tmp = (float*)workspace;
     float* partial = tmp + n_cells;
     hipLaunchKernelGGL(k_sweep_fill, dim3(div_up<uint32_t>(n_cells, 256)), dim3(256), 0, st, tmp, n_cells);
-    if (n) {
-        if (sigma_dtype == S3D_F16)
-            hipLaunchKernelGGL(k_sweep_scatter<_Float16>, dim3(div_up<uint32_t>(n, 256)), dim3(256), 0, st, cells, (const _Float16*)sigma, n,
-                               density_scale, tmp);
-        else
-            hipLaunchKernelGGL(k_sweep_scatter<float>, dim3(div_up<uint32_t>(n, 256)), dim3(256), 0, st, cells, (const float*)sigma, n,
-                               density_scale, tmp);
-    }
-    const uint32_t blocks = std::min<uint32_t>(kSweepBlocks, div_up<uint32_t>(n_cells, 256));
+    launch_sweep_scatter(cells, sigma, sigma_dtype, 1, n, density_scale, tmp, st);
+    const uint32_t blocks = sweep_update_blocks(n_cells);
     hipLaunchKernelGGL(k_sweep_update, dim3(blocks), dim3(256), 0, st, density_grid, (const float*)tmp, n_cells, decay, partial);
     hipLaunchKernelGGL(k_sweep_mean, dim3(1), dim3(256), 0, st, (const float*)partial, blocks, 1.0f, grid_sum, step_counter);
     return check_launch("sweep_update");
+}
+
+// ---- the sweep with its streams, tail and re-pack on the device (seal3d_hip.h)
+static uint32_t sweep_cell_blocks(uint32_t H) { return div_up<uint32_t>(H * H * H, kScanBlock); }
+
+S3D_EXPORT size_t s3d_sweep_draw_native_workspace_size(uint32_t H) { return (size_t)sweep_cell_blocks(H) * 33 * sizeof(uint32_t); }
+
+S3D_EXPORT int s3d_sweep_draw_native(const double* u_uniform, const double* u_occupied, const float* density_grid, uint32_t N,
+                                     uint32_t H, float bound, float half_cell, uint32_t noise_key, const int32_t* noise_step,
+                                     float* tmp, int32_t* cells, float* xyzs, void* workspace, size_t workspace_bytes,
+                                     s3d_stream_t stream) {
+    S3D_REQUIRE(u_uniform && u_occupied && density_grid && tmp && cells && xyzs && N > 0, "sweep_draw_native: null pointer or N = 0");
+    S3D_REQUIRE(H >= 2 && H <= 1024 && (uint64_t)2 * N < (1ull << 31), "sweep_draw_native: unsupported grid size H=%u or N=%u", H, N);
+    S3D_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= s3d_sweep_draw_native_workspace_size(H),
+                "sweep_draw_native: workspace too small or misaligned");
+    const uint32_t nbc = sweep_cell_blocks(H), H3 = H * H * H;
+    uint32_t* occ_bits = (uint32_t*)workspace;  // (16-byte aligned: the draw reads the masks as uint4)
+    int32_t* cnt = (int32_t*)(occ_bits + (size_t)nbc * 32);
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(k_sweep_partials, dim3(std::min<uint32_t>(nbc, 4096)), dim3(256), 0, st, density_grid, H3, tmp, cnt, occ_bits, nbc);
+    hipLaunchKernelGGL(k_sweep_scan, dim3(1), dim3(256), 0, st, cnt, nbc);
+    hipLaunchKernelGGL(k_sweep_draw_native, dim3(div_up<uint32_t>(N, kScanBlock)), dim3(256), 0, st, u_uniform, u_occupied,
+                       (const int32_t*)cnt, (const uint32_t*)occ_bits, nbc, N, H, bound, half_cell, noise_key, noise_step, cells, xyzs);
+    return check_launch("sweep_draw_native");
+}
+
+S3D_EXPORT uint32_t s3d_sweep_partial_stride(void) { return kSweepBlocks; }
+
+S3D_EXPORT int s3d_sweep_scatter_update(float* density_grid, uint32_t n_cells, const int32_t* cells, const void* sigma, int sigma_dtype,
+                                        uint32_t sigma_stride, uint32_t n, float density_scale, float decay, float* tmp,
+                                        float* partial, s3d_stream_t stream) {
+    S3D_REQUIRE(density_grid && n_cells > 0 && (n == 0 || (cells && sigma)) && tmp && partial, "sweep_scatter_update: null pointer");
+    S3D_REQUIRE(sigma_dtype == S3D_F32 || sigma_dtype == S3D_F16, "sweep_scatter_update: sigma dtype must be f32 or f16");
+    hipStream_t st = as_stream(stream);
+    launch_sweep_scatter(cells, sigma, sigma_dtype, sigma_stride, n, density_scale, tmp, st);
+    hipLaunchKernelGGL(k_sweep_update, dim3(sweep_update_blocks(n_cells)), dim3(256), 0, st, density_grid, (const float*)tmp, n_cells,
+                       decay, partial);
+    return check_launch("sweep_scatter_update");
+}
+
+S3D_EXPORT int s3d_sweep_tail(const float* partial, uint32_t cascades, uint32_t n_cells, float density_thresh,
+                              const int32_t* step_ring, const int32_t* local_step, int32_t* sweep_step, void* record,
+                              s3d_stream_t stream) {
+    S3D_REQUIRE(partial && cascades > 0 && n_cells > 0 && step_ring && local_step && record, "sweep_tail: null pointer");
+    S3D_REQUIRE(((uintptr_t)record & 3) == 0, "sweep_tail: record must be 4-byte aligned");
+    const float inv_n = 1.0f / (float)((uint64_t)cascades * n_cells);
+    hipLaunchKernelGGL(k_sweep_tail, dim3(1), dim3(256), 0, as_stream(stream), partial, cascades, kSweepBlocks,
+                       sweep_update_blocks(n_cells), inv_n, density_thresh, step_ring, local_step, sweep_step, (SweepRecord*)record);
+    return check_launch("sweep_tail");
+}
+
+S3D_EXPORT int s3d_packbits_record(const float* grid, uint32_t N, const void* record, uint8_t* bitfield, s3d_stream_t stream) {
+    if (N == 0) return S3D_OK;
+    S3D_REQUIRE(grid && bitfield && record, "packbits_record: null pointer");
+    S3D_REQUIRE(((uintptr_t)grid & 15) == 0 && ((uintptr_t)record & 3) == 0, "packbits_record: grid must be 16-byte aligned");
+    hipLaunchKernelGGL(k_packbits_record, dim3(stream_grid(N, 256)), dim3(256), 0, as_stream(stream), grid, N,
+                       (const SweepRecord*)record, bitfield);
+    return check_launch("packbits_record");
 }

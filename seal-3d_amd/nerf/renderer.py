@@ -56,7 +56,77 @@ def sample_pdf(bins, weights, n_samples, det=False):
     return bins_g[..., 0] + t * (bins_g[..., 1] - bins_g[..., 0])
 
 
+class _SweepState:
+    """Device words and the host landing buffer of the native occupancy sweep (`partial_grid_update_device`): the sweep's
+    step number (jitter counter), the sample-ring depth `local_step` as a device word, the 16-byte record of the tail launch
+    (seal3d_hip.h: s3d_sweep_tail), its pinned host copy and the event recorded behind that copy.  Not part of a model's
+    copies: a deep copy or a pickle starts without one."""
+
+    def __init__(self, dev):
+        self.device = dev
+        self.step = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.local_step = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.record = torch.zeros(4, dtype=torch.int32, device=dev)
+        self.host = torch.zeros(4, dtype=torch.int32).pin_memory()
+        self.event = torch.cuda.Event()
+        self.key = torch.initial_seed() & 0xFFFFFFFF
+        self.pending = None  # total_step of the update whose record is on its way to `host`
+
+    # (the model files a pending record before it is copied or pickled: NeRFRenderer.__getstate__)
+    def __deepcopy__(self, memo):
+        return None
+
+    def __reduce__(self):
+        return (type(None), ())
+
+
 class NeRFRenderer(nn.Module):
+    # mean_density / mean_count: plain host numbers, except between a native occupancy update and the first read after it —
+    # then the update's record is still on its way from the device and the read waits for its event (finish_extra_state)
+    _mean_density = 0
+    _mean_count = 0
+    _sweep = None
+
+    @property
+    def mean_density(self):
+        self._resolve_extra_state()
+        return self._mean_density
+
+    @mean_density.setter
+    def mean_density(self, value):
+        self._resolve_extra_state()
+        self._mean_density = value
+
+    @property
+    def mean_count(self):
+        self._resolve_extra_state()
+        return self._mean_count
+
+    @mean_count.setter
+    def mean_count(self, value):
+        self._resolve_extra_state()
+        self._mean_count = value
+
+    def __getstate__(self):
+        self._resolve_extra_state()  # a copy or a pickle carries the last update's numbers, not a record still on its way
+        return self.__dict__
+
+    def extra_state_pending(self):
+        """True while the last occupancy update's mean density / sample count have not been read back yet"""
+        return self._sweep is not None and self._sweep.pending is not None
+
+    def _resolve_extra_state(self):
+        st = self._sweep
+        if st is None or st.pending is None:
+            return
+        total_step, st.pending = st.pending, None
+        st.event.synchronize()
+        rec = st.host.numpy()
+        self._mean_density = float(rec.view(np.float32)[0])
+        if total_step > 0:
+            count = int(rec.view(np.uint32)[2]) | (int(rec.view(np.uint32)[3]) << 32)
+            self._mean_count = int(count / total_step)
+
     def __init__(self, bound=1, cuda_ray=False, density_scale=1, min_near=0.2, density_thresh=0.01, bg_radius=-1,
                  device_compaction=True, infer_batch_scale=1):
         super().__init__()
@@ -435,31 +505,37 @@ class NeRFRenderer(nn.Module):
 
     @torch.no_grad()
     def partial_grid_update_device(self, decay=0.95):
-        """density_grid <- EMA-max with fresh samples; returns mean(clamp(density_grid, 0)) as a device scalar"""
+        """density_grid <- EMA-max with fresh samples.  On the GPU (fp32 grid) everything up to the re-packed bitfield runs in
+        native launches without a host value in between, and the result is the device record of the update (mean density,
+        packing threshold, sample count of the last `local_step` steps; seal3d_hip.h: s3d_sweep_tail) for
+        `finish_extra_state`; the torch sequence returns mean(clamp(density_grid, 0)) as a device scalar."""
         dev = self.density_grid.device
         H3 = self.grid_size ** 3
         N = H3 // 4
         if dev.type == "cuda" and self.density_grid.dtype == torch.float32:
-            # native sweep (csrc/raymarching.hip): cells + jittered positions in one launch, scatter / EMA-max / mean in four —
-            # instead of ~40 elementwise torch kernels around the density query
+            # native sweep (csrc/raymarching.hip), per cascade: cells + jittered positions out of the two sorted streams in three
+            # launches (block counts, one-workgroup scan, draw), the density query, scatter + EMA-max in two; then one tail launch
+            # (mean, threshold, sample count) and the bitfield re-pack reading its threshold from the tail's record
             R = s3d_hip.RaymarchingBackend
-            if getattr(self, "_sweep_step", None) is None or self._sweep_step.device != dev:
-                self._sweep_step = torch.zeros(1, dtype=torch.int32, device=dev)
-                self._sweep_key = torch.initial_seed() & 0xFFFFFFFF
-            total = None
+            st = self._sweep
+            if st is None or st.device != dev:
+                st = self._sweep = _SweepState(dev)
+            if not torch.cuda.is_current_stream_capturing():
+                self.stage_extra_state()
+            tmp = torch.empty(H3, dtype=torch.float32, device=dev)
+            partial = torch.empty(self.cascade, R.sweep_partial_stride(), dtype=torch.float32, device=dev)
             for cas in range(self.cascade):
                 bound, hgs = self._cascade_geometry(cas)
                 grid = self.density_grid[cas]
-                csum = torch.cumsum(grid > 0, dim=0, dtype=torch.int32)
-                cells, xyzs = R.sweep_draw(self._sorted_uniform(N, dev), self._sorted_uniform(N, dev), csum, self.grid_size, bound,
-                                           hgs, self._sweep_key + cas, self._sweep_step)
+                cells, xyzs = R.sweep_draw_native(self._sorted_uniform(N, dev), self._sorted_uniform(N, dev), grid, self.grid_size,
+                                                  bound, hgs, tmp, st.key + cas, st.step)
                 sigma = self.density(xyzs)["sigma"].reshape(-1).detach()
                 if sigma.dtype not in (torch.float16, torch.float32):
                     sigma = sigma.float()
-                part = R.sweep_update(grid, cells, sigma.contiguous(), self.density_scale, decay,
-                                      self._sweep_step if cas == self.cascade - 1 else None)
-                total = part if total is None else total + part
-            return total / self.density_grid.numel()
+                R.sweep_scatter_update(grid, cells, sigma, self.density_scale, decay, tmp, partial[cas])
+            R.sweep_tail(partial, H3, self.density_thresh, self.step_counter, st.local_step, st.step, st.record)
+            R.packbits_record(self.density_grid, self.cascade * H3 // 8, st.record, self.density_bitfield)
+            return st.record
         tmp_grid = torch.full_like(self.density_grid, -1)
         for cas in range(self.cascade):
             # (uniform cells: a uniform morton index IS a uniform cell — the curve is a bijection of the H^3 grid)
@@ -479,8 +555,27 @@ class NeRFRenderer(nn.Module):
         return g.view(-1, 4096).sum(dim=1).sum() / g.numel()
 
     @torch.no_grad()
+    def stage_extra_state(self):
+        """hand the host counter `local_step` to the native update as a device word (one fill launch, no sync): called by
+        `partial_grid_update_device` itself when it runs eagerly, and by whoever replays a captured one, before the replay"""
+        if self._sweep is not None:
+            self._sweep.local_step.fill_(int(self.local_step))
+
+    @torch.no_grad()
     def finish_extra_state(self, mean_density_dev):
-        """bitfield re-pack + mean sample count from the device results of `partial_grid_update_device`: ONE host read"""
+        """Host bookkeeping after `partial_grid_update_device`.  Native update (its device record): the bitfield is already
+        re-packed; the record goes to pinned host memory with ONE asynchronous copy and an event behind it — no host read here.
+        `mean_density` / `mean_count` wait for that event when somebody reads them, and then return the exact numbers.
+        Torch sequence (a device scalar): bitfield re-pack + mean sample count with one host read."""
+        st = self._sweep
+        if st is not None and mean_density_dev is st.record:
+            self._resolve_extra_state()  # (an older record nobody asked for: file it before its buffer is reused)
+            st.host.copy_(st.record, non_blocking=True)
+            st.event.record()
+            st.pending = min(16, self.local_step)
+            self.iter_density += 1
+            self.local_step = 0
+            return
         total_step = min(16, self.local_step)
         counted = self.step_counter[:max(total_step, 1), 0].sum().float()  # < 2^24: exact
         mean_density, count_sum = torch.stack([mean_density_dev.float().reshape(()), counted]).tolist()

@@ -384,6 +384,7 @@ class GraphedTrainer(Trainer):
         self.graph_opt = None
         self.n_captures = 0
         self.budget = 0
+        self._budget_check_due = False  # an update's sample mean is still to be set against the budget (_maybe_update_extra_state)
         self.s_loss = None
         self.s_counter = torch.zeros(2, dtype=torch.int32, device=dev)
         # the graph itself files each step's loss and sample counter in 16-slot rings (seal3d_hip.h: s3d_step_ring_push)
@@ -520,10 +521,23 @@ class GraphedTrainer(Trainer):
         self.graph = self.graph_opt = None  # optimizer state tensors were replaced, mean_count may have moved: re-capture
         return out
 
+    def _check_budget(self):
+        """drop the captured step when the running mean sample count left the static budget's useful range: re-capture"""
+        mean = self.model.mean_count
+        if self.graph is not None and (mean * 1.1 > self.budget or mean * 2 < self.budget):
+            self.graph = None
+
     def _maybe_update_extra_state(self):
-        """steady state: the partial occupancy update replayed from its own HIP graph (~30 launches, two host syncs
-        less), then one host read for mean density / mean sample count.  First sweeps, models that extend
-        `update_extra_state`, and `graph_extra_state=False` keep the eager reference sequence."""
+        """steady state: the partial occupancy update replayed from its own HIP graph, with NO host read.  Per cascade: the
+        two sorted streams (torch), three launches for the draw, the density query, two for the scatter / EMA-max; then one
+        tail launch and the bitfield re-pack.  The update's mean density and sample count travel to pinned host memory behind
+        an event (NeRFRenderer.finish_extra_state), so the host keeps running ahead of the device across the update.
+        The sample-budget check that follows an update is therefore put off to the top of the NEXT update, when that event
+        has long completed: a re-capture decision lags by one update interval (16 steps).  The budget is 1.3 x the running
+        mean, and the check fires once 1.1 x the mean exceeds it or 2 x the mean falls below it, which leaves room for that
+        lag; a step whose samples exceed the budget drops the overflowing rays, as it always did.
+        First sweeps, models that extend `update_extra_state`, and `graph_extra_state=False` keep the eager reference
+        sequence."""
         from .renderer import NeRFRenderer
         model = self.model
         if not (model.cuda_ray and self.global_step % self.update_extra_interval == 0):
@@ -534,6 +548,9 @@ class GraphedTrainer(Trainer):
         plain = type(model).update_extra_state is NeRFRenderer.update_extra_state or epilogue is not None
         if not (self.graph_extra_state and plain and model.iter_density >= 16) or getattr(model, "dist_shard", None) is not None:
             return super()._maybe_update_extra_state()  # (sharded over the ranks: density queries split + all-gather)
+        if self._budget_check_due:
+            self._budget_check_due = False
+            self._check_budget()  # (the previous update's numbers: their event completed many steps ago)
         with torch.autocast("cuda", dtype=torch.float16, enabled=self.fp16):
             if self.ues_graph is None and not self.ues_warm:
                 mean = model.partial_grid_update_device()  # first time: eager (lazy initialisations, allocator warm-up)
@@ -543,6 +560,7 @@ class GraphedTrainer(Trainer):
                     self.ues_graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(self.ues_graph, capture_error_mode=_CAPTURE_MODE):
                         self.ues_mean = model.partial_grid_update_device()
+                model.stage_extra_state()
                 self.ues_graph.replay()
                 mean = self.ues_mean
             model.finish_extra_state(mean)
@@ -603,8 +621,11 @@ class GraphedTrainer(Trainer):
         model.train()
         if self._maybe_update_extra_state():
             self.s_cursor[0].zero_()  # (update_extra_state restarts the counter ring: local_step = 0)
-            if self.graph is not None and (model.mean_count * 1.1 > self.budget or model.mean_count * 2 < self.budget):
-                self.graph = None  # the running mean left the static budget's useful range: re-capture
+            pending = getattr(model, "extra_state_pending", None)
+            if pending is not None and pending():
+                self._budget_check_due = True  # (a native update's numbers are checked at the top of the next update)
+            else:
+                self._check_budget()
         self.global_step += 1
         if self.graph is None and model.mean_count <= 0:
             # no sample statistics yet (first 16 steps): eager step with the wrapper's host sync

@@ -30,6 +30,8 @@ EXPORTS = [
     "s3d_near_far_from_aabb", "s3d_sph_from_ray", "s3d_morton3D", "s3d_morton3D_invert", "s3d_mip_levels", "s3d_packbits",
     "s3d_march_rays_train_workspace_size", "s3d_march_rays_train",
     "s3d_sweep_draw", "s3d_sweep_update_workspace_size", "s3d_sweep_update",
+    "s3d_sweep_draw_native_workspace_size", "s3d_sweep_draw_native", "s3d_sweep_partial_stride", "s3d_sweep_scatter_update",
+    "s3d_sweep_tail", "s3d_packbits_record",
     "s3d_composite_rays_train_forward", "s3d_composite_rays_train_backward", "s3d_composite_rays_train_loss",
     "s3d_march_rays", "s3d_composite_rays", "s3d_compact_alive_workspace_size", "s3d_compact_alive",
     "s3d_grid_level_scales", "s3d_grid_encode_forward", "s3d_grid_encode_forward_pair", "s3d_grid_corner_indices", "s3d_grid_encode_backward",
@@ -79,7 +81,7 @@ def lib():
         for name in ("s3d_march_rays_train_workspace_size", "s3d_compact_alive_workspace_size",
                      "s3d_ffmlp_backward_workspace_size", "s3d_grid_encode_backward_workspace_size",
                      "s3d_grid_encode_backward_control_size", "s3d_l1_pair_workspace_size",
-                     "s3d_sweep_update_workspace_size", "s3d_vm_backward_bins_workspace_size", "s3d_vm_backward_stage_bytes",
+                     "s3d_sweep_update_workspace_size", "s3d_sweep_draw_native_workspace_size", "s3d_vm_backward_bins_workspace_size", "s3d_vm_backward_stage_bytes",
                      "s3d_weighted_abs_sum_workspace_size", "s3d_background_backward_workspace_size",
                      "s3d_vm_background_backward_workspace_size"):
             getattr(l, name).restype = C.c_size_t
@@ -323,6 +325,68 @@ class RaymarchingBackend:
                                       _f(density_scale), _f(decay), _p(ws), C.c_size_t(ws.numel()), _p(out), _p(step_counter),
                                       _stream()), "sweep_update")
         return out
+
+    @staticmethod
+    def sweep_draw_native(u_uniform, u_occupied, density_grid, H, bound, half_cell, tmp, noise_key=0, noise_step=None):
+        """sweep_draw with the occupied cells found in per-block counts + bit masks of density_grid > 0 instead of a prefix array;
+        also leaves tmp [H^3] = -1 (seal3d_hip.h).  Returns cells [2N] int32 and xyzs [2N, 3]."""
+        _need(u_uniform, torch.float64, "u_uniform"); _need(u_occupied, torch.float64, "u_occupied")
+        _need(density_grid, torch.float32, "density_grid"); _need(tmp, torch.float32, "tmp")
+        H3, dev = int(H) ** 3, density_grid.device
+        N = u_uniform.numel()
+        if u_occupied.numel() != N or density_grid.numel() != H3 or tmp.numel() != H3:
+            raise RuntimeError("sweep_draw_native: u_uniform / u_occupied are [N], density_grid and tmp [H^3]")
+        if noise_step is not None:
+            _need(noise_step, torch.int32, "noise_step")
+        ws = _ws.get(lib().s3d_sweep_draw_native_workspace_size(_u(H)), dev)
+        cells = torch.empty(2 * N, dtype=torch.int32, device=dev)
+        xyzs = torch.empty(2 * N, 3, dtype=torch.float32, device=dev)
+        _check(lib().s3d_sweep_draw_native(_p(u_uniform), _p(u_occupied), _p(density_grid), _u(N), _u(H), _f(bound), _f(half_cell),
+                                           _u(int(noise_key) & 0xFFFFFFFF), _p(noise_step), _p(tmp), _p(cells), _p(xyzs), _p(ws),
+                                           C.c_size_t(ws.numel()), _stream()), "sweep_draw_native")
+        return cells, xyzs
+
+    @staticmethod
+    def sweep_partial_stride():
+        return int(lib().s3d_sweep_partial_stride())
+
+    @staticmethod
+    def sweep_scatter_update(density_grid, cells, sigma, density_scale, decay, tmp, partial):
+        """EMA-max update of one cascade's grid from (cells, sigma) through tmp (which the draw left at -1); sigma is a 1-D fp16 /
+        fp32 tensor of any stride; partial [sweep_partial_stride()] receives the block sums of max(grid, 0) (seal3d_hip.h)"""
+        _need(density_grid, torch.float32, "density_grid"); _need(cells, torch.int32, "cells")
+        _need(tmp, torch.float32, "tmp"); _need(partial, torch.float32, "partial")
+        if sigma.dtype not in (torch.float16, torch.float32) or sigma.dim() != 1 or sigma.numel() != cells.numel() or not sigma.is_cuda:
+            raise RuntimeError("sweep_scatter_update: sigma must be a 1-D fp16 / fp32 GPU tensor, one per cell sample")
+        if tmp.numel() != density_grid.numel() or partial.numel() < RaymarchingBackend.sweep_partial_stride():
+            raise RuntimeError("sweep_scatter_update: tmp is [n_cells], partial [sweep_partial_stride()]")
+        stride = sigma.stride(0) if sigma.numel() > 1 else 1
+        if stride < 1:
+            raise RuntimeError("sweep_scatter_update: sigma must have a positive stride")
+        _check(lib().s3d_sweep_scatter_update(_p(density_grid), _u(density_grid.numel()), _p(cells), C.c_void_p(sigma.data_ptr()),
+                                              C.c_int(_dt(sigma)), _u(stride), _u(cells.numel()), _f(density_scale), _f(decay),
+                                              _p(tmp), _p(partial), _stream()), "sweep_scatter_update")
+
+    @staticmethod
+    def sweep_tail(partial, n_cells, density_thresh, step_ring, local_step, sweep_step, record):
+        """mean / threshold / sample count of an update into `record` (int32 [4], 16 bytes; seal3d_hip.h)"""
+        _need(partial, torch.float32, "partial"); _need(step_ring, torch.int32, "step_ring")
+        _need(local_step, torch.int32, "local_step"); _need(record, torch.int32, "record")
+        if partial.dim() != 2 or partial.shape[1] != RaymarchingBackend.sweep_partial_stride() or step_ring.shape != (16, 2) \
+                or record.numel() != 4:
+            raise RuntimeError("sweep_tail: partial is [cascades, sweep_partial_stride()], step_ring [16, 2], record int32 [4]")
+        if sweep_step is not None:
+            _need(sweep_step, torch.int32, "sweep_step")
+        _check(lib().s3d_sweep_tail(_p(partial), _u(partial.shape[0]), _u(n_cells), _f(density_thresh), _p(step_ring),
+                                    _p(local_step), _p(sweep_step), _p(record), _stream()), "sweep_tail")
+
+    @staticmethod
+    def packbits_record(grid, N, record, bitfield):
+        """packbits with the threshold of a sweep_tail record (no host value in between)"""
+        _need(grid, torch.float32, "grid"); _need(record, torch.int32, "record"); _need(bitfield, torch.uint8, "bitfield")
+        if grid.numel() != 8 * int(N) or bitfield.numel() < int(N) or record.numel() != 4:
+            raise RuntimeError("packbits_record: grid holds 8 N cells, bitfield N bytes, record int32 [4]")
+        _check(lib().s3d_packbits_record(_p(grid), _u(N), _p(record), _p(bitfield), _stream()), "packbits_record")
 
     @staticmethod
     def sph_from_ray(rays_o, rays_d, radius, N, coords):
