@@ -217,6 +217,14 @@ def _need(t, dtype, name):
         raise RuntimeError(f"{name} must be {dtype}, got {t.dtype}")
 
 
+def _background_workspace(size_fn, N, device, found_inf):
+    """both background backward bindings: found_inf's dtype check, the workspace query -> (uint8 workspace on `device`, its c_size_t size)"""
+    if found_inf is not None:
+        _need(found_inf, torch.float32, "found_inf")
+    nb = int(size_fn(_u(N)))
+    return torch.empty(max(nb, 1), dtype=torch.uint8, device=device), C.c_size_t(nb)
+
+
 class _Workspace:
     """Per-device, per-stream scratch owned by the binding (grown on demand, reused).  While the stream is being captured
     into a HIP graph the scratch is a plain temporary instead: a cached tensor would come out of THAT graph's private memory
@@ -1080,15 +1088,22 @@ class NgpHeadBackend:
                                          _p(out_rgb), _p(out_depth), _stream()), "bg_targets_rays")
 
     @staticmethod
+    def _background_args(sph, dirs, table, offsets, w0, w1, rgb, what):
+        """shape / dtype checks shared by background_forward and background_backward; returns N"""
+        for t, n in ((sph, "sph"), (dirs, "dirs"), (w0, "w0"), (w1, "w1"), (rgb, "rgb")):
+            _need(t, torch.float32, n)
+        _need(offsets, torch.int32, "offsets")
+        N = sph.shape[0]
+        if (sph.shape != (N, 2) or dirs.shape != (N, 3) or rgb.shape != (N, 3) or offsets.numel() != 5 or table.dim() != 2
+                or table.shape[1] != 2 or w0.shape != (64, 24) or w1.shape != (3, 64)):
+            raise RuntimeError(f"{what}: sph [N,2], dirs / rgb [N,3], offsets [5], table [rows,2], w0 [64,24], w1 [3,64]")
+        return N
+
+    @staticmethod
     def background_forward(sph, dirs, table, offsets, S, H, w0, w1, rgb, features=None):
         """the background model (seal3d_hip.h: s3d_background_forward): sph [N,2], dirs [N,3] fp32, table [rows,2] fp32/fp16,
         offsets [5] int32, w0 [64,24] / w1 [3,64] fp32 (read as fp16) -> rgb [N,3] fp32 (+ the grid features [4,N,2] of the table's dtype)"""
-        N = sph.shape[0]
-        _need(sph, torch.float32, "sph"); _need(dirs, torch.float32, "dirs"); _need(rgb, torch.float32, "rgb")
-        _need(w0, torch.float32, "w0"); _need(w1, torch.float32, "w1"); _need(offsets, torch.int32, "offsets")
-        if (sph.shape != (N, 2) or dirs.shape != (N, 3) or rgb.shape != (N, 3) or offsets.numel() != 5 or table.dim() != 2
-                or table.shape[1] != 2 or w0.shape != (64, 24) or w1.shape != (3, 64)):
-            raise RuntimeError("background_forward: sph [N,2], dirs / rgb [N,3], offsets [5], table [rows,2], w0 [64,24], w1 [3,64]")
+        N = NgpHeadBackend._background_args(sph, dirs, table, offsets, w0, w1, rgb, "background_forward")
         if features is not None and (features.dtype != table.dtype or features.shape != (4, N, 2)):
             raise RuntimeError("background_forward: features [4,N,2] of the table's dtype")
         _check(lib().s3d_background_forward(_p(sph), _p(dirs), _p(table), _p(offsets), _u(N), _f(S), _u(H), C.c_int(_dt(table)),
@@ -1097,24 +1112,16 @@ class NgpHeadBackend:
     @staticmethod
     def background_backward(grad_rgb, rgb, sph, dirs, table, offsets, S, H, w0, w1, grad_table, grad_w0, grad_w1, found_inf=None):
         """backward of background_forward: ADDS the table gradient into grad_table (the table's shape and dtype; None: no table
-        gradient), overwrites
-        grad_w0 [64,24] / grad_w1 [3,64] (fp32); found_inf (optional fp32 [1]) raised for a non-finite gradient"""
-        N = sph.shape[0]
-        for t, n in ((grad_rgb, "grad_rgb"), (rgb, "rgb"), (sph, "sph"), (dirs, "dirs"), (grad_w0, "grad_w0"), (grad_w1, "grad_w1")):
-            _need(t, torch.float32, n)
-        _need(w0, torch.float32, "w0"); _need(w1, torch.float32, "w1"); _need(offsets, torch.int32, "offsets")
-        if (grad_rgb.shape != (N, 3) or rgb.shape != (N, 3) or dirs.shape != (N, 3) or offsets.numel() != 5
-                or (grad_table is not None and (grad_table.shape != table.shape or grad_table.dtype != table.dtype))
-                or table.dim() != 2 or table.shape[1] != 2
-                or grad_w0.shape != (64, 24) or grad_w1.shape != (3, 64) or w0.shape != (64, 24) or w1.shape != (3, 64)):
-            raise RuntimeError("background_backward: shapes as background_forward, grad_table like table, grad_w0 [64,24], grad_w1 [3,64]")
-        if found_inf is not None:
-            _need(found_inf, torch.float32, "found_inf")
-        nb = int(lib().s3d_background_backward_workspace_size(_u(N)))
-        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=sph.device)
+        gradient), overwrites grad_w0 [64,24] / grad_w1 [3,64] (fp32); found_inf (optional fp32 [1]) raised for a non-finite gradient"""
+        N = NgpHeadBackend._background_args(sph, dirs, table, offsets, w0, w1, rgb, "background_backward")
+        _need(grad_rgb, torch.float32, "grad_rgb"); _need(grad_w0, torch.float32, "grad_w0"); _need(grad_w1, torch.float32, "grad_w1")
+        if (grad_rgb.shape != (N, 3) or grad_w0.shape != (64, 24) or grad_w1.shape != (3, 64)
+                or (grad_table is not None and (grad_table.shape != table.shape or grad_table.dtype != table.dtype))):
+            raise RuntimeError("background_backward: grad_rgb [N,3], grad_table like table, grad_w0 [64,24], grad_w1 [3,64]")
+        ws, nb = _background_workspace(lib().s3d_background_backward_workspace_size, N, sph.device, found_inf)
         _check(lib().s3d_background_backward(_p(grad_rgb), _p(rgb), _p(sph), _p(dirs), _p(table), _p(offsets), _u(table.shape[0]), _u(N),
                                              _f(S), _u(H), C.c_int(_dt(table)), _p(w0), _p(w1), _p(grad_table), _p(grad_w0),
-                                             _p(grad_w1), _p(found_inf), _p(ws), C.c_size_t(nb), _stream()), "background_backward")
+                                             _p(grad_w1), _p(found_inf), _p(ws), nb, _stream()), "background_backward")
 
     _l1_ws = {}
 
@@ -1428,18 +1435,14 @@ class VmBackend:
         """backward of background_forward: ADDS the plane gradient into grad_plane (fp32, the plane's shape; None: no plane
         gradient), overwrites grad_w0 [64,23] / grad_w1 [3,64] (fp32); found_inf (optional fp32 [1]) raised for a non-finite gradient"""
         N, R, H, W = VmBackend._background_args(sph, dirs, plane, w0, w1, rgb, "vm background_backward")
-        for t, n in ((grad_rgb, "grad_rgb"), (grad_w0, "grad_w0"), (grad_w1, "grad_w1")):
-            _need(t, torch.float32, n)
+        _need(grad_rgb, torch.float32, "grad_rgb"); _need(grad_w0, torch.float32, "grad_w0"); _need(grad_w1, torch.float32, "grad_w1")
         if (grad_rgb.shape != (N, 3) or grad_w0.shape != (64, 23) or grad_w1.shape != (3, 64)
                 or (grad_plane is not None and (grad_plane.shape != plane.shape or grad_plane.dtype != torch.float32))):
             raise RuntimeError("vm background_backward: grad_rgb [N,3], grad_plane like plane, grad_w0 [64,23], grad_w1 [3,64]")
-        if found_inf is not None:
-            _need(found_inf, torch.float32, "found_inf")
-        nb = int(lib().s3d_vm_background_backward_workspace_size(_u(N)))
-        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=sph.device)
+        ws, nb = _background_workspace(lib().s3d_vm_background_backward_workspace_size, N, sph.device, found_inf)
         _check(lib().s3d_vm_background_backward(_p(grad_rgb), _p(rgb), _p(sph), _p(dirs), _p(plane), _u(R), _u(H), _u(W), _p(w0), _p(w1),
-                                                _u(N), _p(grad_plane), _p(grad_w0), _p(grad_w1), _p(found_inf), _p(ws),
-                                                C.c_size_t(nb), _stream()), "vm_background_backward")
+                                                _u(N), _p(grad_plane), _p(grad_w0), _p(grad_w1), _p(found_inf), _p(ws), nb,
+                                                _stream()), "vm_background_backward")
 
     @staticmethod
     def aabb_normalize(x, aabb, out):

@@ -331,3 +331,182 @@ def test_graphed_seal_bbox_finetune_and_proxy_truth_with_background(hip, S):
     hist = [float(tr.train_step(ro, rd)) for _ in range(24)]
     assert tr.n_captures >= 1 and np.isfinite(hist).all(), hist
     assert not torch.equal(student.encoder_bg.embeddings.detach(), bg0)
+
+
+# ------------------------------------------------------------------------------------------------ edge shapes, frozen table, stride loop
+# coordinates on the border exactly (x01 = 0 or 1 is inside), at the centre, and outside [-1, 1] on one axis or both; 1.0000001
+# is the fp32 neighbour of 1 whose (x + 1) rounds back to 2: inside after normalisation
+_SPECIAL = [[1.0, -1.0], [-1.0, 1.0], [0.0, 0.0], [1.05, -1.02], [-1.0, -1.0], [1.0, 1.0], [1.0, 0.0], [0.0, -1.0], [1.01, 0.3],
+            [-0.2, -1.05], [-1.03, 1.04], [1.0, 1.05], [-1.05, -1.0], [0.999, 1.0], [1.02, 1.0], [1.0000001, 0.5], [-3.25, 0.5]]
+GUARD, GUARD_VALUE = 256, 1234.0  # (exact in fp16)
+
+
+def _small_table_net(log2_hashmap_size=10):
+    """the background network on a small table (the dense 17 x 17 level + three hashed levels of 2^10 rows, so rays collide on
+    every level): cheap to guard, and every row is reached"""
+    from encoding import get_encoder
+    net = _net()
+    enc, _ = get_encoder("hashgrid", input_dim=2, num_levels=4, log2_hashmap_size=log2_hashmap_size, desired_resolution=2048)
+    enc.embeddings.data.copy_(_seeded(enc.embeddings.shape, 77, -0.5, 0.5))
+    net.encoder_bg = enc.cuda()
+    return net
+
+
+def _torch_path(net, sph, rd, g, dt):
+    """(rgb, dW0, dW1, d table) of background()'s torch op sequence under fp16 autocast.  fp32 table: the encoder is called
+    outside autocast, where it reads the parameter itself, and the rest of the sequence under it"""
+    from nerf.network import _run_mlp
+    net.zero_grad()
+    if dt == torch.float16:
+        rgb = _bg(net, sph, rd, False)
+    else:
+        feat = net.encoder_bg(sph)
+        with torch.autocast("cuda", dtype=torch.float16):
+            rgb = torch.sigmoid(_run_mlp(net.bg_net, torch.cat([net.encoder_dir(rd), feat], dim=-1)))
+    rgb.float().backward(g)
+    return (rgb.detach().float(), net.bg_net[0].weight.grad.clone(), net.bg_net[1].weight.grad.clone(),
+            net.encoder_bg.embeddings.grad.float().clone())
+
+
+class _Guarded:
+    """the table and a zeroed table gradient of dtype `dt`, each between guard words"""
+
+    def __init__(self, net, dt):
+        emb = net.encoder_bg.embeddings.detach()
+        n = emb.numel()
+        self.bufs = [torch.full((GUARD + n + GUARD,), GUARD_VALUE, dtype=dt, device="cuda") for _ in range(2)]
+        self.table, self.grad = (b[GUARD:GUARD + n].view(emb.shape) for b in self.bufs)
+        self.table.copy_(emb)
+        self.grad.zero_()
+
+    def intact(self):
+        return all(bool((b[:GUARD] == GUARD_VALUE).all()) and bool((b[-GUARD:] == GUARD_VALUE).all()) for b in self.bufs)
+
+
+def _fused_pair(hip, net, sph, rd, g, table, grad_table):
+    """(rgb, dW0, dW1) of the two fused launches on `table`; the table gradient is ADDED into grad_table"""
+    enc = net.encoder_bg
+    S = float(np.log2(enc.per_level_scale))
+    w0, w1 = net.bg_net[0].weight.detach(), net.bg_net[1].weight.detach()
+    N = sph.shape[0]
+    rgb = torch.empty(N, 3, device="cuda")
+    gw0, gw1 = torch.empty(64, 24, device="cuda"), torch.empty(3, 64, device="cuda")
+    hip.NgpHeadBackend.background_forward(sph, rd, table, enc.offsets, S, enc.base_resolution, w0, w1, rgb)
+    hip.NgpHeadBackend.background_backward(g, rgb, sph, rd, table, enc.offsets, S, enc.base_resolution, w0, w1, grad_table, gw0, gw1)
+    torch.cuda.synchronize()
+    return rgb, gw0, gw1
+
+
+def _assert_paths_agree(got, want, what=""):
+    """the bounds of test_fused_forward_backward_vs_fixture_and_torch_path: the two paths share their fp16 roundings and differ in
+    summation order only: 1e-3 on the colour, 1 % of the largest entry (+ 1e-4) on each gradient"""
+    print(what, "colour max diff", (got[0] - want[0]).abs().max().item())
+    for name, a, b in zip(("dW0", "dW1", "d table"), got[1:], want[1:]):
+        print(what, name, "max diff", (a - b).abs().max().item(), "of max", b.abs().max().item())
+    assert (got[0] - want[0]).abs().max().item() <= 1e-3
+    for a, b in zip(got[1:], want[1:]):
+        assert (a - b).abs().max().item() <= 1e-2 * b.abs().max().item() + 1e-4
+
+
+def _outside(sph):
+    """[N] mask of the rows outside [0,1]^2 after the kernels' normalisation (x + 1) * 0.5 in fp32"""
+    x01 = (sph + 1.0) * 0.5
+    return ((x01 < 0) | (x01 > 1)).any(1)
+
+
+def _touched_rows(hip, net, sph):
+    """[rows] mask of the table rows a corner of some inside ray lands on (the grid encoder's own index kernel)"""
+    enc = net.encoder_bg
+    N = sph.shape[0]
+    cidx = torch.empty(N, 4, 4, dtype=torch.int32, device="cuda")
+    hip.GridBackend.grid_corner_indices(((sph + 1.0) * 0.5).cuda().contiguous(), enc.offsets, cidx, N, 2, 2, 4,
+                                        float(np.log2(enc.per_level_scale)), enc.base_resolution, 0, False)
+    rows = cidx.long() + enc.offsets[:4].long().view(1, 4, 1)
+    mask = torch.zeros(enc.embeddings.shape[0], dtype=torch.bool, device="cuda")
+    mask[rows[~_outside(sph).cuda()].reshape(-1)] = True
+    return mask
+
+
+@pytest.mark.parametrize("dt", [torch.float16, torch.float32], ids=["fp16", "fp32"])
+def test_edge_shapes_against_the_torch_path(hip, dt):
+    """N around the wave and block sizes, coordinates on and around the border, both table dtypes: the fused pair against the
+    torch path, guard words around the table and its gradient, exactly zero gradient on every row no inside ray reaches and from
+    the outside rays alone, and exactly the colour of an all-zero table for a ray outside [0,1]^2 after normalisation"""
+    net = _small_table_net()
+    for N in (1, 63, 64, 65, 257):
+        sph = _seeded((N, 2), 10 + N, -1.05, 1.05)
+        k = min(N, len(_SPECIAL))
+        sph[:k] = torch.tensor(_SPECIAL[:k])
+        rd = torch.nn.functional.normalize(_seeded((N, 3), 20 + N, -1, 1), dim=-1).cuda()
+        g = _seeded((N, 3), 30 + N, -1, 1).cuda()
+        want = _torch_path(net, sph.cuda(), rd, g, dt)
+        mem = _Guarded(net, dt)
+        rgb, gw0, gw1 = _fused_pair(hip, net, sph.cuda(), rd, g, mem.table, mem.grad)
+        assert mem.intact(), (dt, N)
+        _assert_paths_agree((rgb, gw0, gw1, mem.grad.float()), want, f"table {dt} N {N}:")
+        # rows no inside ray reaches: exactly zero
+        mask = _touched_rows(hip, net, sph)
+        assert bool((mem.grad[~mask] == 0).all()) and float(mem.grad.float().abs().sum()) > 0
+        outside = _outside(sph).cuda()
+        assert int(outside.sum()) >= (2 if N > len(_SPECIAL) else 0)
+        # outside rows: exactly the colour of an all-zero table ...
+        zero = _Guarded(net, dt)
+        zero.table.zero_()
+        rgb0, _, _ = _fused_pair(hip, net, sph.cuda(), rd, g, zero.table, None)
+        assert zero.intact() and bool((zero.grad == 0).all())
+        assert torch.equal(rgb[outside], rgb0[outside])
+        assert not torch.equal(rgb[~outside], rgb0[~outside])
+        # ... and, run by themselves, exactly nothing added to the gradient table
+        if bool(outside.any()):
+            alone = _Guarded(net, dt)
+            _fused_pair(hip, net, sph.cuda()[outside].contiguous(), rd[outside].contiguous(), g[outside].contiguous(), alone.table,
+                        alone.grad)
+            assert alone.intact() and bool((alone.grad == 0).all())
+
+
+def test_frozen_table_gets_no_scatter(hip, monkeypatch):
+    net = _net()
+    sph = _seeded((300, 2), 5, -1.05, 1.05).cuda()
+    rd = torch.nn.functional.normalize(_seeded((300, 3), 6, -1, 1), dim=-1).cuda()
+    g = _seeded((300, 3), 7, -1, 1).cuda()
+    _bg(net, sph, rd, True).float().backward(g)
+    want = [net.bg_net[0].weight.grad.clone(), net.bg_net[1].weight.grad.clone()]
+    assert float(net.encoder_bg.embeddings.grad.abs().sum()) > 0
+    net.zero_grad()
+    net.encoder_bg.embeddings.requires_grad_(False)
+    seen = []
+    real = hip.NgpHeadBackend.background_backward
+    monkeypatch.setattr(hip.NgpHeadBackend, "background_backward",
+                        staticmethod(lambda *a, **k: (seen.append(a[10]), real(*a, **k))[1]))
+    _bg(net, sph, rd, True).float().backward(g)
+    assert seen == [None] and net.encoder_bg.embeddings.grad is None
+    assert torch.equal(net.bg_net[0].weight.grad, want[0]) and torch.equal(net.bg_net[1].weight.grad, want[1])
+
+
+STRIDE_N = 2048 * 64 + 65  # the backward grid is capped at 2,048 one-wave workgroups: workgroup 0 and one partial wave go round twice
+
+
+def test_backward_stride_loop_second_trip(hip):
+    """The backward's stride loop beyond its first trip: fused against the torch path, and against the sum of two fused calls on
+    the two halves of the batch (one trip each: the same addends in another order), both within 1 % of the largest entry + 1e-4.
+    On an fp32 table: 131,137 rays put ~1,800 addends on each of the 289 rows of the coarsest level, and an fp16 atomic rounds the
+    running sum at every one of them — ~1,800 roundings of up to half an fp16 ulp of a sum of order 1 walk ~1e-2 away in either
+    path, which is that bound; in fp32 the same walk is ~1e-6 and the bound is about the kernels."""
+    net = _small_table_net()
+    N, dt = STRIDE_N, torch.float32
+    sph = _seeded((N, 2), 41, -1.02, 1.02).cuda()
+    rd = torch.nn.functional.normalize(_seeded((N, 3), 42, -1, 1), dim=-1).cuda()
+    g = _seeded((N, 3), 43, -1, 1).cuda()
+    want = _torch_path(net, sph, rd, g, dt)
+    mem = _Guarded(net, dt)
+    rgb, gw0, gw1 = _fused_pair(hip, net, sph, rd, g, mem.table, mem.grad)
+    assert mem.intact()
+    _assert_paths_agree((rgb, gw0, gw1, mem.grad), want, f"N {N}:")
+    halves = _Guarded(net, dt)
+    h = N // 2
+    parts = [_fused_pair(hip, net, sph[s].contiguous(), rd[s].contiguous(), g[s].contiguous(), halves.table, halves.grad)
+             for s in (slice(0, h), slice(h, N))]
+    assert torch.equal(torch.cat([p[0] for p in parts]), rgb)
+    for name, a, b in (("dW0", gw0, parts[0][1] + parts[1][1]), ("dW1", gw1, parts[0][2] + parts[1][2]), ("d table", mem.grad, halves.grad)):
+        print("one call vs two halves:", name, "max diff", (a - b).abs().max().item(), "of max", b.abs().max().item())
+        assert (a - b).abs().max().item() <= 1e-2 * b.abs().max().item() + 1e-4

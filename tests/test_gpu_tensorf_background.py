@@ -1,4 +1,4 @@
-"""The TensoRF background model on the MI355X: the fused kernels (csrc/background.hip: k_vm_bg_forward / k_vm_bg_backward) against
+"""The TensoRF background model on the MI355X: the fused kernels (csrc/background.hip: the head's kernels on VmSource) against
 the reference fixture (tests/golden/tensorf_background.npz) and against the network's own torch path, the plane's edges, and the
 model inside the eager and graph-replayed training steps, Seal fine-tuning and rendering."""
 import os
@@ -231,6 +231,33 @@ def test_frozen_plane_gets_no_scatter(hip, monkeypatch):
     _bg(net, sph, rd, True).float().backward(g)
     assert seen == [None] and net.bg_mat.grad is None
     assert torch.equal(net.bg_net[0].weight.grad, want[0]) and torch.equal(net.bg_net[1].weight.grad, want[1])
+
+
+STRIDE_N = 2048 * 64 + 65  # the backward grid is capped at 2,048 one-wave workgroups: workgroup 0 and one partial wave go round twice
+
+
+def test_backward_stride_loop_second_trip(hip):
+    """The backward's stride loop beyond its first trip: fused against the torch path, and against the sum of two fused calls on
+    the two halves of the batch (one trip each: the same addends in another order), within 1 % of the largest entry + 1e-4"""
+    net = _net((20, 12))
+    N = STRIDE_N
+    sph = _seeded((N, 2), 41, -1.05, 1.05).cuda()
+    rd = F.normalize(_seeded((N, 3), 42, -1, 1), dim=-1).cuda()
+    g = _seeded((N, 3), 43, -1, 1).cuda()
+    outs = _both_paths(net, sph, rd, g)
+    _assert_paths_agree(outs, f"N {N}:")
+    h = N // 2
+    parts = []
+    for s in (slice(0, h), slice(h, N)):
+        net.zero_grad()
+        rgb = _bg(net, sph[s].contiguous(), rd[s].contiguous(), True)
+        rgb.float().backward(g[s].contiguous())
+        parts.append((rgb.detach().float(),) + tuple(p.grad.float().clone() for p in _bg_params(net)))
+    assert torch.equal(torch.cat([p[0] for p in parts]), outs[True][0])
+    for name, a, b0, b1 in zip(("dW0", "dW1", "d bg_mat"), outs[True][1:], parts[0][1:], parts[1][1:]):
+        b = b0 + b1
+        print("one call vs two halves:", name, "max diff", (a - b).abs().max().item(), "of max", b.abs().max().item())
+        assert (a - b).abs().max().item() <= 1e-2 * b.abs().max().item() + 1e-4
 
 
 # ------------------------------------------------------------------------------------------------ trainers
