@@ -158,13 +158,18 @@ int s3d_composite_rays_train_backward(const float* grad_weights_sum, const float
  * walks its samples again for grad_sigmas / grad_rgbs; the loss value is summed by a one-workgroup launch behind it in
  * s3d_bg_mse_forward's order (two launches instead of three, the second off the backward's critical data).  Every output equals
  * the three-call sequence (wave-per-ray paths) bit for bit.  gt [N,3], bg_rgb = 3 HOST floats, gt_depth [N] or NULL (value-only
- * depth term), grad_image [N,3] / grad_weights_sum [N]: optional outputs (both or neither), workspace: 4N floats (scratch). */
+ * depth term), grad_image [N,3] / grad_weights_sum [N]: optional outputs (both or neither), workspace: 4N floats (scratch).
+ * loss = NULL (also s3d_composite_rays_train_loss_bg): the one-workgroup launch is left out; the per-ray terms stay in `workspace`
+ * until s3d_loss_terms_reduce, or a step tail of s3d_grid_encode_backward_adam_tail, sums them in the same order. */
 int s3d_composite_rays_train_loss(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
                                   uint32_t M, uint32_t N, float T_thresh, const float* gt, const float* bg_rgb,
                                   const float* grad_loss, const float* gt_depth, float depth_weight,
                                   float* weights_sum, float* depth, float* image, float* grad_sigmas, float* grad_rgbs,
                                   float* grad_image, float* grad_weights_sum, float* loss, float* workspace,
                                   s3d_stream_t stream);
+/* the one-workgroup sum of s3d_composite_rays_train_loss's per-ray terms on its own: workspace = that call's, with_depth = it
+ * was given a gt_depth.  *loss = sum(sq) / 3N (+ depth_weight * sum(dabs) / N). */
+int s3d_loss_terms_reduce(const float* workspace, uint32_t N, int with_depth, float depth_weight, float* loss, s3d_stream_t stream);
 
 /* raymarching.h:17 void march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, dt_gamma,
  *                       max_steps, C, H, grid, nears, fars, xyzs, dirs, deltas, noises)
@@ -291,6 +296,52 @@ int s3d_grid_encode_backward_adam(const void* grad, const float* inputs, const v
                                   float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int dtype,
                                   void* workspace, size_t workspace_bytes, float bound, const int32_t* n_valid, float* found_inf,
                                   void* control, size_t control_bytes, const s3d_grid_adam* adam, int* applied, s3d_stream_t stream);
+
+/* s3d_grid_encode_backward_adam with a STEP TAIL: small work of the training step that is independent of the table's backward
+ * and would otherwise queue behind it as four launches of 4 - 10 us each.  It runs inside the backward's own two binned launches:
+ *  (a) S3D_TAIL_WGRAD_REDUCE  s3d_ffmlp_wgrad_reduce_pair's work (its arguments: *_a, *_b; workspace_a = NULL: none) and
+ *  (b) S3D_TAIL_LOSS          s3d_loss_terms_reduce's work (loss_workspace = NULL: none) as extra workgroups of the scatter
+ *                             launch — both are complete before the accumulate launch starts;
+ *  (c) S3D_TAIL_ADAM          s3d_adam_step_multi's work on `tensors` (host array, at most four non-empty ones), with the step /
+ *                             grad_scale / lr_scale of `adam`, the call's found_inf and the skip decision of the table's own
+ *                             update (found_inf at entry, or-ed with the poison words of every level), and
+ *  (d) S3D_TAIL_EPILOGUE      s3d_scaler_update on the call's found_inf (scale = NULL: none), followed by s3d_step_ring_push
+ *                             (counter = NULL: none), by the workgroup of the accumulate launch that finishes last.
+ * Same arithmetic and order of additions as the separate entry points: every value is bit-identical.  *tail_applied (host)
+ * receives the S3D_TAIL_* bits of the parts that ran there.  A call that falls back (*applied = 0) issues (a) and (b) as their
+ * ordinary launches in front of the backward and reports no bit; the caller then runs (c) and (d) as it would without a tail.
+ * (d) is applied only together with every tensor of (c): it clears found_inf and advances the step count, so the caller hands
+ * it in only when no other update of the step is left to launch. */
+enum { S3D_TAIL_WGRAD_REDUCE = 1, S3D_TAIL_LOSS = 2, S3D_TAIL_ADAM = 4, S3D_TAIL_EPILOGUE = 8 };
+struct s3d_adam_tensor;
+typedef struct s3d_step_tail {
+    const void* workspace_a; uint32_t B_a, input_dim_a, hidden_dim_a, num_layers_a; uint16_t* grad_weights_a; int accumulate_a; float* found_inf_a;
+    const void* workspace_b; uint32_t B_b, input_dim_b, hidden_dim_b, num_layers_b; uint16_t* grad_weights_b; int accumulate_b; float* found_inf_b;
+    const float* loss_workspace; /* [3N squared errors | N depth terms] of s3d_composite_rays_train_loss(loss = NULL) */
+    uint32_t loss_N;
+    int loss_with_depth;
+    float loss_depth_weight;
+    float* loss;
+    const struct s3d_adam_tensor* tensors;
+    int32_t n_tensors;
+    float* scale;
+    int32_t* growth_tracker;
+    float growth_factor, backoff_factor;
+    int32_t growth_interval;
+    float* adam_step;
+    const float* ring_loss;
+    int32_t* counter;
+    float* loss_ring;
+    int32_t* counter_ring;
+    int32_t* cursor;
+    int32_t ring, loss_slots;
+} s3d_step_tail;
+int s3d_grid_encode_backward_adam_tail(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
+                                       void* grad_embeddings, uint32_t max_level_rows, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
+                                       float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int dtype,
+                                       void* workspace, size_t workspace_bytes, float bound, const int32_t* n_valid, float* found_inf,
+                                       void* control, size_t control_bytes, const s3d_grid_adam* adam, const s3d_step_tail* tail,
+                                       int* applied, uint32_t* tail_applied, s3d_stream_t stream);
 
 /* gridencoder.h:15 void grad_total_variation(inputs, embeddings, grad, offsets, weight, B, D, C, L, S, H,
  *                        gridtype, align_corners) — fp32 only (grid.py:162 disables autocast) */

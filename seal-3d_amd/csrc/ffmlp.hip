@@ -22,6 +22,7 @@
 // WMMA; parity target is the dense math of testing/test_ffmlp.py's torch twin, fp16 tolerance).
 #include "s3d_common.hpp"
 #include "sh_eval.hpp"
+#include "s3d_step_tail.hpp"
 
 namespace s3d {
 namespace {
@@ -722,8 +723,7 @@ __global__ void __launch_bounds__(256) k_ffmlp_dgrad(const _Float16* __restrict_
 
 // ------------------------------------------------------------------------------------ backward: wgrad
 // dW[o][i] = sum_b G[b][o] * X[b][i]; batch is the MFMA K dimension.  One (G, X) pair per layer.
-constexpr uint32_t kMaxMlpLayers = 8;
-constexpr uint32_t kWgradPad = 64;  // partial weight-gradient matrices are stored [64][64] fp32 regardless of W
+// (kMaxMlpLayers, kWgradPad: s3d_step_tail.hpp)
 struct WgradLayer {
     const _Float16* G;  // gradient w.r.t. the layer's pre-activation output
     const _Float16* X;  // the layer's input
@@ -872,22 +872,10 @@ __global__ void __launch_bounds__(256) k_ffmlp_wgrad(WgradPlan plan, uint32_t B,
     }
 }
 
-// Eight lanes per matrix element: each sums every 8th workgroup partial with independent accumulators (a single chain over
-// 256 partials was latency-bound: ~20 us), then a fixed xor-shuffle tree combines the eight.  Deterministic.
-constexpr uint32_t kReduceSplit = 8;
+// (kReduceSplit — eight lanes per matrix element — ReduceJob, ReduceJobs and the per-lane body wgrad_reduce_job: s3d_step_tail.hpp)
 // The same reduction for the weight gradients of SEVERAL networks in one launch (s3d_ffmlp_wgrad_reduce_pair: the backward calls
 // of the colour and the density network leave their partial sums in their workspaces, accumulate_grad_weights = 2, and this
 // launch finishes both — one launch of the step's 18 gone).  Same per-element order of additions as k_ffmlp_wgrad_reduce.
-struct ReduceJob {
-    const float* partial;   // [nblk][64][64] planes of this layer
-    _Float16* gw;           // the network's grad_weights
-    float* found_inf;
-    uint32_t Fo, Fi, w_off, nblk, accumulate;
-};
-struct ReduceJobs {
-    ReduceJob job[2 * kMaxMlpLayers];
-    uint32_t n;
-};
 __global__ void k_ffmlp_wgrad_reduce_jobs(ReduceJobs jobs);
 
 __global__ void k_ffmlp_wgrad_reduce(WgradPlan plan, uint32_t nblk, const float* __restrict__ partial,
@@ -925,33 +913,7 @@ __global__ void k_ffmlp_wgrad_reduce(WgradPlan plan, uint32_t nblk, const float*
 }
 
 __global__ void k_ffmlp_wgrad_reduce_jobs(ReduceJobs jobs) {
-    const ReduceJob L = jobs.job[blockIdx.y];
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t e = t / kReduceSplit, part = t % kReduceSplit;
-    const bool live = e < L.Fo * L.Fi;
-    const uint32_t o = live ? e / L.Fi : 0, i = live ? e - o * L.Fi : 0;
-    const float* p = L.partial + o * kWgradPad + i;
-    constexpr size_t kPlane = (size_t)kWgradPad * kWgradPad;
-    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-    if (live) {
-        uint32_t b = part;
-        for (; b + 3 * kReduceSplit < L.nblk; b += 4 * kReduceSplit) {
-            s0 += p[(size_t)(b + 0 * kReduceSplit) * kPlane];
-            s1 += p[(size_t)(b + 1 * kReduceSplit) * kPlane];
-            s2 += p[(size_t)(b + 2 * kReduceSplit) * kPlane];
-            s3 += p[(size_t)(b + 3 * kReduceSplit) * kPlane];
-        }
-        for (; b < L.nblk; b += kReduceSplit) s0 += p[(size_t)b * kPlane];
-    }
-    float v = (s0 + s1) + (s2 + s3);
-#pragma unroll
-    for (int d = 1; d < (int)kReduceSplit; d <<= 1) v += __shfl_xor(v, d, 64);
-    if (live && part == 0) {
-        if (L.accumulate) v += (float)L.gw[L.w_off + e];
-        const _Float16 h = (_Float16)v;
-        L.gw[L.w_off + e] = h;
-        if (L.found_inf && !(fabsf((float)h) <= 65504.0f)) *L.found_inf = 1.0f;
-    }
+    wgrad_reduce_job(jobs.job[blockIdx.y], blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------ backward: fused
@@ -1713,19 +1675,18 @@ S3D_EXPORT int s3d_ffmlp_ngp_pair_inference(const uint16_t* inputs, const uint16
     return check_launch("ffmlp_ngp_pair_inference");
 }
 
-S3D_EXPORT int s3d_ffmlp_wgrad_reduce_pair(const void* workspace_a, uint32_t B_a, uint32_t input_dim_a, uint32_t hidden_dim_a,
-                                          uint32_t num_layers_a, uint16_t* grad_weights_a, int accumulate_a, float* found_inf_a,
-                                          const void* workspace_b, uint32_t B_b, uint32_t input_dim_b, uint32_t hidden_dim_b,
-                                          uint32_t num_layers_b, uint16_t* grad_weights_b, int accumulate_b, float* found_inf_b,
-                                          s3d_stream_t stream) {
+int s3d::wgrad_reduce_pair_jobs(const void* workspace_a, uint32_t B_a, uint32_t input_dim_a, uint32_t hidden_dim_a,
+                                uint32_t num_layers_a, uint16_t* grad_weights_a, int accumulate_a, float* found_inf_a,
+                                const void* workspace_b, uint32_t B_b, uint32_t input_dim_b, uint32_t hidden_dim_b,
+                                uint32_t num_layers_b, uint16_t* grad_weights_b, int accumulate_b, float* found_inf_b,
+                                ReduceJobs& jobs, uint32_t& wmax) {
     S3D_REQUIRE(workspace_a && grad_weights_a && workspace_b && grad_weights_b, "ffmlp_wgrad_reduce_pair: null pointer");
     S3D_REQUIRE(num_layers_a >= 2 && num_layers_b >= 2 && num_layers_a + num_layers_b + 2 <= 2 * kMaxMlpLayers,
                 "ffmlp_wgrad_reduce_pair: too many layers");
     S3D_REQUIRE(input_dim_a <= kWgradPad && input_dim_b <= kWgradPad && hidden_dim_a <= kWgradPad && hidden_dim_b <= kWgradPad,
                 "ffmlp_wgrad_reduce_pair: the fused backward's shapes only");
-    ReduceJobs jobs;
     memset(&jobs, 0, sizeof(jobs));
-    uint32_t wmax = 0;
+    wmax = 0;
     auto add = [&](const void* ws, uint32_t B, uint32_t in_dim, uint32_t W, uint32_t nl, uint16_t* gw, int acc, float* fi) {
         uint32_t nblk = div_up<uint32_t>(B / 32, 4);  // (launch_backward_fused_k's partial count)
         if (nblk > kWgradBlocks) nblk = kWgradBlocks;
@@ -1742,8 +1703,21 @@ S3D_EXPORT int s3d_ffmlp_wgrad_reduce_pair(const void* workspace_a, uint32_t B_a
     };
     add(workspace_a, B_a, input_dim_a, hidden_dim_a, num_layers_a, grad_weights_a, accumulate_a, found_inf_a);
     add(workspace_b, B_b, input_dim_b, hidden_dim_b, num_layers_b, grad_weights_b, accumulate_b, found_inf_b);
-    hipLaunchKernelGGL(k_ffmlp_wgrad_reduce_jobs, dim3(div_up<uint32_t>(wmax * kWgradPad * kReduceSplit, 256), jobs.n), dim3(256), 0,
-                       as_stream(stream), jobs);
+    return S3D_OK;
+}
+
+S3D_EXPORT int s3d_ffmlp_wgrad_reduce_pair(const void* workspace_a, uint32_t B_a, uint32_t input_dim_a, uint32_t hidden_dim_a,
+                                          uint32_t num_layers_a, uint16_t* grad_weights_a, int accumulate_a, float* found_inf_a,
+                                          const void* workspace_b, uint32_t B_b, uint32_t input_dim_b, uint32_t hidden_dim_b,
+                                          uint32_t num_layers_b, uint16_t* grad_weights_b, int accumulate_b, float* found_inf_b,
+                                          s3d_stream_t stream) {
+    ReduceJobs jobs;
+    uint32_t wmax = 0;
+    const int rc = wgrad_reduce_pair_jobs(workspace_a, B_a, input_dim_a, hidden_dim_a, num_layers_a, grad_weights_a, accumulate_a,
+                                          found_inf_a, workspace_b, B_b, input_dim_b, hidden_dim_b, num_layers_b, grad_weights_b,
+                                          accumulate_b, found_inf_b, jobs, wmax);
+    if (rc != S3D_OK) return rc;
+    hipLaunchKernelGGL(k_ffmlp_wgrad_reduce_jobs, dim3(wgrad_reduce_units(wmax), jobs.n), dim3(256), 0, as_stream(stream), jobs);
     return check_launch("ffmlp_wgrad_reduce_pair");
 }
 

@@ -19,6 +19,7 @@
 //    table slice and summed in LDS as 64-bit fixed point (see "binned backward" below): deterministic, no global atomics.
 #include "s3d_common.hpp"
 #include "s3d_adam.hpp"
+#include "s3d_step_tail.hpp"
 #include "grid_device.hpp"
 #include <math.h>
 #include <type_traits>
@@ -1090,7 +1091,30 @@ __device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t v, uint32_t lane
 // (LDS-only) barrier -> products + wave scan -> LDS rank atomics, arrival counter -> the LAST wave to arrive scans the
 // slice counts and puts the bucket reservations in flight -> barrier -> staging (sorted by slice) while the reservations
 // return -> barrier -> copy-out, four records per lane in flight.
-template <typename T, uint32_t D, uint32_t C, bool FIXED24, uint32_t P>
+// Step tail, part one (s3d_grid_encode_backward_adam_tail): work of the training step that is independent of the scatter and
+// must be finished before the accumulate launch starts rides in this launch as one extra ROW of workgroups (blockIdx.y == 0,
+// dispatched first; the levels move up by one) that take no part in the scatter — no ticket, no wait between workgroups:
+//  (a) the weight-gradient reduce of the two MLPs (k_ffmlp_wgrad_reduce_jobs' 256-lane units, strided over the row),
+//  (b) the value of the criterion (k_bg_mse_reduce's one workgroup, two virtual threads per lane at P = 512): workgroup 0.
+struct ScatterTail {
+    ReduceJobs jobs;   // (a); n = 0: none
+    uint32_t units;    // 256-lane units per job
+    const float* sq;   // (b) [3N squared errors]; loss = nullptr: none
+    const float* dabs; // [N] depth terms or nullptr
+    uint32_t N;
+    float depth_weight;
+    float* loss;
+};
+template <uint32_t P>
+__device__ __forceinline__ void scatter_tail_rider(const ScatterTail& tl, float* lds) {
+    static_assert(P % 256 == 0 && 1024 % P == 0, "whole 256-lane units per workgroup, whole virtual threads per lane");
+    if (tl.loss && blockIdx.x == 0) loss_terms_reduce<1024 / P>(tl.sq, tl.dabs, tl.N, tl.depth_weight, tl.loss, lds, lds + 16);
+    const uint32_t total = tl.jobs.n * tl.units;
+    for (uint32_t u = blockIdx.x * (P / 256) + (threadIdx.x >> 8); u < total; u += gridDim.x * (P / 256))  // (wave-uniform)
+        wgrad_reduce_job(tl.jobs.job[u / tl.units], (u % tl.units) * 256 + (threadIdx.x & 255u));
+}
+
+template <typename T, uint32_t D, uint32_t C, bool FIXED24, uint32_t P, bool TAIL = false>
 __global__ void __launch_bounds__(P) k_bin_scatter6(const T* __restrict__ grad, const float* __restrict__ inputs,
                                                     const int32_t* __restrict__ offsets, uint32_t B, uint32_t level0,
                                                     LevelScales scales, uint32_t* __restrict__ hdr, uint32_t* __restrict__ cursor,
@@ -1098,7 +1122,7 @@ __global__ void __launch_bounds__(P) k_bin_scatter6(const T* __restrict__ grad, 
                                                     uint32_t nchunks, uint32_t cap, uint16_t* __restrict__ gkeys,
                                                     uint32_t* __restrict__ gvals, uint16_t* __restrict__ skeys,
                                                     uint32_t* __restrict__ svals, uint32_t gridtype, bool align_corners,
-                                                    uint32_t interp) {
+                                                    uint32_t interp, const ScatterTail tl) {
     using V = typename FeatVec<T, C>::type;
     static_assert(sizeof(V) == 4, "records carry one 32-bit value word");
     constexpr uint32_t K = 1u << D;
@@ -1114,7 +1138,13 @@ __global__ void __launch_bounds__(P) k_bin_scatter6(const T* __restrict__ grad, 
     uint2* stage = tab + smax;                                        // [P * K] {value, slice << 16 | row-in-slice}
     __shared__ uint32_t total_s, arrived, spilled_s;
 
-    const uint32_t lip = blockIdx.y;  // level inside the pass
+    if constexpr (TAIL) {
+        if (blockIdx.y == 0) {  // (uniform) the riders' row: the dynamic LDS holds (b)'s 32 partial sums
+            scatter_tail_rider<P>(tl, reinterpret_cast<float*>(smem_raw));
+            return;
+        }
+    }
+    const uint32_t lip = blockIdx.y - (TAIL ? 1u : 0u);  // level inside the pass
     const uint32_t level = level0 + lip, chunk = blockIdx.x;
     const uint32_t wg_lin = blockIdx.y * gridDim.x + blockIdx.x;
     (void)wg_lin;
@@ -1403,7 +1433,27 @@ struct GridAdam {
     const float* grad_scale;  // device: loss scale (or nullptr)
     const float* lr_scale;    // device: schedule factor (or nullptr)
 };
-template <typename T, uint32_t D, uint32_t C, bool FIXED24, uint32_t P, bool ADAM = false>
+// Step tail, part two (TAIL, with ADAM only): (c) the Adam of the step's small tensors — k_adam_step_multi's body with the skip
+// decision this kernel forms anyway, strided over the persistent workgroups behind their items — and (d) the end of the step
+// (k_step_epilogue's body) by the workgroup that takes the LAST ticket: by then every workgroup has read found_inf, the step
+// count and the loss scale (its loads complete before the barrier in front of its ticket), and has written its poison flag.
+constexpr int kTailAdamTensors = 4;
+struct AccTail {
+    AdamItem t[kTailAdamTensors];  // (c)
+    int32_t count;
+    float* scale;                  // (d) scaler_update's arguments; nullptr: none
+    int32_t* growth_tracker;
+    float growth, backoff;
+    int32_t interval;
+    float* adam_step;
+    const float* loss;             // step_ring_push's arguments; counter = nullptr: no rings
+    int32_t* counter;
+    float* loss_ring;
+    int32_t* counter_ring;
+    int32_t* cursor;
+    int32_t ring, loss_slots;
+};
+template <typename T, uint32_t D, uint32_t C, bool FIXED24, uint32_t P, bool ADAM = false, bool TAIL = false>
 __global__ void __launch_bounds__(kBinAccThreads) k_bin_accumulate6(const uint16_t* __restrict__ gkeys, const uint32_t* __restrict__ gvals,
                                                                    const uint16_t* __restrict__ skeys, const uint32_t* __restrict__ svals,
                                                                    const int32_t* __restrict__ offsets, T* __restrict__ grad_grid,
@@ -1411,8 +1461,9 @@ __global__ void __launch_bounds__(kBinAccThreads) k_bin_accumulate6(const uint16
                                                                    uint32_t* __restrict__ done, uint32_t* __restrict__ cursor,
                                                                    uint32_t* __restrict__ ovn, const uint2* __restrict__ ovl,
                                                                    uint32_t smax, uint32_t nchunks, uint32_t cap,
-                                                                   float* __restrict__ found_inf, const GridAdam ad) {
+                                                                   float* __restrict__ found_inf, const GridAdam ad, const AccTail at) {
     using V = typename FeatVec<T, C>::type;
+    static_assert(ADAM || !TAIL, "the step tail rides with the fused update only");
     static_assert(!ADAM || (FIXED24 && sizeof(T) == 2 && C == 2), "the fused update is built for the fp16 C = 2 tables of the -O configs");
     static_assert(sizeof(V) == 4, "records carry one 32-bit value word");
     constexpr uint32_t K = 1u << D;
@@ -1749,6 +1800,12 @@ __global__ void __launch_bounds__(kBinAccThreads) k_bin_accumulate6(const uint16
         S3D_STAMP(1, wg_lin, 5);
     }
     if (found_inf && overflow) *found_inf = 1.0f;
+    if constexpr (TAIL) {
+        for (int32_t i = 0; i < at.count; i++)  // (c): the first n / 1,024 workgroups have lanes inside tensor i
+            if ((size_t)blockIdx.x * kBinAccThreads < at.t[i].n)
+                adam_item_run(at.t[i], ad_skip, ad.step, ad.grad_scale, ad.lr_scale, (size_t)blockIdx.x * kBinAccThreads + threadIdx.x,
+                              (size_t)gridDim.x * kBinAccThreads);
+    }
     // the last workgroup to get here clears the header words of the pass's levels and the ticket itself (every workgroup has
     // read its header words before it takes a ticket)
     __syncthreads();
@@ -1757,6 +1814,12 @@ __global__ void __launch_bounds__(kBinAccThreads) k_bin_accumulate6(const uint16
         if (t == gridDim.x - 1) {
             for (uint32_t l = 0; l < nl; l++) hdr[level0 + l] = 0u;
             *done = 0u;
+            if constexpr (TAIL) {
+                if (at.scale) {  // (d)
+                    scaler_update(at.scale, at.growth_tracker, found_inf, at.growth, at.backoff, at.interval, at.adam_step);
+                    if (at.counter) step_ring_push(at.loss, at.counter, at.loss_ring, at.counter_ring, at.cursor, at.ring, at.loss_slots);
+                }
+            }
         }
     }
 }
@@ -2083,15 +2146,76 @@ struct GridBwd {
     hipStream_t st;
     float* found_inf;      // s3d_grid_encode_backward(found_inf), or nullptr
     const GridAdam* adam;  // s3d_grid_encode_backward_adam: the update to apply in the accumulate, or nullptr
+    const s3d_step_tail* tail;  // s3d_grid_encode_backward_adam_tail: work to run inside the two binned launches, or nullptr
 };
 struct GridBwdResult {
     bool reported;  // the path taken has written found_inf while it accumulated (otherwise the caller checks the table)
     bool applied;   // the accumulate applied `adam`
+    uint32_t tail;  // S3D_TAIL_* bits of the parts of `tail` that ran inside the launches
 };
+
+// the device-side forms of a step tail; `want`: S3D_TAIL_* bits of the parts the caller filled in and that CAN ride
+struct TailPlan {
+    ScatterTail sc;
+    AccTail ac;
+    uint32_t want;
+};
+int plan_tail(const s3d_step_tail& t, float* found_inf, TailPlan& p) {
+    memset(&p, 0, sizeof(p));
+    if (t.workspace_a) {
+        uint32_t wmax = 0;
+        const int rc = wgrad_reduce_pair_jobs(t.workspace_a, t.B_a, t.input_dim_a, t.hidden_dim_a, t.num_layers_a, t.grad_weights_a,
+                                              t.accumulate_a, t.found_inf_a, t.workspace_b, t.B_b, t.input_dim_b, t.hidden_dim_b,
+                                              t.num_layers_b, t.grad_weights_b, t.accumulate_b, t.found_inf_b, p.sc.jobs, wmax);
+        if (rc != S3D_OK) return rc;
+        p.sc.units = wgrad_reduce_units(wmax);
+        p.want |= S3D_TAIL_WGRAD_REDUCE;
+    }
+    if (t.loss_workspace && t.loss_N) {
+        S3D_REQUIRE(t.loss, "grid_encode_backward_adam_tail: loss terms without a loss");
+        p.sc.sq = t.loss_workspace;
+        p.sc.dabs = t.loss_with_depth ? t.loss_workspace + (size_t)3 * t.loss_N : nullptr;
+        p.sc.N = t.loss_N; p.sc.depth_weight = t.loss_depth_weight; p.sc.loss = t.loss;
+        p.want |= S3D_TAIL_LOSS;
+    }
+    bool adam_ok = found_inf != nullptr;  // (the riders take the call's flag)
+    S3D_REQUIRE(t.n_tensors >= 0 && (t.tensors || t.n_tensors == 0), "grid_encode_backward_adam_tail: null tensor list");
+    for (int32_t k = 0; k < t.n_tensors && adam_ok; k++) {
+        if (t.tensors[k].n == 0) continue;
+        if (p.ac.count == kTailAdamTensors) { adam_ok = false; break; }
+        if (!adam_item_from(t.tensors[k], 0, k, p.ac.t[p.ac.count])) return S3D_ERR_INVALID;
+        p.ac.count++;
+    }
+    if (!adam_ok) p.ac.count = 0;
+    if (p.ac.count) p.want |= S3D_TAIL_ADAM;
+    // (d) clears the flag and advances the count: never in front of an update the caller still has to launch
+    if (t.scale && found_inf && (adam_ok || t.n_tensors == 0)) {
+        S3D_REQUIRE(t.growth_tracker, "grid_encode_backward_adam_tail: null pointer (scaler)");
+        S3D_REQUIRE(!t.counter || (t.counter_ring && t.cursor && t.ring > 0), "grid_encode_backward_adam_tail: null pointer or empty ring");
+        p.ac.scale = t.scale; p.ac.growth_tracker = t.growth_tracker; p.ac.growth = t.growth_factor; p.ac.backoff = t.backoff_factor;
+        p.ac.interval = t.growth_interval; p.ac.adam_step = t.adam_step;
+        p.ac.loss = t.ring_loss; p.ac.counter = t.counter; p.ac.loss_ring = t.loss_ring; p.ac.counter_ring = t.counter_ring;
+        p.ac.cursor = t.cursor; p.ac.ring = t.ring; p.ac.loss_slots = t.loss_slots;
+        p.want |= S3D_TAIL_EPILOGUE;
+    }
+    return S3D_OK;
+}
+// a call that cannot carry the tail: (a) and (b) as their ordinary launches in front of the backward
+int tail_in_front(const s3d_step_tail& t, hipStream_t st) {
+    if (t.workspace_a) {
+        const int rc = s3d_ffmlp_wgrad_reduce_pair(t.workspace_a, t.B_a, t.input_dim_a, t.hidden_dim_a, t.num_layers_a, t.grad_weights_a,
+                                                   t.accumulate_a, t.found_inf_a, t.workspace_b, t.B_b, t.input_dim_b, t.hidden_dim_b,
+                                                   t.num_layers_b, t.grad_weights_b, t.accumulate_b, t.found_inf_b, (s3d_stream_t)st);
+        if (rc != S3D_OK) return rc;
+    }
+    if (t.loss_workspace && t.loss_N)
+        return s3d_loss_terms_reduce(t.loss_workspace, t.loss_N, t.loss_with_depth, t.loss_depth_weight, t.loss, (s3d_stream_t)st);
+    return S3D_OK;
+}
 
 // `control`: the caller's control block if it is large enough for this layout, else nullptr
 template <typename T, uint32_t D, uint32_t C, bool FIXED24>
-int launch_binned3(const GridBwd& a, const BinLayout3& lay, unsigned char* control, GridBwdResult& res) {
+int launch_binned3(const GridBwd& a, const BinLayout3& lay, unsigned char* control, GridBwdResult& res, const TailPlan* tp = nullptr) {
     const T* grad = (const T*)a.grad;
     T* grad_emb = (T*)a.grad_emb;
     const uint32_t B = a.B, L = a.L;
@@ -2132,11 +2256,34 @@ int launch_binned3(const GridBwd& a, const BinLayout3& lay, unsigned char* contr
     const uint32_t cus = device_cus();
     for (uint32_t l0 = 0; l0 < L; l0 += lay.levels_per_pass) {
         const uint32_t nl = (L - l0 < lay.levels_per_pass) ? L - l0 : lay.levels_per_pass;
-        hipLaunchKernelGGL((k_bin_scatter6<T, D, C, FIXED24, P>), dim3(lay.chunks, nl), dim3(P), stage, st, grad, a.inputs, a.offsets, B,
-                           l0, a.sc, hdr, cursor, ovn, ovl, lay.smax, lay.chunks, lay.cap, keys, vals, skeys, svals, a.gridtype, a.ac,
-                           a.interp);
         const uint32_t items = lay.smax * nl;
         bool fused = false;
+        if constexpr (FIXED24 && sizeof(T) == 2 && C == 2) {
+            if (tp && a.adam && nl == L) {  // (launch_backward_c checked it: one pass, the fused update) both launches with riders
+                static std::atomic<uint64_t> attr_tail{0};
+                int dev3;
+                if (device_needs_setup(attr_tail, &dev3)) {
+                    S3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bin_scatter6<T, D, C, FIXED24, P, true>),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage_max));
+                    S3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bin_accumulate6<T, D, C, FIXED24, P, true, true>),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBinAccBytes));
+                    device_setup_done(attr_tail, dev3);
+                }
+                hipLaunchKernelGGL((k_bin_scatter6<T, D, C, FIXED24, P, true>), dim3(lay.chunks, nl + 1), dim3(P), stage, st, grad, a.inputs,
+                                   a.offsets, B, l0, a.sc, hdr, cursor, ovn, ovl, lay.smax, lay.chunks, lay.cap, keys, vals, skeys, svals,
+                                   a.gridtype, a.ac, a.interp, tp->sc);
+                hipLaunchKernelGGL((k_bin_accumulate6<T, D, C, FIXED24, P, true, true>), dim3(std::min(items, cus * kBinAccPerCu)),
+                                   dim3(kBinAccThreads), kBinAccBytes, st, (const uint16_t*)keys, (const uint32_t*)vals, (const uint16_t*)skeys,
+                                   (const uint32_t*)svals, a.offsets, grad_emb, B, l0, nl, hdr, done, cursor, ovn, (const uint2*)ovl, lay.smax,
+                                   lay.chunks, lay.cap, a.found_inf, *a.adam, tp->ac);
+                res.applied = true;
+                res.tail = tp->want;
+                continue;
+            }
+        }
+        hipLaunchKernelGGL((k_bin_scatter6<T, D, C, FIXED24, P>), dim3(lay.chunks, nl), dim3(P), stage, st, grad, a.inputs, a.offsets, B,
+                           l0, a.sc, hdr, cursor, ovn, ovl, lay.smax, lay.chunks, lay.cap, keys, vals, skeys, svals, a.gridtype, a.ac,
+                           a.interp, ScatterTail{});
         if constexpr (FIXED24 && sizeof(T) == 2 && C == 2) {
             if (a.adam && nl == L) {  // (one pass covers every level: the skip decision needs all poison words up front)
                 static std::atomic<uint64_t> attr_adam{0};
@@ -2149,7 +2296,7 @@ int launch_binned3(const GridBwd& a, const BinLayout3& lay, unsigned char* contr
                 hipLaunchKernelGGL((k_bin_accumulate6<T, D, C, FIXED24, P, true>), dim3(std::min(items, cus * kBinAccPerCu)), dim3(kBinAccThreads),
                                    kBinAccBytes, st, (const uint16_t*)keys, (const uint32_t*)vals, (const uint16_t*)skeys, (const uint32_t*)svals,
                                    a.offsets, grad_emb, B, l0, nl, hdr, done, cursor, ovn, (const uint2*)ovl, lay.smax, lay.chunks, lay.cap,
-                                   a.found_inf, *a.adam);
+                                   a.found_inf, *a.adam, AccTail{});
                 fused = true;
                 res.applied = true;
             }
@@ -2157,7 +2304,7 @@ int launch_binned3(const GridBwd& a, const BinLayout3& lay, unsigned char* contr
         if (!fused)
         hipLaunchKernelGGL((k_bin_accumulate6<T, D, C, FIXED24, P>), dim3(std::min(items, cus * kBinAccPerCu)), dim3(kBinAccThreads), kBinAccBytes, st,
                            (const uint16_t*)keys, (const uint32_t*)vals, (const uint16_t*)skeys, (const uint32_t*)svals, a.offsets,
-                           grad_emb, B, l0, nl, hdr, done, cursor, ovn, (const uint2*)ovl, lay.smax, lay.chunks, lay.cap, a.found_inf, GridAdam{});
+                           grad_emb, B, l0, nl, hdr, done, cursor, ovn, (const uint2*)ovl, lay.smax, lay.chunks, lay.cap, a.found_inf, GridAdam{}, AccTail{});
     }
     res.reported = true;
     return check_launch("grid_encode_backward");
@@ -2176,13 +2323,29 @@ int launch_backward_c(const GridBwd& a, GridBwdResult& res) {
     const BinLayout lay = bin_layout(B, D, C, L, a.max_level_rows, sizeof(T));
     const bool bin_ok = lay.ok && ws && a.ws_bytes >= lay.total;
     const bool binned = bin_ok && (a.force_path >= 2 || (a.force_path == 0 && B >= kBinnedMinPoints));
+    // a step tail rides where the fused update does: fp16 C = 2, the 6-byte-record path at the fixed scale, every level in one pass
+    TailPlan tp;
+    bool rides = false;
+    if constexpr (sizeof(T) == 2 && C == 2) {
+        const BinLayout3 l3 = bin_layout3(B, D, C, L, a.max_level_rows, sizeof(T));
+        rides = a.tail && a.adam && binned && l3.ok && ws && a.ws_bytes >= l3.total && ((uint64_t)B << D) <= (1ull << 23) &&
+                l3.levels_per_pass >= L;
+    }
+    if (rides) {
+        const int rc = plan_tail(*a.tail, a.found_inf, tp);
+        if (rc != S3D_OK) return rc;
+    }
+    if (a.tail && !rides) {
+        const int rc = tail_in_front(*a.tail, st);
+        if (rc != S3D_OK) return rc;
+    }
     if constexpr (sizeof(T) * C == 4) {  // one 32-bit value word per record (fp16 C = 2, fp32 C = 1)
         const BinLayout3 lay3 = bin_layout3(B, D, C, L, a.max_level_rows, sizeof(T));
         if (binned && lay3.ok && ws && a.ws_bytes >= lay3.total) {  // 6-byte records, XCD-private sub-buckets
             int rc;
             unsigned char* cb = (a.control && a.control_bytes >= bin3_control_bytes(lay3, L)) ? a.control : nullptr;
             if (sizeof(T) == 2 && ((uint64_t)B << D) <= (1ull << 23))
-                rc = launch_binned3<T, D, C, true>(a, lay3, cb, res);
+                rc = launch_binned3<T, D, C, true>(a, lay3, cb, res, rides ? &tp : nullptr);
             else
                 rc = launch_binned3<T, D, C, false>(a, lay3, cb, res);
             if (rc != S3D_OK) return rc;
@@ -2390,7 +2553,7 @@ int grid_backward(const void* grad, const float* inputs, const int32_t* offsets,
                   uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, const void* dy_dx, void* grad_inputs,
                   uint32_t gridtype, int align_corners, uint32_t interp, int dtype, void* workspace, size_t workspace_bytes, float bound,
                   const int32_t* n_valid, int path, float* found_inf, void* control, size_t control_bytes, s3d_stream_t stream,
-                  const GridAdam* adam, bool* applied) {
+                  const GridAdam* adam, bool* applied, const s3d_step_tail* tail = nullptr, uint32_t* tail_applied = nullptr) {
     // path: 0 = auto (binned from 8,192 points), 1 = direct global atomics, 2 = binned (partition + LDS accumulate)
     S3D_REQUIRE(path >= 0 && path <= 2, "grid_encode_backward: path must be 0 (auto), 1 (atomics) or 2 (binned)");
     S3D_REQUIRE(bound >= 0.0f && !(bound != 0.0f && dy_dx), "grid_encode_backward: bound must be >= 0 and 0 with an input Jacobian");
@@ -2406,11 +2569,12 @@ int grid_backward(const void* grad, const float* inputs, const int32_t* offsets,
     }
     GridBwd a{grad, dy_dx, grad_embeddings, grad_inputs, inputs, offsets, B, C, L, max_level_rows, gridtype, interp, align_corners != 0,
               LevelScales{}, (unsigned char*)workspace, (unsigned char*)control, workspace_bytes, control_bytes, path, as_stream(stream),
-              found_inf, adam};
+              found_inf, adam, tail};
     host_scales(L, S, H, a.sc, bound, n_valid);
-    GridBwdResult res{false, false};
+    GridBwdResult res{false, false, 0u};
     const int rc = [&]() -> int { S3D_DISPATCH_TD(dtype, D, launch_backward, a, res) }();
     if (applied) *applied = res.applied;
+    if (tail_applied) *tail_applied = res.tail;
     if (rc != S3D_OK || !found_inf || res.reported) return rc;
     if (dtype == S3D_F32)
         hipLaunchKernelGGL(k_table_nonfinite<float>, dim3(kMaxStreamBlocks), dim3(256), 0, a.st, (const float*)grad_embeddings, offsets, L, C, found_inf);
@@ -2433,13 +2597,12 @@ S3D_EXPORT int s3d_grid_encode_backward(const void* grad, const float* inputs, c
                          control_bytes, stream, nullptr, nullptr);
 }
 
-S3D_EXPORT int s3d_grid_encode_backward_adam(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
-                                             void* grad_embeddings, uint32_t max_level_rows, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
-                                             float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int dtype,
-                                             void* workspace, size_t workspace_bytes, float bound, const int32_t* n_valid, float* found_inf,
-                                             void* control, size_t control_bytes, const s3d_grid_adam* adam, int* applied,
-                                             s3d_stream_t stream) {
-    (void)embeddings;
+namespace {
+int grid_backward_adam(const void* grad, const float* inputs, const int32_t* offsets, void* grad_embeddings, uint32_t max_level_rows,
+                       uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype, int align_corners,
+                       uint32_t interp, int dtype, void* workspace, size_t workspace_bytes, float bound, const int32_t* n_valid,
+                       float* found_inf, void* control, size_t control_bytes, const s3d_grid_adam* adam, int* applied,
+                       const s3d_step_tail* tail, uint32_t* tail_applied, s3d_stream_t stream) {
     S3D_REQUIRE(adam && applied, "grid_encode_backward_adam: null pointer");
     S3D_REQUIRE(adam->param && adam->exp_avg && adam->exp_avg_sq && adam->step, "grid_encode_backward_adam: null optimizer state");
     *applied = 0;
@@ -2448,11 +2611,42 @@ S3D_EXPORT int s3d_grid_encode_backward_adam(const void* grad, const float* inpu
     ga.lr = adam->lr; ga.beta1 = adam->beta1; ga.beta2 = adam->beta2; ga.eps = adam->eps;
     ga.step = adam->step; ga.grad_scale = adam->grad_scale; ga.lr_scale = adam->lr_scale;
     bool ran = false;
+    if (B == 0 && tail) {  // (nothing to scatter: the tail's launches still have to happen)
+        const int rc = tail_in_front(*tail, as_stream(stream));
+        if (rc != S3D_OK) return rc;
+    }
     const int rc = grid_backward(grad, inputs, offsets, grad_embeddings, max_level_rows, B, D, C, L, S, H, nullptr, nullptr, gridtype,
                                  align_corners, interp, dtype, workspace, workspace_bytes, bound, n_valid, 0, found_inf, control,
-                                 control_bytes, stream, &ga, &ran);
+                                 control_bytes, stream, &ga, &ran, tail, tail_applied);
     *applied = ran ? 1 : 0;
     return rc;
+}
+}  // namespace
+
+S3D_EXPORT int s3d_grid_encode_backward_adam_tail(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
+                                                  void* grad_embeddings, uint32_t max_level_rows, uint32_t B, uint32_t D, uint32_t C,
+                                                  uint32_t L, float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp,
+                                                  int dtype, void* workspace, size_t workspace_bytes, float bound, const int32_t* n_valid,
+                                                  float* found_inf, void* control, size_t control_bytes, const s3d_grid_adam* adam,
+                                                  const s3d_step_tail* tail, int* applied, uint32_t* tail_applied, s3d_stream_t stream) {
+    (void)embeddings;
+    S3D_REQUIRE(tail && tail_applied, "grid_encode_backward_adam_tail: null pointer");
+    *tail_applied = 0;
+    return grid_backward_adam(grad, inputs, offsets, grad_embeddings, max_level_rows, B, D, C, L, S, H, gridtype, align_corners, interp,
+                              dtype, workspace, workspace_bytes, bound, n_valid, found_inf, control, control_bytes, adam, applied, tail,
+                              tail_applied, stream);
+}
+
+S3D_EXPORT int s3d_grid_encode_backward_adam(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
+                                             void* grad_embeddings, uint32_t max_level_rows, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
+                                             float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int dtype,
+                                             void* workspace, size_t workspace_bytes, float bound, const int32_t* n_valid, float* found_inf,
+                                             void* control, size_t control_bytes, const s3d_grid_adam* adam, int* applied,
+                                             s3d_stream_t stream) {
+    (void)embeddings;
+    return grid_backward_adam(grad, inputs, offsets, grad_embeddings, max_level_rows, B, D, C, L, S, H, gridtype, align_corners, interp,
+                              dtype, workspace, workspace_bytes, bound, n_valid, found_inf, control, control_bytes, adam, applied, nullptr,
+                              nullptr, stream);
 }
 
 S3D_EXPORT int s3d_grad_total_variation(const float* inputs, const float* embeddings, float* grad,

@@ -13,6 +13,7 @@
 //  * Integer results (cell coordinates, morton rows, sample counts, span offsets) follow the
 //    oracle expression by expression: explicit fmaf, -ffp-contract=off, IEEE division.
 #include "s3d_common.hpp"
+#include "s3d_step_tail.hpp"
 
 namespace s3d {
 namespace {
@@ -1340,24 +1341,7 @@ __global__ void __launch_bounds__(256) k_composite_train_loss_wave(
 __global__ void __launch_bounds__(1024) k_bg_mse_reduce(const float* __restrict__ sq, const float* __restrict__ dabs, uint32_t N,
                                                         float depth_weight, float* __restrict__ loss) {
     __shared__ float part[16], dpart[16];
-    float acc = 0.0f, dacc = 0.0f;
-    for (uint32_t m = threadIdx.x; m < N; m += 1024) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) acc += sq[(size_t)m * 3 + c];
-    }
-    if (dabs)
-        for (uint32_t m = threadIdx.x; m < N; m += 1024) dacc += dabs[m];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { acc += __shfl_xor(acc, d, 64); dacc += __shfl_xor(dacc, d, 64); }
-    if ((threadIdx.x & 63) == 0) { part[threadIdx.x >> 6] = acc; dpart[threadIdx.x >> 6] = dacc; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.0f, td = 0.0f;
-        for (int w = 0; w < 16; w++) { t += part[w]; td += dpart[w]; }
-        t = t / (3.0f * (float)N);
-        if (dabs) t = t + depth_weight * (td / (float)N);
-        *loss = t;
-    }
+    loss_terms_reduce<1>(sq, dabs, N, depth_weight, loss, part, dpart);  // (s3d_step_tail.hpp: shared with the grid backward's rider)
 }
 
 // ---------------------------------------------------------------- inference
@@ -1885,7 +1869,7 @@ S3D_EXPORT int s3d_composite_rays_train_loss(const float* sigmas, const float* r
                                              float* grad_image, float* grad_weights_sum, float* loss, float* workspace,
                                              s3d_stream_t stream) {
     if (N == 0) return S3D_OK;
-    S3D_REQUIRE(rays && weights_sum && depth && image && gt && bg_rgb && grad_loss && loss && workspace,
+    S3D_REQUIRE(rays && weights_sum && depth && image && gt && bg_rgb && grad_loss && workspace,
                 "composite_rays_train_loss: null pointer");
     S3D_REQUIRE(M == 0 || (sigmas && rgbs && deltas && grad_sigmas && grad_rgbs), "composite_rays_train_loss: null sample buffer");
     S3D_REQUIRE((grad_image == nullptr) == (grad_weights_sum == nullptr), "composite_rays_train_loss: grad_image and grad_weights_sum "
@@ -1893,8 +1877,9 @@ S3D_EXPORT int s3d_composite_rays_train_loss(const float* sigmas, const float* r
     hipLaunchKernelGGL(k_composite_train_loss_wave, dim3(div_up<uint32_t>(N, 4)), dim3(256), 0, as_stream(stream), sigmas, rgbs, deltas,
                        rays, M, N, T_thresh, gt, bg_rgb[0], bg_rgb[1], bg_rgb[2], grad_loss, gt_depth, depth_weight, weights_sum, depth,
                        image, grad_sigmas, grad_rgbs, grad_image, grad_weights_sum, workspace);
-    hipLaunchKernelGGL(k_bg_mse_reduce, dim3(1), dim3(1024), 0, as_stream(stream), (const float*)workspace,
-                       gt_depth ? (const float*)(workspace + (size_t)3 * N) : nullptr, N, depth_weight, loss);
+    if (loss)  // (NULL: the caller sums the terms later — s3d_loss_terms_reduce, or a step tail of the grid backward)
+        hipLaunchKernelGGL(k_bg_mse_reduce, dim3(1), dim3(1024), 0, as_stream(stream), (const float*)workspace,
+                           gt_depth ? (const float*)(workspace + (size_t)3 * N) : nullptr, N, depth_weight, loss);
     return check_launch("composite_rays_train_loss");
 }
 
@@ -1905,7 +1890,7 @@ S3D_EXPORT int s3d_composite_rays_train_loss_bg(const float* sigmas, const float
                                                 float* grad_image, float* grad_weights_sum, float* grad_bg, float* loss, float* workspace,
                                                 s3d_stream_t stream) {
     if (N == 0) return S3D_OK;
-    S3D_REQUIRE(rays && weights_sum && depth && image && gt && bg && grad_loss && loss && workspace,
+    S3D_REQUIRE(rays && weights_sum && depth && image && gt && bg && grad_loss && workspace,
                 "composite_rays_train_loss_bg: null pointer");
     S3D_REQUIRE(M == 0 || (sigmas && rgbs && deltas && grad_sigmas && grad_rgbs), "composite_rays_train_loss_bg: null sample buffer");
     S3D_REQUIRE((grad_image == nullptr) == (grad_weights_sum == nullptr), "composite_rays_train_loss_bg: grad_image and "
@@ -1913,9 +1898,19 @@ S3D_EXPORT int s3d_composite_rays_train_loss_bg(const float* sigmas, const float
     hipLaunchKernelGGL(k_composite_train_loss_wave, dim3(div_up<uint32_t>(N, 4)), dim3(256), 0, as_stream(stream), sigmas, rgbs, deltas,
                        rays, M, N, T_thresh, gt, 0.0f, 0.0f, 0.0f, grad_loss, gt_depth, depth_weight, weights_sum, depth,
                        image, grad_sigmas, grad_rgbs, grad_image, grad_weights_sum, workspace, bg, grad_bg);
-    hipLaunchKernelGGL(k_bg_mse_reduce, dim3(1), dim3(1024), 0, as_stream(stream), (const float*)workspace,
-                       gt_depth ? (const float*)(workspace + (size_t)3 * N) : nullptr, N, depth_weight, loss);
+    if (loss)  // (NULL: the caller sums the terms later — s3d_loss_terms_reduce, or a step tail of the grid backward)
+        hipLaunchKernelGGL(k_bg_mse_reduce, dim3(1), dim3(1024), 0, as_stream(stream), (const float*)workspace,
+                           gt_depth ? (const float*)(workspace + (size_t)3 * N) : nullptr, N, depth_weight, loss);
     return check_launch("composite_rays_train_loss_bg");
+}
+
+S3D_EXPORT int s3d_loss_terms_reduce(const float* workspace, uint32_t N, int with_depth, float depth_weight, float* loss,
+                                     s3d_stream_t stream) {
+    if (N == 0) return S3D_OK;
+    S3D_REQUIRE(workspace && loss, "loss_terms_reduce: null pointer");
+    hipLaunchKernelGGL(k_bg_mse_reduce, dim3(1), dim3(1024), 0, as_stream(stream), workspace,
+                       with_depth ? workspace + (size_t)3 * N : nullptr, N, depth_weight, loss);
+    return check_launch("loss_terms_reduce");
 }
 
 S3D_EXPORT int s3d_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t* rays_alive, const float* rays_t,

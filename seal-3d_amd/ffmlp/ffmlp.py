@@ -264,8 +264,17 @@ class _FFMLPNgpPair(Function):
         g_sigma = None if g_sigma is None else g_sigma.float().contiguous()
         _backend.ffmlp_backward(None, inputs, w_sigma, None, B, in_s, 16, W_s, nl_s, act_s, oact_s, calc, None, grad_inputs, gw_s,
                                 mid=(g_sigma, g_cin, h0), workspace=ws_s, defer_reduce=True, **ctx.extra, **extra_s)
-        _backend.wgrad_reduce_pair((ws_c, B, in_c, W_c, nl_c, gw_c, extra_c.get("accumulate", False), extra_c.get("found_inf")),
-                                   (ws_s, B, in_s, W_s, nl_s, gw_s, extra_s.get("accumulate", False), extra_s.get("found_inf")))
+        pair = ((ws_c, B, in_c, W_c, nl_c, gw_c, extra_c.get("accumulate", False), extra_c.get("found_inf")),
+                (ws_s, B, in_s, W_s, nl_s, gw_s, extra_s.get("accumulate", False), extra_s.get("found_inf")))
+        tail = s3d_hip.StepTail.current
+        if tail is not None and tail.armed and tail.reduce is None:
+            # the reduce rides in the hash table's backward, which runs behind this node; the holder keeps `scratch` (ws_c / ws_s
+            # are views of it) alive until that call has issued its launches
+            tail.reduce = pair
+            if stash_s is not None and stash_c is not None:
+                tail.adam_params += [ref_s.param, ref_c.param]  # their update may ride as well (nerf/optim.py)
+        else:
+            _backend.wgrad_reduce_pair(*pair)
         for stash, ref in ((stash_s, ref_s), (stash_c, ref_c)):
             if stash is not None:
                 ref.param._s3d_grad_touched = True

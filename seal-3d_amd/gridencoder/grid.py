@@ -136,9 +136,21 @@ class _GridEncode(Function):
         # the optimizer armed this table for THIS backward pass (nerf/optim.py: NativeAdam.arm_fused_tables): the accumulate
         # kernel applies the update itself and no gradient is written
         armed = ctx.param.__dict__.pop("_s3d_fused_arm", None) if stash is not None else None
+        # ... and, with a step tail attached to the arm (s3d_hip.StepTail), the step's small closing launches as well
+        tail = armed.pop("tail", None) if armed is not None else None
+        if tail is not None and not (dy_dx is None and hasattr(_backend, "grid_encode_backward_adam_tail")):
+            tail.flush()
+            tail = None
         if armed is not None and dy_dx is None and hasattr(_backend, "grid_encode_backward_adam"):
-            if _backend.grid_encode_backward_adam(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, gridtype,
-                                                  align_corners, interpolation, armed, **extra):
+            if tail is not None:
+                done, parts = _backend.grid_encode_backward_adam_tail(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S,
+                                                                      H, gridtype, align_corners, interpolation, armed, tail.take(),
+                                                                      **extra)
+                tail.done(parts)
+            else:
+                done = _backend.grid_encode_backward_adam(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, gridtype,
+                                                          align_corners, interpolation, armed, **extra)
+            if done:
                 ctx.param._s3d_grad_touched = was_touched  # (nothing was written into the hand-over buffer)
                 ctx.param._s3d_fused_done = True
             return None, None, None, None, None, None, None, None, None, None, None, None, None, None

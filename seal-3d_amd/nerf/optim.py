@@ -112,6 +112,69 @@ class NativeAdam(torch.optim.Optimizer):
                 n += 1
         return n
 
+    def _tail_item(self, p, lr_of):
+        """adam_step_multi's item for parameter p exactly as step() would form it on the one-launch route, or None when step()
+        would do more than that launch for it (packed weights, a stale fp16 copy, an L1 term)"""
+        g = getattr(p, "_s3d_grad", None)
+        if g is None or getattr(p, "_s3d_pack_spec", None) is not None or not p.requires_grad:
+            return None
+        half = getattr(p, "_s3d_half", None)
+        if hasattr(p, "_s3d_half") and (half is None or p._s3d_half_version != p._version or not half.is_contiguous()):
+            return None
+        if float(p.__dict__.get("_s3d_l1", 0.0)) != 0.0:
+            return None
+        group = next(gr for gr in self.param_groups if any(q is p for q in gr["params"]))
+        st = self.state[p]
+        b1, b2 = group["betas"]
+        return (p.data, g, st["exp_avg"], st["exp_avg_sq"], half, lr_of.get(id(group), group["lr"]), b1, b2, group["eps"],
+                self.consume_grads, 0.0)
+
+    def arm_step_tail(self, tail, scaler=None, ring_push=None):
+        """Called right after `arm_fused_tables` armed exactly ONE table: attach the step tail (s3d_hip.StepTail) to that arm.  The
+        table's backward then also runs, inside its own launches, the weight-gradient reduce and the criterion's sum that were
+        filed in the tail, the update of the parameters whose backward filed them there (`tail.adam_params`: `step()` skips them
+        through `_s3d_fused_done`) and — when no other parameter is left for `step()` — the scaler's update with `ring_push`.
+        Returns False (nothing attached) when this step's launches would not carry the arguments step() would use."""
+        armed = [p for g in self.param_groups for p in g["params"] if "_s3d_fused_arm" in p.__dict__]
+        if len(armed) != 1:
+            return False
+        lr_of = {}
+        if self._lr_captured is not None:
+            # step() moves the device-side schedule factor before its launch; a launch issued ahead of it must find it settled
+            if not torch.cuda.is_current_stream_capturing():
+                now = [float(g["lr"]) for g in self.param_groups]
+                f = [n / c if c != 0 else (1.0 if n == 0 else float("inf")) for n, c in zip(now, self._lr_captured)]
+                if any(x != self._lr_factor for x in f):
+                    return False
+            lr_of = {id(g): lr for g, lr in zip(self.param_groups, self._lr_captured)}
+        table = armed[0]
+        everyone = [p for g in self.param_groups for p in g["params"]]
+
+        def items(params):
+            out = [self._tail_item(p, lr_of) for p in params]
+            return None if any(it is None for it in out) else out
+
+        def covers(params):  # the end of the step may ride only when step() has no update left to launch
+            mine = {id(q) for q in params} | {id(table)}
+            return all(id(p) in mine for p in everyone)
+
+        def applied(t, parts):
+            if parts & s3d_hip.GridBackend.TAIL_ADAM:
+                for p in t.adam_params:
+                    p._s3d_fused_done = True
+                    if self.consume_grads:
+                        p._s3d_grad_consumed = True
+            if parts & s3d_hip.GridBackend.TAIL_EPILOGUE:
+                scaler._tail_done = True
+
+        tail.adam_items, tail.on_applied = items, applied
+        ep = scaler.tail_epilogue(self) if scaler is not None and hasattr(scaler, "tail_epilogue") else None
+        if ep is not None:
+            tail.epilogue = (covers, ep + (tuple(ring_push) if ring_push is not None else ()))
+        table._s3d_fused_arm["tail"] = tail
+        tail.armed = True
+        return True
+
     def disarm_fused_tables(self):
         for group in self.param_groups:
             for p in group["params"]:
@@ -312,6 +375,7 @@ class NativeGradScaler:
         self._found_inf = torch.zeros(1, dtype=torch.float32, device=device)
         self._one = torch.ones(1, dtype=torch.float32, device=device)  # unit inverse scale of the multi-tensor check
         self._advance = None  # step count of the optimizer whose advance rides in update()'s launch
+        self._tail_done = False  # this step's update() already ran inside the hash table's backward (NativeAdam.arm_step_tail)
 
     def scale(self, loss):
         return loss * self._scale.to(loss.dtype) if self.enabled else loss
@@ -430,9 +494,20 @@ class NativeGradScaler:
         while pending:
             dist.finish_chunk(pending.pop(0))
 
+    def tail_epilogue(self, optimizer):
+        """the arguments of this step's update() as a step tail takes them (the optimizer's step-count advance folded in, as
+        step() will fold it), or None when update() is not that one launch"""
+        if not self.enabled or self._advance is not None or getattr(optimizer, "step_count", None) is None:
+            return None
+        return (self._scale, self._growth_tracker, self.growth_factor, self.backoff_factor, self.growth_interval, optimizer.step_count)
+
     def update(self, ring_push=None):
         """`ring_push` = (loss, counter, loss_ring, counter_ring, cursor): a graph-replayed trainer's end-of-step bookkeeping
         (OptimBackend.step_ring_push) rides in the same single-thread launch"""
+        if self._tail_done:  # (scale, flag, step count and rings were moved by the last workgroup of the hash table's backward)
+            self._tail_done = False
+            self._advance = None
+            return
         if self.enabled and ring_push is not None:
             _backend.step_epilogue(self._scale, self._growth_tracker, self._found_inf, self.growth_factor, self.backoff_factor,
                                    self.growth_interval, self._advance, *ring_push)

@@ -254,10 +254,15 @@ class Trainer:
         # without data parallelism the gradients are simply replaced each step (no 49 MB zero fill + 147 MB accumulate);
         # with it they live in the flat all-reduce bucket and are cleared in place
         self.optimizer.zero_grad(set_to_none=self.dist is None)
-        with torch.autocast("cuda", dtype=torch.float16, enabled=self.fp16):
-            out = model.render(rays_o, rays_d, bg_color=bg_color, perturb=True, force_all_rays=False,
-                               defer_background=self.native_optim, fused_loss=self._fused_loss(gt_rgb), **self.render_kwargs)
-            loss = self._regularized(render_loss(out, gt_rgb, self._expected_grad(), error_map=self._em_batch))
+        self._open_step_tail()
+        try:
+            with torch.autocast("cuda", dtype=torch.float16, enabled=self.fp16):
+                out = model.render(rays_o, rays_d, bg_color=bg_color, perturb=True, force_all_rays=False,
+                                   defer_background=self.native_optim, fused_loss=self._fused_loss(gt_rgb), **self.render_kwargs)
+                loss = self._regularized(render_loss(out, gt_rgb, self._expected_grad(), error_map=self._em_batch))
+        except BaseException:
+            self._drop_step_tail()
+            raise
         self._backward(loss)
         self._reduce_and_step()
         return loss.detach()
@@ -300,29 +305,68 @@ class Trainer:
     # the hash tables' Adam inside their backward's accumulate kernel (nerf/optim.py: arm_fused_tables); S3D_FUSE_TABLE_ADAM=0: A/B
     fuse_table_updates = __import__("os").environ.get("S3D_FUSE_TABLE_ADAM", "1") != "0"
 
+    def _fused_tables_allowed(self):
+        opt, sc = self.optimizer, self.scaler
+        if getattr(self.model, "bg_radius", 0) > 0:
+            return False  # (the background model's backward is not ordered behind the tables': their updates stay in step())
+        if not (self.fuse_table_updates and self.native_optim and self.dist is None and hasattr(opt, "arm_fused_tables")
+                and hasattr(sc, "_checked_at_source")):
+            return False
+        params = [p for g in opt.param_groups for p in g["params"]]
+        return all(getattr(p, "_s3d_grad", None) is not None for p in params) and sc._checked_at_source(opt)
+
     def _arm_fused_tables(self):
         """single replica, native optimizer + scaler, every gradient of the step a hand-over buffer whose producer raises the
         scaler's flag itself: the step's skip decision is complete when the tables' backward — the last node of the graph —
         starts, so their update can be applied there.  (Seal's nn.Linear `.grad`s without a pack, TensoRF's factors, data
         parallelism: the separate update as before.)"""
-        opt, sc = self.optimizer, self.scaler
-        if getattr(self.model, "bg_radius", 0) > 0:
-            return 0  # (the background model's backward is not ordered behind the tables': their updates stay in step())
-        if not (self.fuse_table_updates and self.native_optim and self.dist is None and hasattr(opt, "arm_fused_tables")
-                and hasattr(sc, "_checked_at_source")):
+        if not self._fused_tables_allowed():
             return 0
-        params = [p for g in opt.param_groups for p in g["params"]]
-        if not all(getattr(p, "_s3d_grad", None) is not None for p in params) or not sc._checked_at_source(opt):
-            return 0
-        return opt.arm_fused_tables(grad_scale=sc._scale if sc.enabled else None)
+        sc = self.scaler
+        return self.optimizer.arm_fused_tables(grad_scale=sc._scale if sc.enabled else None)
+
+    # The step's small closing launches — the MLPs' weight-gradient reduce and Adam, the criterion's sum, the scaler's update with
+    # the ring push — inside the hash table's backward (s3d_hip.StepTail, NativeAdam.arm_step_tail).  False: the separate
+    # launches (A/B runs, parity tests)
+    fuse_step_tail = True
+    _tail = None
+
+    def _open_step_tail(self):
+        """Before the step's render: a holder for the closing launches, where the tables' update may ride at all (one replica, no
+        background model, ...: `_fused_tables_allowed`).  The criterion's sum is filed in it when nothing reads the loss value
+        before the backward pass (no regularizer is added to it)."""
+        import s3d_hip
+        if s3d_hip.StepTail.current is not None:
+            s3d_hip.StepTail.current.close()  # (a step that ended in an exception)
+        self._tail = None
+        if not (self.fuse_step_tail and getattr(self.scaler, "enabled", False) and self._fused_tables_allowed()
+                and hasattr(self.optimizer, "arm_step_tail")):
+            return
+        self._tail = s3d_hip.StepTail.current = s3d_hip.StepTail()
+        self._tail.accept_loss = type(self)._regularizer is Trainer._regularizer and type(self)._regularized is Trainer._regularized
+
+    def _drop_step_tail(self):
+        """the step failed before its backward pass: nobody may find its holder (nothing it holds is launched)"""
+        import s3d_hip
+        if self._tail is not None and s3d_hip.StepTail.current is self._tail:
+            s3d_hip.StepTail.current = None
+        self._tail = None
 
     def _backward(self, loss):
         """the step's ONE backward pass (every caller follows it with `_reduce_and_step`)"""
-        self._arm_fused_tables()
-        if hasattr(self.scaler, "backward"):  # NativeGradScaler: the scale is passed as the root gradient
-            self.scaler.backward(loss)
-        else:
-            self.scaler.scale(loss).backward()
+        n = self._arm_fused_tables()
+        tail, self._tail = self._tail, None
+        if tail is not None and not (n == 1 and self.optimizer.arm_step_tail(tail, self.scaler, getattr(self, "_ring_args", None))):
+            tail.close()  # (no table, or two of them: a filed criterion sum is launched now, everything else as always)
+            tail = None
+        try:
+            if hasattr(self.scaler, "backward"):  # NativeGradScaler: the scale is passed as the root gradient
+                self.scaler.backward(loss)
+            else:
+                self.scaler.scale(loss).backward()
+        finally:
+            if tail is not None:
+                tail.close()  # (whatever was filed and not taken by the table's backward — it did not run — is launched here)
 
     def train_step(self, rays_o, rays_d, gt_rgb, bg_color=1, index=None, inds_coarse=None):
         """rays_o/d [N,3], gt_rgb [N,3].  Returns the (detached) loss tensor; no host sync.  `index` / `inds_coarse` (a batch
@@ -412,10 +456,16 @@ class GraphedTrainer(Trainer):
 
     def _static_loss(self):
         """the step's loss on the static input buffers (subclasses: other criteria, e.g. Seal's depth term)"""
-        with torch.autocast("cuda", dtype=torch.float16, enabled=self.fp16):
-            out = self.model.render(self.s_ro, self.s_rd, bg_color=self.s_bg if self._graph_bg else 1, perturb=True, force_all_rays=False,
-                                    defer_background=self.native_optim, fused_loss=self._fused_loss(self.s_gt), **self.render_kwargs)
-            return self._regularized(render_loss(out, self.s_gt, self._expected_grad(), error_map=self._em_batch))
+        self._open_step_tail()
+        try:
+            with torch.autocast("cuda", dtype=torch.float16, enabled=self.fp16):
+                out = self.model.render(self.s_ro, self.s_rd, bg_color=self.s_bg if self._graph_bg else 1, perturb=True,
+                                        force_all_rays=False, defer_background=self.native_optim,
+                                        fused_loss=self._fused_loss(self.s_gt), **self.render_kwargs)
+                return self._regularized(render_loss(out, self.s_gt, self._expected_grad(), error_map=self._em_batch))
+        except BaseException:
+            self._drop_step_tail()
+            raise
 
     def _body_fb(self):
         """zero grads -> render -> loss -> scaled backward"""
@@ -423,16 +473,15 @@ class GraphedTrainer(Trainer):
         # with it they live in the flat all-reduce bucket and are cleared in place
         self.optimizer.zero_grad(set_to_none=self.dist is None)
         loss = self._static_loss()
+        self._ring_args = None
+        if self._counter_ring is not None and self.native_optim:
+            # rides in the scaler update's launch (_body_opt), or with it in the hash table's backward (Trainer.fuse_step_tail)
+            self._ring_args = (loss.detach().float().reshape(()), self.s_counter, self.loss_ring, self._counter_ring, self.s_cursor)
         self._backward(loss)
         loss = loss.detach()
-        self._ring_args = None
-        if self._counter_ring is not None:
-            args = (loss.float().reshape(()), self.s_counter, self.loss_ring, self._counter_ring, self.s_cursor)
-            if self.native_optim:
-                self._ring_args = args  # rides in the scaler update's launch (_body_opt)
-            else:
-                import s3d_hip
-                s3d_hip.OptimBackend.step_ring_push(*args)
+        if self._counter_ring is not None and not self.native_optim:
+            import s3d_hip
+            s3d_hip.OptimBackend.step_ring_push(loss.float().reshape(()), self.s_counter, self.loss_ring, self._counter_ring, self.s_cursor)
         return loss
 
     def _body_opt(self):

@@ -270,9 +270,12 @@ class _CompositeRaysTrainLoss(Function):
             workspace = torch.empty(4 * N, dtype=torch.float32, device=dev)
         if gt_depth is not None:
             gt_depth = gt_depth.float().contiguous().view(-1)
+        tail = _loss_tail()
         _backend.composite_rays_train_loss(sigmas, rgbs, deltas, rays, M, N, T_thresh, gt, bg, expected_grad, weights_sum, depth,
                                            image, grad_sigmas, grad_rgbs, loss, workspace, gt_depth=gt_depth,
-                                           depth_weight=float(depth_weight))
+                                           depth_weight=float(depth_weight), **({} if tail is None else {"defer_reduce": True}))
+        if tail is not None:  # the sum of the terms rides in the hash table's backward (s3d_hip.StepTail)
+            tail.loss = (workspace, N, gt_depth is not None, float(depth_weight), loss)
         ctx.pre = (grad_sigmas, grad_rgbs, expected_grad.data_ptr(), expected_grad._version)
         ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, image, gt)
         ctx.dims = (M, N, T_thresh, bg)
@@ -330,9 +333,12 @@ class _CompositeRaysTrainLossBg(Function):
             workspace = torch.empty(4 * N, dtype=torch.float32, device=dev)
         if gt_depth is not None:
             gt_depth = gt_depth.float().contiguous().view(-1)
+        tail = _loss_tail()
         _backend.composite_rays_train_loss_bg(sigmas, rgbs, deltas, rays, M, N, T_thresh, gt, bg, expected_grad, weights_sum, depth,
                                               image, grad_sigmas, grad_rgbs, grad_bg, loss, workspace, gt_depth=gt_depth,
-                                              depth_weight=float(depth_weight))
+                                              depth_weight=float(depth_weight), **({} if tail is None else {"defer_reduce": True}))
+        if tail is not None:
+            tail.loss = (workspace, N, gt_depth is not None, float(depth_weight), loss)
         ctx.pre = (grad_sigmas, grad_rgbs, grad_bg, expected_grad.data_ptr(), expected_grad._version)
         ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, image, gt, bg)
         ctx.dims = (M, N, T_thresh)
@@ -377,6 +383,15 @@ def composite_rays_train_loss_bg(sigmas, rgbs, deltas, rays, T_thresh, gt, bg, e
 def _head():
     import s3d_hip
     return s3d_hip.NgpHeadBackend
+
+
+def _loss_tail():
+    """the step tail that takes this criterion's one-workgroup sum (s3d_hip.StepTail, opened by the trainer), or None"""
+    if not hasattr(_backend, "loss_terms_reduce"):
+        return None
+    import s3d_hip
+    tail = s3d_hip.StepTail.current
+    return tail if (tail is not None and tail.accept_loss and tail.loss is None) else None
 
 
 def composite_rays_train_loss(sigmas, rgbs, deltas, rays, T_thresh, gt, bg, expected_grad, workspace=None, gt_depth=None,

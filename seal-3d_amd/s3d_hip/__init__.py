@@ -44,7 +44,7 @@ EXPORTS = [
     "s3d_grads_nonfinite", "s3d_adam_step", "s3d_adam_step_multi", "s3d_adam_advance", "s3d_scaler_update", "s3d_step_ring_push", "s3d_step_epilogue",
     "s3d_ngp_mid_forward", "s3d_ngp_mid_backward", "s3d_ngp_mid2_forward", "s3d_ngp_mid2_backward", "s3d_ngp_rgb_forward", "s3d_ngp_rgb_backward",
     "s3d_bg_mse_forward", "s3d_bg_mse_backward", "s3d_bg_targets", "s3d_l1_pair_workspace_size", "s3d_l1_pair_loss",
-    "s3d_seal_bbox_map", "s3d_seal_map_color", "s3d_seal_map_color_image", "s3d_seal_brush_map", "s3d_seal_anchor_map", "s3d_grid_encode_backward_adam", "s3d_vm_features_forward",
+    "s3d_seal_bbox_map", "s3d_seal_map_color", "s3d_seal_map_color_image", "s3d_seal_brush_map", "s3d_seal_anchor_map", "s3d_grid_encode_backward_adam", "s3d_grid_encode_backward_adam_tail", "s3d_loss_terms_reduce", "s3d_vm_features_forward",
     "s3d_aabb_normalize", "s3d_weighted_abs_sum_workspace_size", "s3d_weighted_abs_sum", "s3d_pack_linear_chain", "s3d_unpack_linear_chain",
     "s3d_vm_backward_max_bins", "s3d_vm_backward_keys", "s3d_vm_backward_bins_workspace_size", "s3d_vm_backward_bins",
     "s3d_vm_backward_stage_bytes", "s3d_vm_transpose_factors",
@@ -185,6 +185,55 @@ def active_row_limit(B):
     if _ROW_LIMIT is not None and _ROW_LIMIT[1] == int(B):
         return _ROW_LIMIT[0]
     return None
+
+
+class StepTail:
+    """The small launches that end a training step, collected while the step is issued so that the hash table's backward — the
+    last node of the step — can run them inside its own two launches (GridBackend.grid_encode_backward_adam_tail).  A trainer
+    opens one per step (nerf/trainer.py: Trainer.fuse_step_tail); producers file their part instead of launching it:
+      loss     raymarching: the sum of the criterion's per-ray terms          (workspace, N, with_depth, depth_weight, loss)
+      reduce   ffmlp: the weight-gradient reduce of the two networks           (a, b) of FFMLPBackend.wgrad_reduce_pair
+      adam     nerf/optim.py: the update of the parameters in `adam_params`    built by `adam_items` when the table's backward runs
+      epilogue nerf/optim.py: the scaler's update (+ the trainer's ring push)  arguments of scaler_update / step_epilogue
+    `armed`: a table's backward will take the tail (set by the trainer once exactly one table is armed); until then only the loss
+    may be filed.  `flush()` issues whatever was filed and not taken as its ordinary launches.  The holder keeps every tensor it
+    was handed alive until then: under graph capture a freed block would be handed to the next allocation."""
+    current = None
+
+    def __init__(self):
+        self.loss = self.reduce = self.epilogue = None
+        self.adam_params, self.adam_items, self.on_applied = [], None, None
+        self.armed = False
+        self.accept_loss = False  # the step reads the loss value only after the table's backward (no regularizer is added to it)
+        self.applied = 0  # TAIL_* bits of the parts that ran inside the table's backward
+
+    def take(self):
+        """the `tail` dict of grid_encode_backward_adam_tail; what it names is issued by that call, one way or the other"""
+        t = dict(loss=self.loss, reduce=self.reduce)
+        items = self.adam_items(self.adam_params) if (self.adam_items is not None and self.adam_params) else None
+        if items:
+            t["adam"] = items
+        if self.epilogue is not None and (items or not self.adam_params) and self.epilogue[0](self.adam_params):
+            t["epilogue"] = self.epilogue[1]
+        self.loss = self.reduce = None
+        return t
+
+    def done(self, parts):
+        self.applied = parts
+        if self.on_applied is not None:
+            self.on_applied(self, parts)
+
+    def flush(self):
+        if self.reduce is not None:
+            FFMLPBackend.wgrad_reduce_pair(*self.reduce)
+        if self.loss is not None:
+            RaymarchingBackend.loss_terms_reduce(*self.loss)
+        self.loss = self.reduce = None
+
+    def close(self):
+        self.flush()
+        if StepTail.current is self:
+            StepTail.current = None
 
 
 def _shadow2(shadows):
@@ -489,22 +538,32 @@ class RaymarchingBackend:
     @staticmethod
     def composite_rays_train_loss(sigmas, rgbs, deltas, rays, M, N, T_thresh, gt, bg_rgb, grad_loss, weights_sum, depth, image,
                                   grad_sigmas, grad_rgbs, loss, workspace, gt_depth=None, depth_weight=1.0, grad_image=None,
-                                  grad_weights_sum=None):
+                                  grad_weights_sum=None, defer_reduce=False):
         """composite forward + background / MSE loss (announced upstream gradient `grad_loss`) + composite backward of one ray batch
-        in one launch + a one-workgroup sum of the loss terms (seal3d_hip.h); workspace: 4N floats of scratch"""
+        in one launch + a one-workgroup sum of the loss terms (seal3d_hip.h); workspace: 4N floats of scratch.  `defer_reduce`:
+        the sum is left to a later loss_terms_reduce / step tail on the same workspace (`loss` is not written by this call)"""
         RaymarchingBackend._check_train_loss(
             "composite_rays_train_loss", M, N, gt_depth, grad_image, grad_weights_sum, ("gt",), sigmas=sigmas, rgbs=rgbs, deltas=deltas,
             gt=gt, grad_loss=grad_loss, loss=loss, workspace=workspace, grad_sigmas=grad_sigmas, grad_rgbs=grad_rgbs)
         bg = (C.c_float * 3)(*[float(v) for v in bg_rgb])
         _check(lib().s3d_composite_rays_train_loss(_p(sigmas), _p(rgbs), _p(deltas), _p(rays), _u(M), _u(N), _f(T_thresh), _p(gt), bg,
                                                    _p(grad_loss), _p(gt_depth), _f(depth_weight), _p(weights_sum), _p(depth), _p(image),
-                                                   _p(grad_sigmas), _p(grad_rgbs), _p(grad_image), _p(grad_weights_sum), _p(loss),
-                                                   _p(workspace), _stream()), "composite_rays_train_loss")
+                                                   _p(grad_sigmas), _p(grad_rgbs), _p(grad_image), _p(grad_weights_sum),
+                                                   _p(None if defer_reduce else loss), _p(workspace), _stream()), "composite_rays_train_loss")
+
+    @staticmethod
+    def loss_terms_reduce(workspace, N, with_depth, depth_weight, loss):
+        """the one-workgroup sum a composite_rays_train_loss(defer_reduce=True) call left out (seal3d_hip.h)"""
+        _need(workspace, torch.float32, "workspace"); _need(loss, torch.float32, "loss")
+        if workspace.numel() < 4 * N:
+            raise RuntimeError("loss_terms_reduce: workspace holds 4N floats")
+        _check(lib().s3d_loss_terms_reduce(_p(workspace), _u(N), C.c_int(int(bool(with_depth))), _f(depth_weight), _p(loss), _stream()),
+               "loss_terms_reduce")
 
     @staticmethod
     def composite_rays_train_loss_bg(sigmas, rgbs, deltas, rays, M, N, T_thresh, gt, bg, grad_loss, weights_sum, depth, image,
                                      grad_sigmas, grad_rgbs, grad_bg, loss, workspace, gt_depth=None, depth_weight=1.0,
-                                     grad_image=None, grad_weights_sum=None):
+                                     grad_image=None, grad_weights_sum=None, defer_reduce=False):
         """composite_rays_train_loss with a per-ray background bg [N,3] (device) and its gradient grad_bg [N,3] (seal3d_hip.h);
         grad_bg None: a background that needs no gradient (the random background of RGBA frames)"""
         with_grad = {} if grad_bg is None else {"grad_bg": grad_bg}
@@ -515,7 +574,8 @@ class RaymarchingBackend:
         _check(lib().s3d_composite_rays_train_loss_bg(_p(sigmas), _p(rgbs), _p(deltas), _p(rays), _u(M), _u(N), _f(T_thresh), _p(gt),
                                                       _p(bg), _p(grad_loss), _p(gt_depth), _f(depth_weight), _p(weights_sum), _p(depth),
                                                       _p(image), _p(grad_sigmas), _p(grad_rgbs), _p(grad_image), _p(grad_weights_sum),
-                                                      _p(grad_bg), _p(loss), _p(workspace), _stream()), "composite_rays_train_loss_bg")
+                                                      _p(grad_bg), _p(None if defer_reduce else loss), _p(workspace), _stream()),
+               "composite_rays_train_loss_bg")
 
     zero_fills_march_rays = True  # march_rays(zero_unfilled=True): the kernel writes the zeros of the unfilled slots itself
 
@@ -653,6 +713,17 @@ class GridBackend:
                     ("step", C.c_void_p), ("grad_scale", C.c_void_p), ("lr_scale", C.c_void_p)]
 
     @staticmethod
+    def _grid_adam(adam):
+        ga = GridBackend._GridAdam()
+        ga.param, ga.exp_avg, ga.exp_avg_sq = adam["param"].data_ptr(), adam["exp_avg"].data_ptr(), adam["exp_avg_sq"].data_ptr()
+        ga.param_half = adam["param_half"].data_ptr() if adam.get("param_half") is not None else None
+        ga.lr, (ga.beta1, ga.beta2), ga.eps = float(adam["lr"]), adam["betas"], float(adam["eps"])
+        ga.step = adam["step"].data_ptr()
+        ga.grad_scale = adam["grad_scale"].data_ptr() if adam.get("grad_scale") is not None else None
+        ga.lr_scale = adam["lr_scale"].data_ptr() if adam.get("lr_scale") is not None else None
+        return ga
+
+    @staticmethod
     def grid_encode_backward_adam(grad, inputs, embeddings, offsets, grad_embeddings, B, D, Cc, L, S, H, gridtype, align_corners,
                                   interp, adam, bound=0.0, n_valid=None, found_inf=None):
         """backward of a table with its Adam update inside the accumulate kernel (include/seal3d_hip.h:
@@ -669,13 +740,7 @@ class GridBackend:
             if adam[k].shape != embeddings.shape or not adam[k].is_contiguous():
                 raise RuntimeError(f"adam[{k!r}] must be a contiguous fp32 tensor of the table's shape")
         mlr, ws, ctl = GridBackend._backward_buffers(grad, offsets, B, D, Cc, L)
-        ga = GridBackend._GridAdam()
-        ga.param, ga.exp_avg, ga.exp_avg_sq = adam["param"].data_ptr(), adam["exp_avg"].data_ptr(), adam["exp_avg_sq"].data_ptr()
-        ga.param_half = adam["param_half"].data_ptr() if adam.get("param_half") is not None else None
-        ga.lr, (ga.beta1, ga.beta2), ga.eps = float(adam["lr"]), adam["betas"], float(adam["eps"])
-        ga.step = adam["step"].data_ptr()
-        ga.grad_scale = adam["grad_scale"].data_ptr() if adam.get("grad_scale") is not None else None
-        ga.lr_scale = adam["lr_scale"].data_ptr() if adam.get("lr_scale") is not None else None
+        ga = GridBackend._grid_adam(adam)
         applied = C.c_int(0)
         _check(lib().s3d_grid_encode_backward_adam(_p(grad), _p(inputs), _p(embeddings), _p(offsets), _p(grad_embeddings), _u(mlr), _u(B),
                                                    _u(D), _u(Cc), _u(L), _f(S), _u(H), _u(gridtype), C.c_int(int(align_corners)), _u(interp),
@@ -683,6 +748,85 @@ class GridBackend:
                                                    _p(found_inf), _p(ctl), C.c_size_t(ctl.numel() if ctl is not None else 0),
                                                    C.byref(ga), C.byref(applied), _stream()), "grid_encode_backward_adam")
         return bool(applied.value)
+
+    class _StepTail(C.Structure):
+        """seal3d_hip.h: s3d_step_tail"""
+        _net = lambda x: [("workspace_" + x, C.c_void_p), ("B_" + x, C.c_uint32), ("input_dim_" + x, C.c_uint32),
+                          ("hidden_dim_" + x, C.c_uint32), ("num_layers_" + x, C.c_uint32), ("grad_weights_" + x, C.c_void_p),
+                          ("accumulate_" + x, C.c_int), ("found_inf_" + x, C.c_void_p)]
+        _fields_ = _net("a") + _net("b") + [
+            ("loss_workspace", C.c_void_p), ("loss_N", C.c_uint32), ("loss_with_depth", C.c_int), ("loss_depth_weight", C.c_float),
+            ("loss", C.c_void_p), ("tensors", C.c_void_p), ("n_tensors", C.c_int32), ("scale", C.c_void_p),
+            ("growth_tracker", C.c_void_p), ("growth_factor", C.c_float), ("backoff_factor", C.c_float),
+            ("growth_interval", C.c_int32), ("adam_step", C.c_void_p), ("ring_loss", C.c_void_p), ("counter", C.c_void_p),
+            ("loss_ring", C.c_void_p), ("counter_ring", C.c_void_p), ("cursor", C.c_void_p), ("ring", C.c_int32),
+            ("loss_slots", C.c_int32)]
+
+    TAIL_WGRAD_REDUCE, TAIL_LOSS, TAIL_ADAM, TAIL_EPILOGUE = 1, 2, 4, 8
+
+    @staticmethod
+    def grid_encode_backward_adam_tail(grad, inputs, embeddings, offsets, grad_embeddings, B, D, Cc, L, S, H, gridtype, align_corners,
+                                       interp, adam, tail, bound=0.0, n_valid=None, found_inf=None):
+        """grid_encode_backward_adam with a step tail (include/seal3d_hip.h: s3d_grid_encode_backward_adam_tail).  `tail`: dict of
+        optional parts — reduce=(a, b) as for FFMLPBackend.wgrad_reduce_pair, loss=(workspace, N, with_depth, depth_weight, loss)
+        as for RaymarchingBackend.loss_terms_reduce, adam=items as for OptimBackend.adam_step_multi, epilogue=(scale,
+        growth_tracker, growth_factor, backoff_factor, growth_interval, adam_step[, loss, counter, loss_ring, counter_ring,
+        cursor]) as for OptimBackend.scaler_update / step_epilogue.  Returns (applied, TAIL_* bits of the parts that ran inside
+        the backward's launches); a call that falls back has issued reduce and loss as ordinary launches in front."""
+        _need(inputs, torch.float32, "inputs")
+        if found_inf is not None:
+            _need(found_inf, torch.float32, "found_inf")
+        if grad_embeddings.dtype != grad.dtype:
+            raise RuntimeError("grad_embeddings must have the dtype of grad")
+        for k in ("param", "exp_avg", "exp_avg_sq"):
+            _need(adam[k], torch.float32, k)
+            if adam[k].shape != embeddings.shape or not adam[k].is_contiguous():
+                raise RuntimeError(f"adam[{k!r}] must be a contiguous fp32 tensor of the table's shape")
+        mlr, ws, ctl = GridBackend._backward_buffers(grad, offsets, B, D, Cc, L)
+        ga = GridBackend._grid_adam(adam)
+        st = GridBackend._StepTail()
+        if tail.get("reduce") is not None:
+            for x, (ws_x, B_x, in_x, hid_x, nl_x, gw_x, acc_x, fi_x) in zip("ab", tail["reduce"]):
+                _need(gw_x, torch.float16, "grad_weights")
+                for name, v in (("workspace_", _p(ws_x)), ("B_", int(B_x)), ("input_dim_", int(in_x)), ("hidden_dim_", int(hid_x)),
+                                ("num_layers_", int(nl_x)), ("grad_weights_", _p(gw_x)), ("accumulate_", int(bool(acc_x))),
+                                ("found_inf_", _p(fi_x))):
+                    setattr(st, name + x, v)
+        if tail.get("loss") is not None:
+            lws, lN, ldepth, lw, loss = tail["loss"]
+            _need(lws, torch.float32, "workspace"); _need(loss, torch.float32, "loss")
+            if lws.numel() < 4 * lN:
+                raise RuntimeError("step tail: the loss workspace holds 4N floats")
+            st.loss_workspace, st.loss_N, st.loss_with_depth, st.loss_depth_weight, st.loss = _p(lws), int(lN), int(bool(ldepth)), float(lw), _p(loss)
+        arr = OptimBackend._adam_tensors(tail.get("adam") or [])
+        st.tensors, st.n_tensors = C.cast(arr, C.c_void_p), len(arr)
+        if tail.get("epilogue") is not None:
+            ep = tail["epilogue"]
+            scale, tracker, growth, backoff, interval, adam_step = ep[:6]
+            _need(scale, torch.float32, "scale"); _need(tracker, torch.int32, "growth_tracker")
+            if adam_step is not None:
+                _need(adam_step, torch.float32, "adam_step")
+            st.scale, st.growth_tracker, st.growth_factor, st.backoff_factor = _p(scale), _p(tracker), float(growth), float(backoff)
+            st.growth_interval, st.adam_step = int(interval), _p(adam_step)
+            if len(ep) > 6:
+                loss, counter, loss_ring, counter_ring, cursor = ep[6:11]
+                _need(counter, torch.int32, "counter"); _need(counter_ring, torch.int32, "counter_ring"); _need(cursor, torch.int32, "cursor")
+                if loss is not None:
+                    _need(loss, torch.float32, "loss"); _need(loss_ring, torch.float32, "loss_ring")
+                ring = counter_ring.shape[0]
+                if cursor.numel() < 2 or counter_ring.numel() != 2 * ring or (loss is not None and loss_ring.numel() < 1):
+                    raise RuntimeError("step tail: cursor is int32[2], rings are [ring, 2] / [loss_slots]")
+                st.ring_loss, st.counter, st.loss_ring = _p(loss), _p(counter), _p(loss_ring if loss is not None else None)
+                st.counter_ring, st.cursor, st.ring = _p(counter_ring), _p(cursor), int(ring)
+                st.loss_slots = 0 if loss is None or loss_ring.numel() == ring else loss_ring.numel()
+        applied, parts = C.c_int(0), C.c_uint32(0)
+        _check(lib().s3d_grid_encode_backward_adam_tail(_p(grad), _p(inputs), _p(embeddings), _p(offsets), _p(grad_embeddings), _u(mlr),
+                                                        _u(B), _u(D), _u(Cc), _u(L), _f(S), _u(H), _u(gridtype),
+                                                        C.c_int(int(align_corners)), _u(interp), C.c_int(_dt(grad)), _p(ws),
+                                                        C.c_size_t(ws.numel()), _f(bound), _nv(n_valid), _p(found_inf), _p(ctl),
+                                                        C.c_size_t(ctl.numel() if ctl is not None else 0), C.byref(ga), C.byref(st),
+                                                        C.byref(applied), C.byref(parts), _stream()), "grid_encode_backward_adam_tail")
+        return bool(applied.value), int(parts.value)
 
     _backward_path = 0  # `path` argument of s3d_grid_encode_backward (binding-side state for tests / experiments)
 
@@ -909,6 +1053,13 @@ class OptimBackend:
         adam_step for all of them in one launch; `consume_grads` (all tensors) / the optional tenth element (that tensor): the
         gradient is cleared behind the read; eleventh element: coefficient of an L1 penalty whose gradient the update adds
         (seal3d_hip.h)"""
+        arr = OptimBackend._adam_tensors(items)
+        _check(lib().s3d_adam_step_multi(arr, C.c_int32(len(items)), _p(step), _p(grad_scale), _p(found_inf), _p(lr_scale),
+                                         C.c_int(int(bool(consume_grads))), _stream()), "adam_step_multi")
+
+    @staticmethod
+    def _adam_tensors(items):
+        """the s3d_adam_tensor array of adam_step_multi's `items`"""
         arr = (_AdamTensor * len(items))()
         for a, item in zip(arr, items):
             param, grad, exp_avg, exp_avg_sq, param_half, lr, beta1, beta2, eps = item[:9]
@@ -935,8 +1086,7 @@ class OptimBackend:
             a.n = param.numel()
             a.lr, a.beta1, a.beta2, a.eps = float(lr), float(beta1), float(beta2), float(eps)
             a.grad_dtype = _dt(grad)
-        _check(lib().s3d_adam_step_multi(arr, C.c_int32(len(items)), _p(step), _p(grad_scale), _p(found_inf), _p(lr_scale),
-                                         C.c_int(int(bool(consume_grads))), _stream()), "adam_step_multi")
+        return arr
 
     @staticmethod
     def scaler_update(scale, growth_tracker, found_inf, growth_factor, backoff_factor, growth_interval, adam_step=None):
