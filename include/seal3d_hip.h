@@ -824,6 +824,25 @@ int s3d_error_map_update(float* error_map, uint32_t n_img, const int64_t* index,
                          const float* image, const float* weights_sum, const float* gt, const float* bg_rgb, const float* bg_rays,
                          const float* depth, const float* gt_depth, float depth_weight, s3d_stream_t stream);
 
+/* Build extension — mesh export: marching cubes over a dense fp32 volume u [nx,ny,nz] (C order, z fastest); DESIGN.md §8.
+ * A grid point is solid iff u > iso, with NaN read as 0 and +-inf as +-FLT_MAX (u is not modified).  Point p owns its +x, +y,
+ * +z edges; a crossing edge (exactly one solid end) gives one welded vertex at lo + t along its axis, t = (iso - f_lo) /
+ * (f_hi - f_lo) in fp32 (kept inside [0, 1]), lo the owning point.  Vertices are ordered by the owner's linear index
+ * (x ny + y) nz + z, then x-, y-, z-edge; world = v / (n_axis - 1) * (max - min) + min per axis.  Triangles are ordered by cell
+ * linear index over the (nx-1)(ny-1)(nz-1) cells and by the generated case table (csrc/mc_tables.h) inside a cell, normals from
+ * solid to non-solid.  Any axis < 2 or nx ny nz >= 2^31: error (s3d_mc_workspace_bytes: 0), nothing is launched.
+ * s3d_mc_workspace_bytes (host): bytes of `workspace` (16-byte aligned), at most 16 per grid point.
+ * s3d_mc_count: classify + count + device-wide exclusive scan into `workspace`; totals [2] uint32 on the device = {V, T}
+ * (both 0xFFFFFFFF when a count does not fit).
+ * s3d_mc_emit: vertices [V,3] fp32, triangles [T,3] int32 from the same u / iso and the workspace s3d_mc_count filled; bounds
+ * [6] fp32 on the device = {min xyz, max xyz}.  It reads the counted totals back (one stream synchronisation) and returns an
+ * error, launching nothing, unless V and T equal them; the kernel never writes at or past row V / T. */
+size_t s3d_mc_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
+int s3d_mc_count(const float* u, uint32_t nx, uint32_t ny, uint32_t nz, float iso, void* workspace, uint32_t* totals,
+                 s3d_stream_t stream);
+int s3d_mc_emit(const float* u, uint32_t nx, uint32_t ny, uint32_t nz, float iso, const void* workspace, const float* bounds,
+                float* vertices, uint32_t V, int32_t* triangles, uint32_t T, s3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

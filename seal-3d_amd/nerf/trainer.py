@@ -3,6 +3,7 @@ Adam, with fp16 autocast + GradScaler (`-O`), `update_extra_state` every 16 step
 Adam(betas=(0.9, 0.99), eps=1e-15) and lr 1e-2 (main_SealNeRF.py:283-288), PSNR as in nerf/utils.py:226-233.
 Optional data parallelism over rays: gradients are all-reduced through one flat bucket (parallel/dist.py)."""
 import math
+import os
 
 import torch
 import torch.nn.functional as F
@@ -174,6 +175,7 @@ class Trainer:
             self.rebuild_optimizer()
         self.global_step = 0
         self.epoch = 0
+        self.workspace, self.name = None, "ngp"  # where save_mesh puts a file it is given no path for
         # the training set's error map (nerf/utils.py:616 `self.error_map = train_loader._data.error_map`): with it, steps that
         # are handed `index` / `inds_coarse` fold their per-ray errors into it (update_error_map)
         self.error_map = None
@@ -382,6 +384,18 @@ class Trainer:
         finally:
             self._em_batch = None
         return loss
+
+    def save_mesh(self, save_path=None, resolution=256, threshold=10):
+        """nerf/utils.py:583-603: the model's density > threshold surface on the resolution^3 lattice of aabb_infer, as a PLY
+        (default <workspace>/meshes/<name>_<epoch>.ply).  Field and marching cubes stay on the device (nerf/mesh.py); the
+        model is only read, so a captured step replays unchanged afterwards."""
+        from .mesh import save_mesh
+        if save_path is None:
+            if self.workspace is None:
+                raise ValueError("save_mesh: no save_path, and the trainer has no `workspace` to derive one from")
+            save_path = os.path.join(self.workspace, "meshes", f"{self.name}_{self.epoch}.ply")
+        save_mesh(self.model, save_path, resolution=resolution, threshold=threshold, fp16=self.fp16)
+        return save_path
 
     @torch.no_grad()
     def render_image(self, rays_o, rays_d, bg_color=1):

@@ -53,6 +53,7 @@ EXPORTS = [
     "s3d_background_forward", "s3d_background_backward_workspace_size", "s3d_background_backward",
     "s3d_vm_background_forward", "s3d_vm_background_backward_workspace_size", "s3d_vm_background_backward",
     "s3d_sample_train_rays", "s3d_error_map_update", "s3d_sample_train_rays_rgba", "s3d_rgba_targets",
+    "s3d_mc_workspace_bytes", "s3d_mc_count", "s3d_mc_emit",
 ]
 
 
@@ -83,7 +84,7 @@ def lib():
                      "s3d_grid_encode_backward_control_size", "s3d_l1_pair_workspace_size",
                      "s3d_sweep_update_workspace_size", "s3d_sweep_draw_native_workspace_size", "s3d_vm_backward_bins_workspace_size", "s3d_vm_backward_stage_bytes",
                      "s3d_weighted_abs_sum_workspace_size", "s3d_background_backward_workspace_size",
-                     "s3d_vm_background_backward_workspace_size"):
+                     "s3d_vm_background_backward_workspace_size", "s3d_mc_workspace_bytes"):
             getattr(l, name).restype = C.c_size_t
         l.s3d_vm_backward_max_bins.restype = C.c_uint32
         l.s3d_grid_level_scales.restype = None
@@ -1762,3 +1763,37 @@ class VmBackend:
                                            _p(bound_words), _p(line_scratch), _p(stage), C.c_size_t(stage.numel()), _p(found_inf),
                                            *_shadow1(shadows), _nv(n_valid), _stream()), "vm_color_backward")
         return g_planes, g_lines, g_basis
+
+
+class MeshBackend:
+    """Mesh export (csrc/mesh.hip): marching cubes on the device."""
+
+    @staticmethod
+    def marching_cubes(u, iso, bounds):
+        """u [nx, ny, nz] fp32 on the GPU, bounds = 6 numbers or a tensor (min xyz, max xyz) -> (vertices [V, 3] float32 in
+        world coordinates, triangles [T, 3] int32), both on u's device, in the fixed order of include/seal3d_hip.h.  The two
+        totals are read on the host between the counting and the emitting pass (an export is not part of a step), so the
+        call cannot run while the stream is being captured."""
+        if not isinstance(u, torch.Tensor) or not u.is_cuda:
+            raise RuntimeError("seal3d HIP backend needs GPU tensors (no CPU fallback in the product path)")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("marching_cubes reads its totals on the host: it cannot be captured into a graph")
+        _need(u, torch.float32, "u")
+        if u.dim() != 3:
+            raise RuntimeError(f"marching_cubes: u must be [nx, ny, nz], got {tuple(u.shape)}")
+        u = u.contiguous()
+        nx, ny, nz = u.shape
+        if min(nx, ny, nz) < 2 or nx * ny * nz >= 2 ** 31:
+            raise RuntimeError(f"marching_cubes: every axis needs at least 2 points and the volume fewer than 2^31, got {nx} x {ny} x {nz}")
+        bounds = torch.as_tensor(bounds, dtype=torch.float32).reshape(6).to(u.device).contiguous()
+        ws = _ws.get(lib().s3d_mc_workspace_bytes(_u(nx), _u(ny), _u(nz)), u.device)
+        totals = torch.empty(2, dtype=torch.int64, device=u.device)  # (room for two uint32, 8-byte aligned)
+        _check(lib().s3d_mc_count(_p(u), _u(nx), _u(ny), _u(nz), _f(iso), _p(ws), _p(totals), _stream()), "mc_count")
+        V, T = (int(v) for v in totals.view(torch.int32)[:2].cpu().numpy().view("uint32"))
+        if V == 0xFFFFFFFF or T == 0xFFFFFFFF:
+            raise RuntimeError("marching_cubes: the mesh has 2^32 - 1 vertices or triangles, or more")
+        vertices = torch.empty(V, 3, dtype=torch.float32, device=u.device)
+        triangles = torch.empty(T, 3, dtype=torch.int32, device=u.device)
+        _check(lib().s3d_mc_emit(_p(u), _u(nx), _u(ny), _u(nz), _f(iso), _p(ws), _p(bounds), _p(vertices), _u(V), _p(triangles), _u(T), _stream()),
+               "mc_emit")
+        return vertices, triangles

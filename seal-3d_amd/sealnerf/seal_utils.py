@@ -717,3 +717,30 @@ def get_seal_mapper(config_dict=None, config_file=None, image_loader=None):
     if kind == "anchor":
         return SealAnchorMapper(config_dict)
     raise NotImplementedError(f"unknown seal tool `{kind}` (bbox, brush, anchor)")
+
+
+def generate_default_editing_tool_config(type):
+    """scripts/mesh2config.py:11-29: the defaults of a tool's config, `raw` still empty"""
+    obj = {"type": type, "raw": []}
+    if type == "bbox":
+        obj["transform"] = [[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1]]
+        obj["scale"] = [1, 1, 1]
+    elif type == "brush":
+        obj.update(normal=[0, 1, 0], brushType="line", brushDepth=0.3, brushPressure=0.05, attenuationDistance=0.02,
+                   attenuationMode="linear")
+    elif type == "anchor":
+        obj.update(translation=[0, 0.1, 0], radius=0.03)
+    else:
+        raise NotImplementedError(f"unknown seal tool `{type}` (bbox, brush, anchor)")
+    return obj
+
+
+def config_from_mesh(mesh_path, type, config=None):
+    """scripts/mesh2config.py:32-43: the vertices of a mesh marked in a mesh tool (a PLY, e.g. cut from Trainer.save_mesh's
+    export) become the `raw` points of a tool config — `config` when given (an existing config whose points are replaced),
+    else the tool's defaults.  -> a dict for get_seal_mapper(config_dict=...)"""
+    from nerf.mesh import read_ply
+    vertices, _ = read_ply(mesh_path)
+    obj = dict(config) if config is not None else generate_default_editing_tool_config(type)
+    obj["raw"] = vertices.astype(np.float64).tolist()
+    return obj
