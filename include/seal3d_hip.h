@@ -533,6 +533,50 @@ int s3d_vm_color_backward(const float* x, uint32_t N, const float* const* planes
                           uint32_t* bound_words, float* line_scratch, void* stage, size_t stage_bytes, float* found_inf,
                           const float* const* planes_t, const int32_t* n_valid, s3d_stream_t stream);
 
+/* ------------------------------------------------------------------ TensoRF CP features (line factors only)
+ * tensoRF/network_cp.py:78-111 get_sigma_feat / get_color_feat (3 F.grid_sample calls on "fake 2-D" [1,R,D,1] tensors, two
+ * products of [R,N] tensors, a sum or basis_mat) in one pass, csrc/tensorf_cp.hip.
+ * x [N,3] fp32 in [-1,1]; lines / rank / resolution: HOST arrays of 3: lines[i] device fp32 [rank, res[vec_ids[i]]],
+ * vec_ids = 2,1,0 (network_cp.py:35).  The three ranks must be equal (the product runs over ONE rank index; anything else is
+ * refused).  Per line: p = ((u + 1) / 2) * (D - 1), i0 = floor(p), value = v[i0] * ((i0 + 1) - p) + v[i0 + 1] * (p - i0), a
+ * tap outside [0, D - 1] counts as zero; f[r][n] = (l0 * l1) * l2.
+ * reduce = 1: out [N] = sum_r f[r][n] (sigma_feat); reduce = 0: out [rank, N] (the tensor the reference transposes into
+ * basis_mat).  Any N >= 1.
+ * lines_t (optional): rank-fastest shadows lines_t[i] [D_i][rank] written by s3d_cp_transpose_lines from the current parameters;
+ * a tap's channels are then one contiguous run (four per 16-byte load when rank % 4 == 0 and the shadows are 16-byte aligned).
+ * Same values, same arithmetic; NULL: the parameters' own layout.
+ * n_valid (optional): as for the s3d_vm_* entry points — rows [round_up(*n_valid, 128), N) are absent: the forwards do not write
+ * them, the backwards do not read them (the binning sorts them behind every bin). */
+int s3d_cp_transpose_lines(const float* const* lines, const uint32_t* rank, const uint32_t* resolution, float* const* lines_t,
+                           s3d_stream_t stream);
+int s3d_cp_features_forward(const float* x, uint32_t N, const float* const* lines, const uint32_t* rank,
+                            const uint32_t* resolution, int reduce, float* out, const float* const* lines_t,
+                            const int32_t* n_valid, s3d_stream_t stream);
+/* The products with basis_mat applied inside the kernel (network_cp.py:109), the fp16-autocast Linear's arithmetic exactly as
+ * s3d_vm_color_forward defines it: out [N, basis_rows] fp16 = half(sum_r half(basis[c][r]) * half(f[r][n])), fp32 accumulation.
+ * basis: fp16 [basis_rows <= 32, rank], rank <= 512 (the weight sits in LDS). */
+int s3d_cp_color_forward(const float* x, uint32_t N, const float* const* lines, const uint32_t* rank,
+                         const uint32_t* resolution, const uint16_t* basis, uint32_t basis_rows, uint16_t* out,
+                         const float* const* lines_t, const int32_t* n_valid, s3d_stream_t stream);
+/* Parameter gradients: grad_lines[i] fp32 [rank, D_i], ZERO-INITIALISED by the caller (the kernels add).  grad: [N]
+ * (reduce = 1) or [N, rank] point-major (reduce = 0).  perm / start / n_bounds: the result of s3d_vm_backward_bins for the same
+ * x, resolution and n_valid (its rows 3-5, the 64-row line chunks, are read; no further workspace).  A workgroup sums up to
+ * 1,024 sorted points of one chunk and one 32-rank slice in LDS in fp32 and adds each of its 65 cells to grad_lines with one
+ * atomic; the order of those few adds is the only thing that varies between runs.  Non-finite gradients travel through the
+ * sums; one that belongs to a point outside every line's range (which reaches no cell) makes grad_lines[0][0] NaN and raises
+ * found_inf (optional device float, set to 1).  The coordinates' gradient is not computed.
+ * s3d_cp_color_backward: from grad_out fp16 [N, 32] (rows zero-padded to 32 columns, 16-byte aligned) the line gradients and
+ * grad_basis fp32 [basis_rows, rank] (zero-initialised; one atomic per entry and workgroup). */
+int s3d_cp_features_backward(const float* x, uint32_t N, const float* const* lines, const uint32_t* rank,
+                             const uint32_t* resolution, int reduce, const float* grad, const int32_t* perm,
+                             const int32_t* start, uint32_t n_bounds, float* const* grad_lines, float* found_inf,
+                             const float* const* lines_t, const int32_t* n_valid, s3d_stream_t stream);
+int s3d_cp_color_backward(const float* x, uint32_t N, const float* const* lines, const uint32_t* rank,
+                          const uint32_t* resolution, const uint16_t* basis, uint32_t basis_rows, const uint16_t* grad_out,
+                          const int32_t* perm, const int32_t* start, uint32_t n_bounds, float* const* grad_lines,
+                          float* grad_basis, float* found_inf, const float* const* lines_t, const int32_t* n_valid,
+                          s3d_stream_t stream);
+
 /* Build extensions for the TensoRF step (chains of tiny launches otherwise):
  * s3d_aabb_normalize: out[n][a] = 2 (x[n][a] - aabb[a]) / (aabb[3 + a] - aabb[a]) - 1 (tensoRF/network.py:155-157, the reference's
  *   operation order; aabb = 6 DEVICE floats);

@@ -49,6 +49,7 @@ EXPORTS = [
     "s3d_vm_backward_max_bins", "s3d_vm_backward_keys", "s3d_vm_backward_bins_workspace_size", "s3d_vm_backward_bins",
     "s3d_vm_backward_stage_bytes", "s3d_vm_transpose_factors",
     "s3d_vm_features_backward", "s3d_vm_color_forward", "s3d_vm_color_backward",
+    "s3d_cp_transpose_lines", "s3d_cp_features_forward", "s3d_cp_color_forward", "s3d_cp_features_backward", "s3d_cp_color_backward",
     "s3d_composite_rays_train_loss_bg", "s3d_bg_targets_rays",
     "s3d_background_forward", "s3d_background_backward_workspace_size", "s3d_background_backward",
     "s3d_vm_background_forward", "s3d_vm_background_backward_workspace_size", "s3d_vm_background_backward",
@@ -1763,6 +1764,127 @@ class VmBackend:
                                            _p(bound_words), _p(line_scratch), _p(stage), C.c_size_t(stage.numel()), _p(found_inf),
                                            *_shadow1(shadows), _nv(n_valid), _stream()), "vm_color_backward")
         return g_planes, g_lines, g_basis
+
+
+class CpBackend:
+    """csrc/tensorf_cp.hip — TensoRF CP features (tensoRF/network_cp.py:78-111 of the reference): three line factors
+    [1,R,D_i,1] per factor set, equal ranks"""
+
+    @staticmethod
+    def _lines(lines, resolution, what):
+        """(lines pointers, rank, res, R) of a line set as the C calls take it"""
+        for t in lines:
+            _need(t, torch.float32, "line factor")
+            if not t.is_cuda or not t.is_contiguous() or t.dim() != 4 or t.shape[0] != 1 or t.shape[3] != 1:
+                raise RuntimeError(f"{what}: lines must be contiguous [1,R,D,1] GPU tensors")
+        ptr3, u3 = C.c_void_p * 3, C.c_uint32 * 3
+        ranks = [int(t.shape[1]) for t in lines]
+        if len(lines) != 3 or len(set(ranks)) != 1:
+            raise RuntimeError(f"{what}: three lines of equal rank, got ranks {ranks}")
+        for t, a in zip(lines, (2, 1, 0)):
+            if int(t.shape[2]) != int(resolution[a]):
+                raise RuntimeError(f"{what}: line of {t.shape[2]} rows along axis {a} of resolution {list(resolution)}")
+        return ptr3(*[t.data_ptr() for t in lines]), u3(*ranks), u3(*[int(r) for r in resolution]), ranks[0]
+
+    @staticmethod
+    def _shadows(shadows):
+        return None if shadows is None else (C.c_void_p * 3)(*[t.data_ptr() for t in shadows])
+
+    @staticmethod
+    def _x(x, what):
+        _need(x, torch.float32, "x")
+        if not x.is_contiguous() or x.dim() != 2 or x.shape[1] != 3:
+            raise RuntimeError(f"{what}: x must be contiguous [N,3]")
+        return x.shape[0]
+
+    @staticmethod
+    def transpose_lines(lines, resolution):
+        """rank-fastest shadows [D_i, R] x 3 (fp32) from the CURRENT values of the lines (s3d_cp_transpose_lines)"""
+        ln, rank, res, _ = CpBackend._lines(lines, resolution, "cp transpose_lines")
+        lt = [torch.empty(t.shape[2], t.shape[1], dtype=torch.float32, device=t.device) for t in lines]
+        _check(lib().s3d_cp_transpose_lines(ln, rank, res, (C.c_void_p * 3)(*[t.data_ptr() for t in lt]), _stream()), "cp_transpose_lines")
+        return lt
+
+    @staticmethod
+    def features_forward(x, lines, resolution, reduce, out, n_valid=None, shadows=None):
+        """x [N,3] fp32; lines[i] [1,R,D_i,1] fp32; out [N] (reduce) or [R, N]"""
+        N = CpBackend._x(x, "cp features_forward")
+        _need(out, torch.float32, "out")
+        ln, rank, res, R = CpBackend._lines(lines, resolution, "cp features_forward")
+        if not out.is_contiguous() or out.numel() != (N if reduce else N * R):
+            raise RuntimeError("cp features_forward: out must be contiguous [N] / [R, N]")
+        _check(lib().s3d_cp_features_forward(_p(x), _u(N), ln, rank, res, C.c_int(int(bool(reduce))), _p(out),
+                                             CpBackend._shadows(shadows), _nv(n_valid), _stream()), "cp_features_forward")
+
+    @staticmethod
+    def color_forward(x, lines, resolution, basis, out, n_valid=None, shadows=None):
+        """the products with basis_mat applied in the kernel: basis fp16 [Cb <= 32, R] (the Linear's weight), out fp16 [N, Cb]"""
+        N = CpBackend._x(x, "cp color_forward")
+        _need(basis, torch.float16, "basis"); _need(out, torch.float16, "out")
+        ln, rank, res, R = CpBackend._lines(lines, resolution, "cp color_forward")
+        if not basis.is_contiguous() or basis.dim() != 2 or basis.shape[1] != R or not out.is_contiguous() or out.numel() != N * basis.shape[0]:
+            raise RuntimeError("cp color_forward: basis contiguous [Cb, R], out contiguous [N, Cb]")
+        _check(lib().s3d_cp_color_forward(_p(x), _u(N), ln, rank, res, _p(basis), _u(basis.shape[0]), _p(out),
+                                          CpBackend._shadows(shadows), _nv(n_valid), _stream()), "cp_color_forward")
+
+    @staticmethod
+    def backward_bins(x, resolution, n_valid=None):
+        """(perm, start, n_bounds): the points sorted by 64-row line chunk — the sort of the VM backward (s3d_vm_backward_bins),
+        whose rows 3-5 the CP backward reads.  Depends on x, the resolution and n_valid only: the density and the colour lines of
+        one network share it."""
+        N, dev = CpBackend._x(x, "cp backward_bins"), x.device
+        u3 = C.c_uint32 * 3
+        rank, res = u3(1, 1, 1), u3(*[int(r) for r in resolution])
+        n_bounds = int(lib().s3d_vm_backward_max_bins(res)) + 2
+        perm = torch.empty(6, N, dtype=torch.int32, device=dev)
+        start = torch.empty(6, n_bounds, dtype=torch.int32, device=dev)
+        nbytes = int(lib().s3d_vm_backward_bins_workspace_size(_u(N), _u(n_bounds)))
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _check(lib().s3d_vm_backward_bins(_p(x), _u(N), rank, res, _p(perm), _p(start), _u(n_bounds), _p(work), C.c_size_t(nbytes),
+                                          _nv(n_valid), _stream()), "vm_backward_bins")
+        return perm, start, n_bounds
+
+    @staticmethod
+    def features_backward(x, lines, resolution, reduce, grad, bins=None, found_inf=None, n_valid=None, shadows=None):
+        """gradients of features_forward w.r.t. the lines (a list shaped like them).  grad: [N] (reduce) or [N, R] point-major."""
+        N = CpBackend._x(x, "cp features_backward")
+        _need(grad, torch.float32, "grad")
+        ln, rank, res, R = CpBackend._lines(lines, resolution, "cp features_backward")
+        if not grad.is_contiguous() or grad.numel() != (N if reduce else N * R):
+            raise RuntimeError("cp features_backward: grad must be contiguous [N] / [N, R]")
+        if found_inf is not None:
+            _need(found_inf, torch.float32, "found_inf")
+        perm, start, n_bounds = bins if bins is not None else CpBackend.backward_bins(x, resolution, n_valid)
+        gs, _ = _zeros_like_many(list(lines))
+        _check(lib().s3d_cp_features_backward(_p(x), _u(N), ln, rank, res, C.c_int(int(bool(reduce))), _p(grad), _p(perm), _p(start),
+                                              _u(n_bounds), (C.c_void_p * 3)(*[t.data_ptr() for t in gs]), _p(found_inf),
+                                              CpBackend._shadows(shadows), _nv(n_valid), _stream()), "cp_features_backward")
+        return gs
+
+    @staticmethod
+    def color_backward(x, lines, resolution, basis, grad_out, bins=None, found_inf=None, n_valid=None, shadows=None):
+        """gradients of color_forward w.r.t. the lines and basis from grad_out fp16 [N, Cb]: (g_lines, g_basis fp32)"""
+        N = CpBackend._x(x, "cp color_backward")
+        _need(basis, torch.float16, "basis"); _need(grad_out, torch.float16, "grad_out")
+        ln, rank, res, R = CpBackend._lines(lines, resolution, "cp color_backward")
+        if grad_out.shape != (N, basis.shape[0]) or not basis.is_contiguous() or basis.shape[1] != R or basis.shape[0] > 32:
+            raise RuntimeError("cp color_backward: grad_out must be [N, Cb <= 32], basis contiguous [Cb, R]")
+        if found_inf is not None:
+            _need(found_inf, torch.float32, "found_inf")
+        # rows padded to 32 columns (a [:, :Cb] view of _MlpInput's zero-padded [N, 32] buffer is taken as it is)
+        base = grad_out._base
+        if (base is not None and getattr(base, "_s3d_zero_padded", False) and base.shape == (N, 32) and base.is_contiguous()
+                and grad_out.data_ptr() == base.data_ptr() and grad_out.stride() == (32, 1)):
+            grad_out = base
+        else:
+            grad_out = torch.nn.functional.pad(grad_out, (0, 32 - basis.shape[0])).contiguous()
+        perm, start, n_bounds = bins if bins is not None else CpBackend.backward_bins(x, resolution, n_valid)
+        gs, _ = _zeros_like_many(list(lines) + [basis])
+        g_lines, g_basis = gs[:3], gs[3]
+        _check(lib().s3d_cp_color_backward(_p(x), _u(N), ln, rank, res, _p(basis), _u(basis.shape[0]), _p(grad_out), _p(perm), _p(start),
+                                           _u(n_bounds), (C.c_void_p * 3)(*[t.data_ptr() for t in g_lines]), _p(g_basis), _p(found_inf),
+                                           CpBackend._shadows(shadows), _nv(n_valid), _stream()), "cp_color_backward")
+        return g_lines, g_basis
 
 
 class MeshBackend:

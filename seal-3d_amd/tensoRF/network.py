@@ -294,7 +294,60 @@ class _MeanAbsSum(torch.autograd.Function):
         return tuple(signs)
 
 
-class NeRFNetwork(NeRFRenderer):
+class TensoRFCommon:
+    """what both TensoRF backbones share (this file's vector-matrix network and tensoRF/network_cp.py): the colour MLP on the MFMA
+    kernels and the value of the L1 term; the host class provides color_net, hidden_dim, in_dim, encoder, encoder_dir,
+    density_factors() and fused_l1"""
+
+    fused_mlp = True  # A-B runs / tests: False = the nn.Linear chain (library GEMMs + elementwise launches)
+
+    def _fused_mlp_ok(self, feat, d_requires_grad=False):
+        """the colour MLP (tensoRF/network.py:71-83: bias-free Linear -> ReLU chain, 150 -> 128 -> 128 -> 3) on the MFMA kernels
+        of the ffmlp package: hidden width 128, input padded to a multiple of 16 (<= 160), whole 128-row tiles, fp16 autocast"""
+        net = self.color_net
+        return (self.fused_mlp and feat.is_cuda and feat.dim() == 2 and feat.shape[0] > 0 and feat.shape[0] % 128 == 0
+                and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.float16
+                and len(net) >= 2 and all(l.bias is None for l in net) and self.hidden_dim == 128
+                and net[-1].out_features <= 16 and (self.in_dim + 15) // 16 * 16 <= 160
+                and hasattr(self.encoder, "degree") and hasattr(self.encoder_dir, "degree") and not d_requires_grad)
+
+    def _color_mlp_fused(self, cf, d):
+        """the colours: same arithmetic as the encoders + Linear chain + sigmoid under autocast (fp32 encodings rounded to fp16 once,
+        fp16 operands, fp32 accumulation, fp16 activations); the weights travel as the ffmlp layout [W, in_pad] | (n - 1) x [W, W] | [16, W] built from
+        the nn.Linear parameters each step (_PackChain: ~39 K elements, one launch per direction)"""
+        from ffmlp.ffmlp import _FFMLPForward
+        net = self.color_net
+        in_pad, out = (self.in_dim + 15) // 16 * 16, net[-1].out_features
+        h = _MlpInput.apply(cf, d, self.encoder.degree, self.encoder_dir.degree, in_pad)
+        flat = _PackChain.apply(in_pad, *[l.weight for l in net])
+        # (the kernels write the output padded to 16 columns, ffmlp.py:117-118, 162-163)
+        # (no graph being recorded — rendering: the inference entry point, no activation buffers)
+        nv = s3d_hip.active_row_limit(cf.shape[0])  # (padded sample batch: the MLP kernels skip the absent rows too)
+        out16 = _FFMLPForward.apply(h, flat, in_pad, 16, self.hidden_dim, len(net) - 1, 0, 6, not torch.is_grad_enabled(), True,
+                                    None, None, 0, nv)
+        if out == 3:
+            # sigmoid of the three real columns as fp32 with torch.sigmoid's fp16 rounding, one launch per direction
+            # (nerf/network_ff.py: _NgpRgb — instead of slice, sigmoid, cast and their four backward launches)
+            from nerf.network_ff import _NgpRgb
+            return _NgpRgb.apply(out16, nv)
+        return torch.sigmoid(out16[:, :out])
+
+    @torch.no_grad()
+    def density_loss_value(self):
+        """the value of density_loss() without a graph (tensoRF/utils.py: the trainer whose optimizer forms the gradient itself)"""
+        ts = [t.detach() for t in self.density_factors()]
+        if self.fused_l1 and all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in ts) and len(ts) <= 8:
+            out = torch.empty((), dtype=torch.float32, device=ts[0].device)  # (two launches instead of eight)
+            s3d_hip.VmBackend.weighted_abs_sum(ts, [1.0 / t.numel() for t in ts], out)
+            return out
+        key = tuple(t.numel() for t in ts)
+        inv = self.__dict__.get("_l1_inv")
+        if inv is None or inv[0] != key or inv[1].device != ts[0].device:
+            inv = self.__dict__["_l1_inv"] = (key, torch.tensor([1.0 / n for n in key], dtype=torch.float32, device=ts[0].device))
+        return (torch.stack(torch._foreach_norm(ts, 1)) * inv[1]).sum()
+
+
+class NeRFNetwork(TensoRFCommon, NeRFRenderer):
     def __init__(self, resolution=(128, 128, 128), sigma_rank=(16, 16, 16), color_rank=(48, 48, 48), bg_resolution=(512, 512), bg_rank=8,
                  color_feat_dim=27, num_layers=3, hidden_dim=128, num_layers_bg=2, hidden_dim_bg=64, bound=1, **kwargs):
         super().__init__(bound, **kwargs)
@@ -405,39 +458,6 @@ class NeRFNetwork(NeRFRenderer):
                 h = F.relu(h, inplace=True)
         return sigma, torch.sigmoid(h)
 
-    fused_mlp = True  # A-B runs / tests: False = the nn.Linear chain (library GEMMs + elementwise launches)
-
-    def _fused_mlp_ok(self, feat, d_requires_grad=False):
-        """the colour MLP (tensoRF/network.py:71-83: bias-free Linear -> ReLU chain, 150 -> 128 -> 128 -> 3) on the MFMA kernels
-        of the ffmlp package: hidden width 128, input padded to a multiple of 16 (<= 160), whole 128-row tiles, fp16 autocast"""
-        net = self.color_net
-        return (self.fused_mlp and feat.is_cuda and feat.dim() == 2 and feat.shape[0] > 0 and feat.shape[0] % 128 == 0
-                and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.float16
-                and len(net) >= 2 and all(l.bias is None for l in net) and self.hidden_dim == 128
-                and net[-1].out_features <= 16 and (self.in_dim + 15) // 16 * 16 <= 160
-                and hasattr(self.encoder, "degree") and hasattr(self.encoder_dir, "degree") and not d_requires_grad)
-
-    def _color_mlp_fused(self, cf, d):
-        """the colours: same arithmetic as the encoders + Linear chain + sigmoid under autocast (fp32 encodings rounded to fp16 once,
-        fp16 operands, fp32 accumulation, fp16 activations); the weights travel as the ffmlp layout [W, in_pad] | (n - 1) x [W, W] | [16, W] built from
-        the nn.Linear parameters each step (_PackChain: ~39 K elements, one launch per direction)"""
-        from ffmlp.ffmlp import _FFMLPForward
-        net = self.color_net
-        in_pad, out = (self.in_dim + 15) // 16 * 16, net[-1].out_features
-        h = _MlpInput.apply(cf, d, self.encoder.degree, self.encoder_dir.degree, in_pad)
-        flat = _PackChain.apply(in_pad, *[l.weight for l in net])
-        # (the kernels write the output padded to 16 columns, ffmlp.py:117-118, 162-163)
-        # (no graph being recorded — rendering: the inference entry point, no activation buffers)
-        nv = s3d_hip.active_row_limit(cf.shape[0])  # (padded sample batch: the MLP kernels skip the absent rows too)
-        out16 = _FFMLPForward.apply(h, flat, in_pad, 16, self.hidden_dim, len(net) - 1, 0, 6, not torch.is_grad_enabled(), True,
-                                    None, None, 0, nv)
-        if out == 3:
-            # sigmoid of the three real columns as fp32 with torch.sigmoid's fp16 rounding, one launch per direction
-            # (nerf/network_ff.py: _NgpRgb — instead of slice, sigmoid, cast and their four backward launches)
-            from nerf.network_ff import _NgpRgb
-            return _NgpRgb.apply(out16, nv)
-        return torch.sigmoid(out16[:, :out])
-
     def density(self, x):
         return {"sigma": trunc_exp(self.get_sigma_feat(self._normalize(x)))}
 
@@ -465,6 +485,10 @@ class NeRFNetwork(NeRFRenderer):
                 h = F.relu(h, inplace=True)
         return torch.sigmoid(h)
 
+    def density_factors(self):
+        """the density factors the L1 term covers (tensoRF/utils.py: _regularizer)"""
+        return list(self.sigma_mat) + list(self.sigma_vec)
+
     def density_loss(self):
         """L1 penalty on the density factors (tensoRF/network.py:259-263): sum over the three plane / line pairs of
         mean|sigma_mat| + mean|sigma_vec|; the trainer adds it times `l1_reg_weight` (tensoRF/utils.py:42-49)"""
@@ -476,20 +500,6 @@ class NeRFNetwork(NeRFRenderer):
         return loss
 
     fused_l1 = True  # tests / A-B runs: False = the reference's op-by-op expression
-
-    @torch.no_grad()
-    def density_loss_value(self):
-        """the value of density_loss() without a graph (tensoRF/utils.py: the trainer whose optimizer forms the gradient itself)"""
-        ts = [t.detach() for t in list(self.sigma_mat) + list(self.sigma_vec)]
-        if self.fused_l1 and all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in ts) and len(ts) <= 8:
-            out = torch.empty((), dtype=torch.float32, device=ts[0].device)  # (two launches instead of eight)
-            s3d_hip.VmBackend.weighted_abs_sum(ts, [1.0 / t.numel() for t in ts], out)
-            return out
-        key = tuple(t.numel() for t in ts)
-        inv = self.__dict__.get("_l1_inv")
-        if inv is None or inv[0] != key or inv[1].device != ts[0].device:
-            inv = self.__dict__["_l1_inv"] = (key, torch.tensor([1.0 / n for n in key], dtype=torch.float32, device=ts[0].device))
-        return (torch.stack(torch._foreach_norm(ts, 1)) * inv[1]).sum()
 
     def get_params(self, lr1, lr2=None):
         lr2 = lr1 if lr2 is None else lr2

@@ -42,7 +42,7 @@ class TensoRFSteps:
         from nerf.optim import NativeAdam
         if (self.l1_in_update and self.native_optim and self.dist is None and isinstance(self.optimizer, NativeAdam)
                 and self._expected_grad() is not None):
-            for p in list(self.model.sigma_mat) + list(self.model.sigma_vec):
+            for p in self.model.density_factors():
                 p._s3d_l1 = self.l1_reg_weight / p.numel() if p.requires_grad else 0.0
             return self.model.density_loss_value() * self.l1_reg_weight
         return self.model.density_loss() * self.l1_reg_weight
