@@ -1534,6 +1534,30 @@ def _zeros_like_many(tensors, words=0):
     return out, (flat[off:off + words].view(torch.int32) if words else None)
 
 
+def _native_bins(x, rank, res, n_bounds, n_valid):
+    """(perm [6,N] i32, start [6,n_bounds] i32, n_bounds): the points of x sorted by plane tile (rows 0-2, `rank` decides the tile)
+    and by 64-row line chunk (rows 3-5) in native launches — the sort both TensoRF backends' factor backward reads"""
+    N, dev = x.shape[0], x.device
+    perm = torch.empty(6, N, dtype=torch.int32, device=dev)
+    start = torch.empty(6, n_bounds, dtype=torch.int32, device=dev)
+    nbytes = int(lib().s3d_vm_backward_bins_workspace_size(_u(N), _u(n_bounds)))
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _check(lib().s3d_vm_backward_bins(_p(x), _u(N), rank, res, _p(perm), _p(start), _u(n_bounds), _p(work), C.c_size_t(nbytes),
+                                      _nv(n_valid), _stream()), "vm_backward_bins")
+    return perm, start, n_bounds
+
+
+def _rows_of_32(grad_out, N):
+    """grad_out fp16 [N, Cb <= 32] as the colour backward kernels read it — a point's gradients as four 16-byte words: rows padded
+    to 32 columns.  A [:, :Cb] view of a zero-padded [N, 32] buffer (FreqBackend.freq_encode_pack_backward's caller marks what it
+    wrote, tensoRF/network.py: _MlpInput) is taken as it is: the buffer behind the view."""
+    base = grad_out._base
+    if (base is not None and getattr(base, "_s3d_zero_padded", False) and base.shape == (N, 32) and base.is_contiguous()
+            and grad_out.data_ptr() == base.data_ptr() and grad_out.stride() == (32, 1)):
+        return base
+    return torch.nn.functional.pad(grad_out, (0, 32 - grad_out.shape[1])).contiguous()
+
+
 class VmBackend:
     """csrc/tensorf.hip — TensoRF vector-matrix features (tensoRF/network.py:112-153 of the reference)"""
 
@@ -1659,13 +1683,7 @@ class VmBackend:
         _, _, rank, res, _ = VmBackend._factors(planes, None, resolution)
         n_bounds = int(lib().s3d_vm_backward_max_bins(res)) + 2
         if VmBackend.native_bins:
-            perm = torch.empty(6, N, dtype=torch.int32, device=dev)
-            start = torch.empty(6, n_bounds, dtype=torch.int32, device=dev)
-            nbytes = int(lib().s3d_vm_backward_bins_workspace_size(_u(N), _u(n_bounds)))
-            work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            _check(lib().s3d_vm_backward_bins(_p(x), _u(N), rank, res, _p(perm), _p(start), _u(n_bounds), _p(work), C.c_size_t(nbytes),
-                                              _nv(n_valid), _stream()), "vm_backward_bins")
-            return perm, start, n_bounds
+            return _native_bins(x, rank, res, n_bounds, n_valid)
         if n_valid is not None:
             raise RuntimeError("vm backward bins: the torch.sort twin (A/B) has no padded-batch form")
         keys = torch.empty(6, N, dtype=torch.int32, device=dev)
@@ -1747,14 +1765,7 @@ class VmBackend:
         pl, ln, rank, res, rows = VmBackend._factors(planes, lines, resolution)
         if grad_out.shape != (N, basis.shape[0]) or not basis.is_contiguous() or basis.shape[1] != rows or basis.shape[0] > 32:
             raise RuntimeError("vm color backward: grad_out must be [N, Cb <= 32], basis contiguous [Cb, sum rank]")
-        # the kernel reads a point's gradients as four 16-byte words: rows padded to 32 columns (a [:, :Cb] view of a zero-padded
-        # [N, 32] buffer — FreqBackend.freq_encode_pack_backward marks what it wrote — is taken as it is)
-        base = grad_out._base
-        if (base is not None and getattr(base, "_s3d_zero_padded", False) and base.shape == (N, 32) and base.is_contiguous()
-                and grad_out.data_ptr() == base.data_ptr() and grad_out.stride() == (32, 1)):
-            grad_out = base
-        else:
-            grad_out = torch.nn.functional.pad(grad_out, (0, 32 - basis.shape[0])).contiguous()
+        grad_out = _rows_of_32(grad_out, N)
         perm, start, n_bounds, gm, gs, bound_words, line_scratch, stage = VmBackend._backward_buffers(
             x, planes, lines, resolution, rank, res, rows, bins, n_valid, extra=[basis])
         g_planes, g_lines, g_basis = gs[:3], gs[3:6], gs[6]
@@ -1832,17 +1843,10 @@ class CpBackend:
         """(perm, start, n_bounds): the points sorted by 64-row line chunk — the sort of the VM backward (s3d_vm_backward_bins),
         whose rows 3-5 the CP backward reads.  Depends on x, the resolution and n_valid only: the density and the colour lines of
         one network share it."""
-        N, dev = CpBackend._x(x, "cp backward_bins"), x.device
+        CpBackend._x(x, "cp backward_bins")
         u3 = C.c_uint32 * 3
         rank, res = u3(1, 1, 1), u3(*[int(r) for r in resolution])
-        n_bounds = int(lib().s3d_vm_backward_max_bins(res)) + 2
-        perm = torch.empty(6, N, dtype=torch.int32, device=dev)
-        start = torch.empty(6, n_bounds, dtype=torch.int32, device=dev)
-        nbytes = int(lib().s3d_vm_backward_bins_workspace_size(_u(N), _u(n_bounds)))
-        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _check(lib().s3d_vm_backward_bins(_p(x), _u(N), rank, res, _p(perm), _p(start), _u(n_bounds), _p(work), C.c_size_t(nbytes),
-                                          _nv(n_valid), _stream()), "vm_backward_bins")
-        return perm, start, n_bounds
+        return _native_bins(x, rank, res, int(lib().s3d_vm_backward_max_bins(res)) + 2, n_valid)
 
     @staticmethod
     def features_backward(x, lines, resolution, reduce, grad, bins=None, found_inf=None, n_valid=None, shadows=None):
@@ -1871,13 +1875,7 @@ class CpBackend:
             raise RuntimeError("cp color_backward: grad_out must be [N, Cb <= 32], basis contiguous [Cb, R]")
         if found_inf is not None:
             _need(found_inf, torch.float32, "found_inf")
-        # rows padded to 32 columns (a [:, :Cb] view of _MlpInput's zero-padded [N, 32] buffer is taken as it is)
-        base = grad_out._base
-        if (base is not None and getattr(base, "_s3d_zero_padded", False) and base.shape == (N, 32) and base.is_contiguous()
-                and grad_out.data_ptr() == base.data_ptr() and grad_out.stride() == (32, 1)):
-            grad_out = base
-        else:
-            grad_out = torch.nn.functional.pad(grad_out, (0, 32 - basis.shape[0])).contiguous()
+        grad_out = _rows_of_32(grad_out, N)
         perm, start, n_bounds = bins if bins is not None else CpBackend.backward_bins(x, resolution, n_valid)
         gs, _ = _zeros_like_many(list(lines) + [basis])
         g_lines, g_basis = gs[:3], gs[3]

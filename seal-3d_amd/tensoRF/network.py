@@ -12,6 +12,11 @@ per call (`s3d_vm_features_forward`, csrc/tensorf.hip), and 
 fp32 atomics per step grid_sample's backward issues at the Lego sample count).  A gradient w.r.t. the coordinates (not
 needed by any trainer of the reference) falls back to the grid_sample sequence under autograd.
 
+The host path of those kernels is written once, for this network and the CP one (tensoRF/network_cp.py): the Functions
+`_Features` / `_ColorBasis`, the sorted-point cache `_bins` and the mixin `TensoRFCommon` below.  A backbone names its backend
+class, cuts its flat factor list into the backend's leading arguments and supplies the scaler flag; the shared code never asks
+which backbone it serves.
+
 The background model (`bg_radius > 0`, tensoRF/network.py:69-96, :201-218: a dense plane `bg_mat` sampled at the ray's sphere
 coordinates + FreqEncoder(3, deg 2) -> 23 -> 64 -> 3) runs as one forward and two backward launches under fp16 autocast
 (`s3d_vm_background_forward` / `_backward`, csrc/background.hip)."""
@@ -42,23 +47,54 @@ def _source_check(net, factors, *more):
     return flag
 
 
-class _VmFeatures(torch.autograd.Function):
+BINS = "_s3d_bins"  # the sorted-point cache's key in `net.__dict__` (both backbones)
+
+
+def _bins(net, x, lead, n_valid=None):
+    """the points of x sorted by plane tile / line chunk (`backward_bins` of the network's backend): x and the resolution decide
+    it, so the density and the colour features of one forward share the sort.  Kept on the network, keyed by the storage of x
+    (alive until both backward nodes have run), dropped after two uses or at the next forward.  `lead`: the backend's leading
+    factor arguments; the sort takes all but the lines (the planes' ranks set the VM tile; nothing for CP)."""
+    cache = net.__dict__.setdefault(BINS, {})
+    key = (x.data_ptr(), x._version, x.shape[0], tuple(net.resolution), None if n_valid is None else n_valid.data_ptr())
+    if key not in cache:
+        if len(cache) >= 4:
+            cache.clear()
+        # (the entry keeps x itself: while it is cached no other tensor can live at its address; two consumers — the density
+        #  and the colour features' backward — then the points and their six sorted index rows are let go)
+        cache[key] = [x, net._backend.backward_bins(x, *lead[:-1], net.resolution, n_valid), 2]
+    ent = cache[key]
+    ent[2] -= 1
+    if ent[2] <= 0:
+        del cache[key]
+    return ent[1]
+
+
+def _flat(groups):
+    """a backend's gradient result as the flat tuple autograd returns: (planes, lines) for VM, the lines or (lines,) for CP"""
+    out = []
+    for g in groups:
+        out += list(g) if isinstance(g, (list, tuple)) else [g]
+    return tuple(out)
+
+
+class _Features(torch.autograd.Function):
     """forward: one HIP kernel; backward: binned HIP kernels for the factor gradients (coordinates' gradient, if ever
-    asked for: the reference's grid_sample sequence re-run under autograd)"""
+    asked for: the reference's grid_sample sequence re-run under autograd).  The network names its backend (`_backend`), cuts
+    the flat factor tuple into the backend's leading arguments (`_split`) and supplies the scaler flag (`_found_inf`)."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)  # grid_sample is an fp32 op under autocast too
     def forward(ctx, x, net, reduce, *factors):
         x = x.contiguous()
-        mats, vecs = factors[:3], factors[3:]
         N = x.shape[0]
-        out = torch.empty((N,) if reduce else (sum(m.shape[1] for m in mats), N), dtype=torch.float32, device=x.device)
+        lead = net._split([f.contiguous() for f in factors])
+        out = torch.empty((N,) if reduce else (net._product_rows(lead), N), dtype=torch.float32, device=x.device)
         # (a padded sample batch announced by the renderer, s3d_hip.row_limit: rows behind the device-side count are absent —
         #  not written here, sorted behind every bin in the backward, nerf/renderer.py never reads them)
         nv = s3d_hip.active_row_limit(N)
-        mats, vecs = [m.contiguous() for m in mats], [v.contiguous() for v in vecs]
-        sh = _shadows(net, mats, vecs, net.resolution)
-        s3d_hip.VmBackend.features_forward(x, mats, vecs, net.resolution, reduce, out, n_valid=nv, shadows=sh)
+        sh = net._shadows(*lead)
+        net._backend.features_forward(x, *lead, net.resolution, reduce, out, n_valid=nv, shadows=sh)
         ctx.save_for_backward(x, *factors)
         ctx.net, ctx.reduce, ctx.nv, ctx.sh = net, reduce, nv, sh
         return out
@@ -67,71 +103,39 @@ class _VmFeatures(torch.autograd.Function):
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, g):
         x, *factors = ctx.saved_tensors
+        net = ctx.net
         if not ctx.needs_input_grad[0]:
             g = g if ctx.reduce else g.t()  # [rows, N] gradient of the `.T` consumer: point-major underneath
-            gp, gl = s3d_hip.VmBackend.features_backward(x, [f.contiguous() for f in factors[:3]],
-                                                         [f.contiguous() for f in factors[3:]], ctx.net.resolution, ctx.reduce,
-                                                         g.float().contiguous(), _bins(ctx.net, x, factors[:3], ctx.nv),
-                                                         _source_check(ctx.net, factors), n_valid=ctx.nv, shadows=ctx.sh)
-            return (None, None, None) + tuple(gp) + tuple(gl)
+            lead = net._split([f.contiguous() for f in factors])
+            grads = net._backend.features_backward(x, *lead, net.resolution, ctx.reduce, g.float().contiguous(),
+                                                   _bins(net, x, lead, ctx.nv), net._found_inf(factors), n_valid=ctx.nv, shadows=ctx.sh)
+            return (None, None, None) + _flat(grads)
         if ctx.nv is not None:  # (the torch route sums over every row: the absent ones hold anything)
             live = torch.arange(x.shape[0], device=x.device) < (ctx.nv.reshape(-1)[:1] + 127) // 128 * 128
             g = torch.where(live if ctx.reduce else live.unsqueeze(0), g, torch.zeros((), dtype=g.dtype, device=g.device))
         with torch.enable_grad():
             leaves = [f.detach().requires_grad_(True) for f in factors]
-            xin = x.detach().requires_grad_(ctx.needs_input_grad[0])
-            fn = ctx.net._sigma_feat_torch if ctx.reduce else ctx.net._color_prod_torch
-            out = fn(xin, leaves[:3], leaves[3:])
-            wanted = ([xin] if ctx.needs_input_grad[0] else []) + leaves
-            grads = torch.autograd.grad(out, wanted, g.contiguous())
-        gx = grads[0] if ctx.needs_input_grad[0] else None
-        return (gx, None, None) + tuple(grads[1:] if ctx.needs_input_grad[0] else grads)
+            xin = x.detach().requires_grad_(True)
+            fn = net._sigma_feat_torch if ctx.reduce else net._color_prod_torch
+            grads = torch.autograd.grad(fn(xin, *net._split(leaves)), [xin] + leaves, g.contiguous())
+        return (grads[0], None, None) + tuple(grads[1:])
 
 
-def _shadows(net, mats, vecs, resolution):
-    """rank-fastest shadows of a factor set (VmBackend.transpose_factors), taken afresh at EVERY forward: the native optimizer
-    rewrites the parameters without touching `_version`, so nothing cheaper than the ~10 us launch says whether they are stale;
-    the forward and the backward of one step share them (the parameters do not change in between).  None: shapes the
-    16-byte loads do not cover (a rank that is not a multiple of four) or the switch `fused_shadows` off."""
-    if not getattr(net, "fused_shadows", True) or any(m.shape[1] % 4 for m in mats) or not all(t.is_cuda for t in mats):
-        return None
-    return s3d_hip.VmBackend.transpose_factors([m.detach() for m in mats], [v.detach() for v in vecs], resolution)
-
-
-def _bins(net, x, mats, n_valid=None):
-    """the points of x sorted by plane tile / line chunk (VmBackend.backward_bins): x and the resolution decide it, so the
-    density and the colour features of one forward share the sort.  Kept on the network, keyed by the storage of x (alive
-    until both backward nodes have run), dropped at the next forward."""
-    cache = net.__dict__.setdefault("_vm_bins", {})
-    key = (x.data_ptr(), x._version, x.shape[0], tuple(net.resolution), None if n_valid is None else n_valid.data_ptr())
-    if key not in cache:
-        if len(cache) >= 4:
-            cache.clear()
-        # (the entry keeps x itself: while it is cached no other tensor can live at its address; two consumers — the density
-        #  and the colour features' backward — then the points and their six sorted index rows are let go)
-        cache[key] = [x, s3d_hip.VmBackend.backward_bins(x, [m.contiguous() for m in mats], net.resolution, n_valid), 2]
-    ent = cache[key]
-    ent[2] -= 1
-    if ent[2] <= 0:
-        del cache[key]
-    return ent[1]
-
-
-class _VmColorBasis(torch.autograd.Function):
-    """basis_mat((mat * vec).T) of tensoRF/network.py:149-153 in ONE kernel per direction (s3d_vm_color_forward / _backward): the
-    [144, N] products stay in registers, the Linear's weight in LDS; the backward derives each product's gradient from the
-    Linear's output gradient on the fly and accumulates basis_mat's own gradient next to the plane gradients.  Arithmetic of the
-    fp16 autocast Linear: operands rounded to binary16, fp32 accumulation, binary16 output."""
+class _ColorBasis(torch.autograd.Function):
+    """basis_mat(products.T) of tensoRF/network.py:149-153 / network_cp.py:105-109 in ONE kernel per direction (the backend's
+    color_forward / color_backward): the [rows, N] products stay in registers, the Linear's weight in LDS; the backward derives
+    each product's gradient from the Linear's output gradient on the fly and accumulates basis_mat's own gradient next to the factor
+    gradients.  Arithmetic of the fp16 autocast Linear: operands rounded to binary16, fp32 accumulation, binary16 output."""
 
     @staticmethod
     def forward(ctx, x, net, weight, *factors):
         x = x.float().contiguous()
-        mats, vecs = [f.float().contiguous() for f in factors[:3]], [f.float().contiguous() for f in factors[3:]]
+        lead = net._split([f.float().contiguous() for f in factors])
         w16 = weight.detach().to(torch.float16).contiguous()
         out = torch.empty(x.shape[0], w16.shape[0], dtype=torch.float16, device=x.device)
         nv = s3d_hip.active_row_limit(x.shape[0])
-        sh = _shadows(net, mats, vecs, net.resolution)
-        s3d_hip.VmBackend.color_forward(x, mats, vecs, net.resolution, w16, out, n_valid=nv, shadows=sh)
+        sh = net._shadows(*lead)
+        net._backend.color_forward(x, *lead, net.resolution, w16, out, n_valid=nv, shadows=sh)
         ctx.save_for_backward(x, w16, *factors)
         ctx.net, ctx.nv, ctx.sh = net, nv, sh
         return out
@@ -139,12 +143,20 @@ class _VmColorBasis(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, w16, *factors = ctx.saved_tensors
-        mats, vecs = [f.float().contiguous() for f in factors[:3]], [f.float().contiguous() for f in factors[3:]]
+        net = ctx.net
+        lead = net._split([f.float().contiguous() for f in factors])
         # (g as it arrives: a [:, :27] view of _MlpInput's zero-padded [N, 32] gradient is used in place, anything else is padded)
-        gp, gl, gw = s3d_hip.VmBackend.color_backward(x, mats, vecs, ctx.net.resolution, w16, g.to(torch.float16),
-                                                      _bins(ctx.net, x, mats, ctx.nv), _source_check(ctx.net, factors, ctx.net.basis_mat.weight),
-                                                      n_valid=ctx.nv, shadows=ctx.sh)
-        return (None, None, gw) + tuple(gp) + tuple(gl)
+        *grads, gw = net._backend.color_backward(x, *lead, net.resolution, w16, g.to(torch.float16), _bins(net, x, lead, ctx.nv),
+                                                 net._found_inf(factors, net.basis_mat.weight), n_valid=ctx.nv, shadows=ctx.sh)
+        return (None, None, gw) + _flat(grads)
+
+
+class _VmFeatures(_Features):
+    pass
+
+
+class _VmColorBasis(_ColorBasis):
+    pass
 
 
 class _VmBackground(torch.autograd.Function):
@@ -204,7 +216,7 @@ class _MlpInput(torch.autograd.Function):
         feat, = ctx.saved_tensors
         ga = torch.empty(feat.shape[0], max(32, feat.shape[1]), dtype=torch.float16, device=feat.device)
         s3d_hip.FreqBackend.freq_encode_pack_backward(g.to(torch.float16).contiguous(), feat, ctx.deg1, ga, n_valid=ctx.nv)
-        ga._s3d_zero_padded = True  # (VmBackend.color_backward takes the buffer behind the view)
+        ga._s3d_zero_padded = True  # (both backends' color_backward take the buffer behind the view: s3d_hip._rows_of_32)
         return ga[:, :feat.shape[1]], None, None, None, None
 
 
@@ -295,11 +307,99 @@ class _MeanAbsSum(torch.autograd.Function):
 
 
 class TensoRFCommon:
-    """what both TensoRF backbones share (this file's vector-matrix network and tensoRF/network_cp.py): the colour MLP on the MFMA
-    kernels and the value of the L1 term; the host class provides color_net, hidden_dim, in_dim, encoder, encoder_dir,
-    density_factors() and fused_l1"""
+    """what both TensoRF backbones share (this file's vector-matrix network and tensoRF/network_cp.py): the host path of the fused
+    feature kernels (normalisation, dispatch, the Functions above and their sorted-point cache), the colour MLP on the MFMA
+    kernels, the occupied box of shrink_model and the value of the L1 term.  The host class provides its parameters, color_net,
+    hidden_dim, in_dim, encoder, encoder_dir, fused_l1, the grid_sample route (_sigma_feat_torch / _color_prod_torch) and
 
+    - `_backend` (s3d_hip.VmBackend / CpBackend: reached through the class at every call), `_Features`, `_ColorBasis` (its named
+      Functions) and `_fused` (its switch: fused_vm / fused_cp);
+    - density_factors() / _color_factors(): a factor set as the flat list autograd sees (3 planes + 3 lines, or 3 lines);
+      `_split(flat)`: the backend's leading arguments out of it, `_product_rows(lead)`: rows of the un-reduced products;
+    - `_found_inf(factors, *more)`: the scaler flag a factor backward reports into, or None (the scaler reads the gradients);
+    - `_shadows(*lead)`: the rank-fastest shadows of a factor set, `_basis_rank_ok()`: the ranks the fused basis_mat kernel takes."""
+
+    fused_basis = True  # A-B runs: False = the products through HBM and basis_mat as an nn.Linear
     fused_mlp = True  # A-B runs / tests: False = the nn.Linear chain (library GEMMs + elementwise launches)
+
+    def __getstate__(self):
+        """copy.deepcopy (teacher creation, EMA) and pickling leave the backward's sorted-point cache behind"""
+        state = self.__dict__.copy()
+        state.pop(BINS, None)
+        state.pop("_l1_inv", None)
+        state.pop("_s3d_found_inf", None)  # (a trainer's scaler flag: re-attached by the trainer that owns the copy)
+        return state
+
+    def _use_native(self, x):
+        return self._fused and x.is_cuda and x.dim() == 2 and x.shape[0] > 0
+
+    def get_sigma_feat(self, x):
+        factors = self.density_factors()
+        if self._use_native(x):
+            return self._Features.apply(x, self, True, *factors)
+        return self._sigma_feat_torch(x, *self._split(factors))
+
+    def get_color_feat(self, x):
+        factors = self._color_factors()
+        if not self._use_native(x):
+            return _linear(self.basis_mat, self._color_prod_torch(x, *self._split(factors)).T)
+        if (self.fused_basis and not x.requires_grad and self.basis_mat.bias is None and self.basis_mat.out_features <= 32
+                and self._basis_rank_ok() and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.float16):
+            return self._ColorBasis.apply(x, self, self.basis_mat.weight, *factors)
+        return _linear(self.basis_mat, self._Features.apply(x, self, False, *factors).T)
+
+    def _normalize(self, x):
+        if (self._fused and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous() and not x.requires_grad
+                and self.aabb_train.is_cuda and self.aabb_train.dtype == torch.float32):
+            out = torch.empty_like(x)  # (one launch instead of five, the same operations in the same order)
+            s3d_hip.VmBackend.aabb_normalize(x, self.aabb_train.contiguous(), out)
+            return out
+        return 2 * (x - self.aabb_train[:3]) / (self.aabb_train[3:] - self.aabb_train[:3]) - 1
+
+    def _colors(self, cf, d):
+        if self._fused_mlp_ok(cf, d.requires_grad):
+            return self._color_mlp_fused(cf, d)
+        h = torch.cat([self.encoder(cf), self.encoder_dir(d)], dim=-1)
+        for k, layer in enumerate(self.color_net):
+            h = _linear(layer, h)
+            if k != self.num_layers - 1:
+                h = F.relu(h, inplace=True)
+        return torch.sigmoid(h)
+
+    def forward(self, x, d):
+        x = self._normalize(x)
+        self.__dict__[BINS] = {}  # (the previous forward's sorted points)
+        sigma = trunc_exp(self.get_sigma_feat(x))
+        return sigma, self._colors(self.get_color_feat(x), d)
+
+    def density(self, x):
+        return {"sigma": trunc_exp(self.get_sigma_feat(self._normalize(x)))}
+
+    def _occupied_box(self):
+        """(tl, br, min_pos, max_pos): the bounding box of the occupied cells of the coarsest density grid, as the kept index
+        range per axis of the factors (host lists) and as the new corners of aabb_train (tensoRF/network.py:273-296)"""
+        import raymarching
+        hgs = self.bound / self.grid_size
+        thresh = min(self.density_thresh, self.mean_density)
+        occupied = self.density_grid[self.cascade - 1] > thresh
+        pos = raymarching.morton3D_invert(torch.nonzero(occupied).squeeze(-1))
+        if pos.shape[0] == 0:
+            raise RuntimeError("shrink_model: no cell of the coarsest cascade is above the density threshold")
+        pos = (2 * pos / (self.grid_size - 1) - 1) * (self.bound - hgs)
+        min_pos, max_pos = pos.amin(0) - hgs, pos.amax(0) + hgs
+        reso = torch.tensor(self.resolution, dtype=torch.long, device=self.aabb_train.device)
+        units = (self.aabb_train[3:] - self.aabb_train[:3]) / reso
+        tl = torch.round((min_pos - self.aabb_train[:3]) / units).long().clamp(min=0)
+        br = torch.minimum(torch.round((max_pos - self.aabb_train[:3]) / units).long(), reso)
+        return tl.tolist(), br.tolist(), min_pos, max_pos
+
+    def _cropped_to(self, tl_h, br_h, min_pos, max_pos):
+        """the tail of shrink_model, after the factors were cropped to _occupied_box()"""
+        self.aabb_train = torch.cat([min_pos, max_pos], dim=0).to(self.aabb_train.dtype)
+        # (the reference leaves `self.resolution` stale after the crop — it only reads it again in the next upsample; the
+        #  fused feature kernels take the factor extents from it, so it follows the parameters here)
+        self.resolution = [b - a for a, b in zip(tl_h, br_h)]
+        return tl_h, br_h
 
     def _fused_mlp_ok(self, feat, d_requires_grad=False):
         """the colour MLP (tensoRF/network.py:71-83: bias-free Linear -> ReLU chain, 150 -> 128 -> 128 -> 3) on the MFMA kernels
@@ -374,14 +474,6 @@ class NeRFNetwork(TensoRFCommon, NeRFRenderer):
         else:
             self.bg_net = None
 
-    def __getstate__(self):
-        """copy.deepcopy (teacher creation, EMA) and pickling leave the backward's sorted-point cache behind"""
-        state = self.__dict__.copy()
-        state.pop("_vm_bins", None)
-        state.pop("_l1_inv", None)
-        state.pop("_s3d_found_inf", None)  # (a trainer's scaler flag: re-attached by the trainer that owns the copy)
-        return state
-
     def init_one_svd(self, n_component, resolution, scale=0.1):
         mat, vec = [], []
         for i, vec_id in enumerate(self.vec_ids):
@@ -416,50 +508,33 @@ class NeRFNetwork(TensoRFCommon, NeRFRenderer):
         mf, vf = self._factors(mats, vecs, x)
         return torch.cat(mf, dim=0) * torch.cat(vf, dim=0)  # [3R, N]
 
-    def _use_native(self, x):
-        return self.fused_vm and x.is_cuda and x.dim() == 2 and x.shape[0] > 0
+    # what the shared host path (TensoRFCommon) asks of a backbone
+    _backend, _Features, _ColorBasis = s3d_hip.VmBackend, _VmFeatures, _VmColorBasis
+    _fused = property(lambda self: self.fused_vm)
+    _found_inf = _source_check
 
-    def get_sigma_feat(self, x):
-        if self._use_native(x):
-            return _VmFeatures.apply(x, self, True, *self.sigma_mat, *self.sigma_vec)
-        return self._sigma_feat_torch(x, self.sigma_mat, self.sigma_vec)
+    def _color_factors(self):
+        return list(self.color_mat) + list(self.color_vec)
 
-    fused_basis = True  # A-B runs: False = the products through HBM and basis_mat as an nn.Linear
+    @staticmethod
+    def _split(factors):
+        return factors[:3], factors[3:]
 
-    def get_color_feat(self, x):
-        if self._use_native(x):
-            if (self.fused_basis and not x.requires_grad and self.basis_mat.bias is None and self.basis_mat.out_features <= 32
-                    and sum(self.color_rank) <= 512 and max(self.color_rank) <= 64 and torch.is_autocast_enabled("cuda")
-                    and torch.get_autocast_dtype("cuda") == torch.float16):
-                return _VmColorBasis.apply(x, self, self.basis_mat.weight, *self.color_mat, *self.color_vec)
-            return _linear(self.basis_mat, _VmFeatures.apply(x, self, False, *self.color_mat, *self.color_vec).T)
-        return _linear(self.basis_mat, self._color_prod_torch(x, self.color_mat, self.color_vec).T)
+    @staticmethod
+    def _product_rows(lead):
+        return sum(m.shape[1] for m in lead[0])
 
-    def _normalize(self, x):
-        if (self.fused_vm and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous() and not x.requires_grad
-                and self.aabb_train.is_cuda and self.aabb_train.dtype == torch.float32):
-            out = torch.empty_like(x)  # (one launch instead of five, the same operations in the same order)
-            s3d_hip.VmBackend.aabb_normalize(x, self.aabb_train.contiguous(), out)
-            return out
-        return 2 * (x - self.aabb_train[:3]) / (self.aabb_train[3:] - self.aabb_train[:3]) - 1
+    def _basis_rank_ok(self):
+        return sum(self.color_rank) <= 512 and max(self.color_rank) <= 64
 
-    def forward(self, x, d):
-        x = self._normalize(x)
-        self.__dict__["_vm_bins"] = {}  # (the previous forward's sorted points)
-        sigma = trunc_exp(self.get_sigma_feat(x))
-        cf = self.get_color_feat(x)
-        if self._fused_mlp_ok(cf, d.requires_grad):
-            return sigma, self._color_mlp_fused(cf, d)
-        feat, dirs = self.encoder(cf), self.encoder_dir(d)
-        h = torch.cat([feat, dirs], dim=-1)
-        for k, layer in enumerate(self.color_net):
-            h = _linear(layer, h)
-            if k != self.num_layers - 1:
-                h = F.relu(h, inplace=True)
-        return sigma, torch.sigmoid(h)
-
-    def density(self, x):
-        return {"sigma": trunc_exp(self.get_sigma_feat(self._normalize(x)))}
+    def _shadows(self, mats, vecs):
+        """rank-fastest shadows of a factor set (VmBackend.transpose_factors), taken afresh at EVERY forward: the native optimizer
+        rewrites the parameters without touching `_version`, so nothing cheaper than the ~10 us launch says whether they are stale;
+        the forward and the backward of one step share them (the parameters do not change in between).  None: shapes the
+        16-byte loads do not cover (a rank that is not a multiple of four) or the switch `fused_shadows` off."""
+        if not getattr(self, "fused_shadows", True) or any(m.shape[1] % 4 for m in mats) or not all(t.is_cuda for t in mats):
+            return None
+        return s3d_hip.VmBackend.transpose_factors([m.detach() for m in mats], [v.detach() for v in vecs], self.resolution)
 
     fused_background = True  # False (test reference): the reference's op sequence
 
@@ -527,27 +602,10 @@ class NeRFNetwork(TensoRFCommon, NeRFRenderer):
         """crop aabb_train and every factor to the bounding box of the occupied cells of the coarsest density grid
         (tensoRF/network.py:273-318).  Returns (tl, br): the kept index range per axis.  The parameter set changes:
         re-create the optimizer afterwards (Trainer.rebuild_optimizer), as after upsample_model."""
-        import raymarching
-        hgs = self.bound / self.grid_size
-        thresh = min(self.density_thresh, self.mean_density)
-        occupied = self.density_grid[self.cascade - 1] > thresh
-        pos = raymarching.morton3D_invert(torch.nonzero(occupied).squeeze(-1))
-        if pos.shape[0] == 0:
-            raise RuntimeError("shrink_model: no cell of the coarsest cascade is above the density threshold")
-        pos = (2 * pos / (self.grid_size - 1) - 1) * (self.bound - hgs)
-        min_pos, max_pos = pos.amin(0) - hgs, pos.amax(0) + hgs
-        reso = torch.tensor(self.resolution, dtype=torch.long, device=self.aabb_train.device)
-        units = (self.aabb_train[3:] - self.aabb_train[:3]) / reso
-        tl = torch.round((min_pos - self.aabb_train[:3]) / units).long().clamp(min=0)
-        br = torch.minimum(torch.round((max_pos - self.aabb_train[:3]) / units).long(), reso)
-        tl_h, br_h = tl.tolist(), br.tolist()
+        tl_h, br_h, min_pos, max_pos = self._occupied_box()
         for i, vec_id in enumerate(self.vec_ids):
             m0, m1 = self.mat_ids[i]
             for vecs, mats in ((self.sigma_vec, self.sigma_mat), (self.color_vec, self.color_mat)):
                 vecs[i] = nn.Parameter(vecs[i].data[..., tl_h[vec_id]:br_h[vec_id], :].contiguous())
                 mats[i] = nn.Parameter(mats[i].data[..., tl_h[m1]:br_h[m1], tl_h[m0]:br_h[m0]].contiguous())
-        self.aabb_train = torch.cat([min_pos, max_pos], dim=0).to(self.aabb_train.dtype)
-        # (the reference leaves `self.resolution` stale after the crop — it only reads it again in the next upsample; the
-        #  fused feature kernels take the factor extents from it, so it follows the parameters here)
-        self.resolution = [b - a for a, b in zip(tl_h, br_h)]
-        return tl_h, br_h
+        return self._cropped_to(tl_h, br_h, min_pos, max_pos)

@@ -9,112 +9,27 @@ On the GPU the three grid_sample calls + two products + sum (or basis_mat) of `g
 kernel per call (`s3d_cp_features_forward` / `s3d_cp_color_forward`, csrc/tensorf_cp.hip) and their parameter gradients as one
 (`s3d_cp_features_backward` / `s3d_cp_color_backward`: points sorted by 64-row line chunk, fp32 sums per cell in LDS, one global
 atomic per cell and workgroup instead of one per (point, rank, tap)).  The factor gradients are NOT marked as checked: a
-GradScaler reads their 1.4 MB itself.  A gradient w.r.t. the coordinates falls back to the grid_sample sequence."""
+GradScaler reads their 1.4 MB itself.  A gradient w.r.t. the coordinates falls back to the grid_sample sequence.
+
+The host path that drives these kernels (the two autograd Functions, the sorted-point cache, `forward` / `density`, the dispatch
+of `get_sigma_feat` / `get_color_feat`) is the vector-matrix network's: tensoRF/network.py, `TensoRFCommon`.  This file holds
+the parameters, the grid_sample route, the line crop / resample loops and what the shared path asks of a backbone."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 import s3d_hip
-from activation import trunc_exp
 from encoding import get_encoder
 from nerf.renderer import NeRFRenderer
-from tensoRF.network import TensoRFCommon, _linear, _MeanAbsSum
+from tensoRF.network import TensoRFCommon, _ColorBasis, _Features, _MeanAbsSum
 
 
-def _shadows(net, lines):
-    """rank-fastest shadows of a line set (CpBackend.transpose_lines), taken afresh at every forward (the native optimizer
-    rewrites the parameters without touching `_version`); the forward and the backward of one step share them"""
-    if not getattr(net, "fused_shadows", True):
-        return None
-    return s3d_hip.CpBackend.transpose_lines([v.detach() for v in lines], net.resolution)
+class _CpFeatures(_Features):
+    pass
 
 
-def _bins(net, x, n_valid=None):
-    """the points of x sorted by line chunk (CpBackend.backward_bins): x and the resolution decide it, so the density and the
-    colour features of one forward share the sort.  Kept on the network, keyed by the storage of x, dropped after two uses or at
-    the next forward (tensoRF/network.py: _bins)."""
-    cache = net.__dict__.setdefault("_cp_bins", {})
-    key = (x.data_ptr(), x._version, x.shape[0], tuple(net.resolution), None if n_valid is None else n_valid.data_ptr())
-    if key not in cache:
-        if len(cache) >= 4:
-            cache.clear()
-        cache[key] = [x, s3d_hip.CpBackend.backward_bins(x, net.resolution, n_valid), 2]
-    ent = cache[key]
-    ent[2] -= 1
-    if ent[2] <= 0:
-        del cache[key]
-    return ent[1]
-
-
-def _torch_backward(ctx, fn, x, lines, g, reduce, extra=()):
-    """the reference's op sequence re-run under autograd (a gradient for the coordinates was asked for)"""
-    if ctx.nv is not None:  # (the torch route sums over every row: the absent ones hold anything)
-        live = torch.arange(x.shape[0], device=x.device) < (ctx.nv.reshape(-1)[:1] + 127) // 128 * 128
-        g = torch.where(live if reduce else live.unsqueeze(0), g, torch.zeros((), dtype=g.dtype, device=g.device))
-    with torch.enable_grad():
-        leaves = [v.detach().requires_grad_(True) for v in lines]
-        xin = x.detach().requires_grad_(True)
-        out = fn(xin, leaves)
-        grads = torch.autograd.grad(out, [xin] + leaves, g.contiguous())
-    return grads[0], grads[1:]
-
-
-class _CpFeatures(torch.autograd.Function):
-    """forward: one HIP kernel; backward: the chunk-binned HIP kernel for the line gradients"""
-
-    @staticmethod
-    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)  # grid_sample is an fp32 op under autocast too
-    def forward(ctx, x, net, reduce, *lines):
-        x = x.contiguous()
-        N = x.shape[0]
-        out = torch.empty((N,) if reduce else (lines[0].shape[1], N), dtype=torch.float32, device=x.device)
-        nv = s3d_hip.active_row_limit(N)  # (padded sample batch: rows behind the device-side count are absent)
-        sh = _shadows(net, lines)
-        s3d_hip.CpBackend.features_forward(x, [v.contiguous() for v in lines], net.resolution, reduce, out, n_valid=nv, shadows=sh)
-        ctx.save_for_backward(x, *lines)
-        ctx.net, ctx.reduce, ctx.nv, ctx.sh = net, reduce, nv, sh
-        return out
-
-    @staticmethod
-    @torch.amp.custom_bwd(device_type="cuda")
-    def backward(ctx, g):
-        x, *lines = ctx.saved_tensors
-        if not ctx.needs_input_grad[0]:
-            g = g if ctx.reduce else g.t()  # [R, N] gradient of the `.T` consumer: point-major underneath
-            gl = s3d_hip.CpBackend.features_backward(x, [v.contiguous() for v in lines], ctx.net.resolution, ctx.reduce,
-                                                     g.float().contiguous(), _bins(ctx.net, x, ctx.nv), None, n_valid=ctx.nv,
-                                                     shadows=ctx.sh)
-            return (None, None, None) + tuple(gl)
-        fn = ctx.net._sigma_feat_torch if ctx.reduce else ctx.net._color_prod_torch
-        gx, gl = _torch_backward(ctx, fn, x, lines, g, ctx.reduce)
-        return (gx, None, None) + tuple(gl)
-
-
-class _CpColorBasis(torch.autograd.Function):
-    """basis_mat(vec_feat.T) of tensoRF/network_cp.py:105-109 in ONE kernel per direction (s3d_cp_color_forward / _backward): the
-    [288, N] products never leave the chip.  Arithmetic of the fp16 autocast Linear: operands rounded to binary16, fp32
-    accumulation, binary16 output."""
-
-    @staticmethod
-    def forward(ctx, x, net, weight, *lines):
-        x = x.float().contiguous()
-        lines_c = [v.float().contiguous() for v in lines]
-        w16 = weight.detach().to(torch.float16).contiguous()
-        out = torch.empty(x.shape[0], w16.shape[0], dtype=torch.float16, device=x.device)
-        nv = s3d_hip.active_row_limit(x.shape[0])
-        sh = _shadows(net, lines_c)
-        s3d_hip.CpBackend.color_forward(x, lines_c, net.resolution, w16, out, n_valid=nv, shadows=sh)
-        ctx.save_for_backward(x, w16, *lines)
-        ctx.net, ctx.nv, ctx.sh = net, nv, sh
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        x, w16, *lines = ctx.saved_tensors
-        # (g as it arrives: a [:, :27] view of _MlpInput's zero-padded [N, 32] gradient is used in place, anything else is padded)
-        gl, gw = s3d_hip.CpBackend.color_backward(x, [v.float().contiguous() for v in lines], ctx.net.resolution, w16,
-                                                  g.to(torch.float16), _bins(ctx.net, x, ctx.nv), None, n_valid=ctx.nv, shadows=ctx.sh)
-        return (None, None, gw) + tuple(gl)
+class _CpColorBasis(_ColorBasis):
+    pass
 
 
 class NeRFNetwork(TensoRFCommon, NeRFRenderer):
@@ -140,14 +55,6 @@ class NeRFNetwork(TensoRFCommon, NeRFRenderer):
         dims = [self.in_dim] + [hidden_dim] * (num_layers - 1) + [3]
         self.color_net = nn.ModuleList([nn.Linear(i, o, bias=False) for i, o in zip(dims[:-1], dims[1:])])
 
-    def __getstate__(self):
-        """copy.deepcopy and pickling leave the backward's sorted-point cache behind"""
-        state = self.__dict__.copy()
-        state.pop("_cp_bins", None)
-        state.pop("_l1_inv", None)
-        state.pop("_s3d_found_inf", None)
-        return state
-
     def init_one_svd(self, n_component, resolution, scale=0.2):
         return nn.ParameterList([nn.Parameter(scale * torch.randn((1, n_component[i], resolution[vec_id], 1)))  # [1, R, D, 1]
                                  for i, vec_id in enumerate(self.vec_ids)])
@@ -169,51 +76,36 @@ class NeRFNetwork(TensoRFCommon, NeRFRenderer):
     def _sigma_feat_torch(self, x, vecs):
         return torch.sum(self._color_prod_torch(x, vecs), dim=0)
 
+    # what the shared host path (tensoRF/network.py: TensoRFCommon) asks of a backbone
+    _backend, _Features, _ColorBasis = s3d_hip.CpBackend, _CpFeatures, _CpColorBasis
+    _fused = property(lambda self: self.fused_cp)
+
+    def _found_inf(self, factors, *more):
+        return None  # (the line gradients are not marked as checked: a GradScaler reads their 1.4 MB itself)
+
+    def _color_factors(self):
+        return list(self.color_vec)
+
+    @staticmethod
+    def _split(factors):
+        return (factors,)
+
+    @staticmethod
+    def _product_rows(lead):
+        return lead[0][0].shape[1]
+
+    def _basis_rank_ok(self):
+        return self.color_rank[0] <= 512
+
+    def _shadows(self, lines):
+        """rank-fastest shadows of a line set (CpBackend.transpose_lines), taken afresh at every forward (the native optimizer
+        rewrites the parameters without touching `_version`); the forward and the backward of one step share them"""
+        if not getattr(self, "fused_shadows", True):
+            return None
+        return s3d_hip.CpBackend.transpose_lines([v.detach() for v in lines], self.resolution)
+
     def _use_native(self, x):
-        return self.fused_cp and x.is_cuda and x.dim() == 2 and x.shape[0] > 0 and all(v.dtype == torch.float32 for v in self.sigma_vec)
-
-    def get_sigma_feat(self, x):
-        if self._use_native(x):
-            return _CpFeatures.apply(x, self, True, *self.sigma_vec)
-        return self._sigma_feat_torch(x, self.sigma_vec)
-
-    fused_basis = True  # A-B runs: False = the products through HBM and basis_mat as an nn.Linear
-
-    def get_color_feat(self, x):
-        if self._use_native(x):
-            if (self.fused_basis and not x.requires_grad and self.basis_mat.bias is None and self.basis_mat.out_features <= 32
-                    and self.color_rank[0] <= 512 and torch.is_autocast_enabled("cuda")
-                    and torch.get_autocast_dtype("cuda") == torch.float16):
-                return _CpColorBasis.apply(x, self, self.basis_mat.weight, *self.color_vec)
-            return _linear(self.basis_mat, _CpFeatures.apply(x, self, False, *self.color_vec).T)
-        return _linear(self.basis_mat, self._color_prod_torch(x, self.color_vec).T)
-
-    def _normalize(self, x):
-        if (self.fused_cp and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous() and not x.requires_grad
-                and self.aabb_train.is_cuda and self.aabb_train.dtype == torch.float32):
-            out = torch.empty_like(x)  # (one launch instead of five, the same operations in the same order)
-            s3d_hip.VmBackend.aabb_normalize(x, self.aabb_train.contiguous(), out)
-            return out
-        return 2 * (x - self.aabb_train[:3]) / (self.aabb_train[3:] - self.aabb_train[:3]) - 1
-
-    def _colors(self, cf, d):
-        if self._fused_mlp_ok(cf, d.requires_grad):
-            return self._color_mlp_fused(cf, d)
-        h = torch.cat([self.encoder(cf), self.encoder_dir(d)], dim=-1)
-        for k, layer in enumerate(self.color_net):
-            h = _linear(layer, h)
-            if k != self.num_layers - 1:
-                h = F.relu(h, inplace=True)
-        return torch.sigmoid(h)
-
-    def forward(self, x, d):
-        x = self._normalize(x)
-        self.__dict__["_cp_bins"] = {}  # (the previous forward's sorted points)
-        sigma = trunc_exp(self.get_sigma_feat(x))
-        return sigma, self._colors(self.get_color_feat(x), d)
-
-    def density(self, x):
-        return {"sigma": trunc_exp(self.get_sigma_feat(self._normalize(x)))}
+        return super()._use_native(x) and all(v.dtype == torch.float32 for v in self.sigma_vec)
 
     def color(self, x, d, mask=None, **kwargs):
         """masked inference (tensoRF/network_cp.py:156-189): colours where `mask` is set, zeros elsewhere"""
@@ -262,24 +154,8 @@ class NeRFNetwork(TensoRFCommon, NeRFRenderer):
         """crop aabb_train and every line to the bounding box of the occupied cells of the coarsest density grid
         (tensoRF/network_cp.py:214-246).  Returns (tl, br): the kept index range per axis.  The parameter set changes:
         re-create the optimizer afterwards (Trainer.rebuild_optimizer), as after upsample_model."""
-        import raymarching
-        hgs = self.bound / self.grid_size
-        thresh = min(self.density_thresh, self.mean_density)
-        occupied = self.density_grid[self.cascade - 1] > thresh
-        pos = raymarching.morton3D_invert(torch.nonzero(occupied).squeeze(-1))
-        if pos.shape[0] == 0:
-            raise RuntimeError("shrink_model: no cell of the coarsest cascade is above the density threshold")
-        pos = (2 * pos / (self.grid_size - 1) - 1) * (self.bound - hgs)
-        min_pos, max_pos = pos.amin(0) - hgs, pos.amax(0) + hgs
-        reso = torch.tensor(self.resolution, dtype=torch.long, device=self.aabb_train.device)
-        units = (self.aabb_train[3:] - self.aabb_train[:3]) / reso
-        tl = torch.round((min_pos - self.aabb_train[:3]) / units).long().clamp(min=0)
-        br = torch.minimum(torch.round((max_pos - self.aabb_train[:3]) / units).long(), reso)
-        tl_h, br_h = tl.tolist(), br.tolist()
+        tl_h, br_h, min_pos, max_pos = self._occupied_box()
         for i, vec_id in enumerate(self.vec_ids):
             for vecs in (self.sigma_vec, self.color_vec):
                 vecs[i] = nn.Parameter(vecs[i].data[..., tl_h[vec_id]:br_h[vec_id], :].contiguous())
-        self.aabb_train = torch.cat([min_pos, max_pos], dim=0).to(self.aabb_train.dtype)
-        # (the reference leaves `self.resolution` stale after the crop; the fused kernels take the line extents from it)
-        self.resolution = [b - a for a, b in zip(tl_h, br_h)]
-        return tl_h, br_h
+        return self._cropped_to(tl_h, br_h, min_pos, max_pos)

@@ -455,3 +455,79 @@ def test_cp_save_mesh_writes_a_ply(hip, tmp_path):
     v, t = read_ply(path)
     assert len(v) > 0 and len(t) > 0 and t.min() >= 0 and t.max() < len(v)
     assert np.isfinite(v).all() and float(np.abs(v).max()) <= 1.0 + 1e-6
+
+
+@pytest.mark.parametrize("kind", ["vm", "cp"])
+def test_tensorf_backbones_take_one_sort_and_one_shadow_set_per_factor_set_and_step(hip, kind):
+    """what the shared host path of the two backbones (tensoRF/network.py: TensoRFCommon) shares within a step, counted at the
+    backend classes — replaced on the class, so the networks must look the backend up at call time: the density and the colour
+    backward use ONE sort of the points, each factor set's shadows are taken once (in the forward, reused by the backward), and
+    the sorted-point cache on the network is empty when both consumers have run.  Numbers cannot show any of this."""
+    import s3d_hip
+    from tensoRF import network as vm, network_cp as cp
+    key = vm.BINS
+    torch.manual_seed(5)
+    if kind == "vm":
+        net = vm.NeRFNetwork(resolution=[24, 20, 16], sigma_rank=[8] * 3, color_rank=[16] * 3, bound=1, cuda_ray=True).cuda()
+        be, transpose = hip.VmBackend, "transpose_factors"
+    else:
+        net = cp.NeRFNetwork(resolution=[24, 20, 16], sigma_rank=[8] * 3, color_rank=[32] * 3, bound=1, cuda_ray=True).cuda()
+        be, transpose = hip.CpBackend, "transpose_lines"
+    N, live = 384, 256
+    g = torch.Generator().manual_seed(6)
+    xs = [(torch.rand(N, 3, generator=g) * 2 - 1).cuda() for _ in range(2)]
+    d = torch.nn.functional.normalize(torch.randn(N, 3, generator=g), dim=-1).cuda()
+    ws, wr = torch.randn(N, generator=g).cuda(), torch.randn(N, 3, generator=g).cuda()
+    counts, saved = {"backward_bins": 0, transpose: 0}, {n: be.__dict__[n] for n in ("backward_bins", transpose)}
+
+    def counting(name, fn):
+        def wrapper(*a, **kw):
+            counts[name] += 1
+            return fn(*a, **kw)
+        return staticmethod(wrapper)
+
+    def step(x, dirs, rows=N, sigma_only=False):
+        """(sorts, transposes) of one forward + backward on the first `rows` rows"""
+        net.zero_grad(set_to_none=True)
+        before = dict(counts)
+        with torch.autocast("cuda", dtype=torch.float16):
+            sigma, rgb = net(x, dirs)
+        prefix = "_Vm" if kind == "vm" else "_Cp"  # (the fused routes: the density features and the basis_mat Function)
+        assert prefix + "FeaturesBackward" in _graph_nodes(sigma) and prefix + "ColorBasisBackward" in _graph_nodes(rgb)
+        loss = (sigma[:rows].float() * ws[:rows]).sum()
+        (loss if sigma_only else loss + (rgb[:rows].float() * wr[:rows]).sum()).backward()
+        return counts["backward_bins"] - before["backward_bins"], counts[transpose] - before[transpose]
+
+    try:
+        for name, fn in saved.items():
+            setattr(be, name, counting(name, getattr(be, name)))
+        for x in xs:  # (new points the second time: another cache entry, the first one let go)
+            assert step(x, d) == (1, 2)
+            assert net.__dict__[key] == {}
+        before = dict(counts)
+        with torch.no_grad():
+            net.density(xs[0])
+        assert (counts["backward_bins"] - before["backward_bins"], counts[transpose] - before[transpose]) == (0, 1)
+        # the density's backward alone: one consumer of two, the entry waits for the second and the next forward drops it
+        assert step(xs[0], d, sigma_only=True) == (1, 2)
+        assert [e[2] for e in net.__dict__[key].values()] == [1]
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
+            net(xs[1], d)
+        assert net.__dict__[key] == {}
+        # a padded batch (s3d_hip.row_limit): still one sort, and the gradients of the rows in front of round_up(count, 128)
+        xp = xs[0].clone()
+        xp[live:] = float("nan")
+        with s3d_hip.row_limit(torch.tensor([200, 0], dtype=torch.int32, device="cuda"), N):
+            assert step(xp, d, rows=live)[0] == 1
+        padded = {n: p.grad.float().clone() for n, p in net.named_parameters() if p.grad is not None}
+        step(xs[0][:live].contiguous(), d[:live].contiguous(), rows=live)
+        plain = {n: p.grad.float().clone() for n, p in net.named_parameters() if p.grad is not None}
+    finally:
+        for name, fn in saved.items():
+            setattr(be, name, fn)
+    assert set(plain) == set(padded) == {n for n, _ in net.named_parameters()}
+    for n, a in plain.items():  # (tolerances of test_cp_padded_sample_batch_follows_the_device_side_count)
+        b = padded[n]
+        assert bool(torch.isfinite(b).all()), n
+        tol = (2e-3 if n.startswith("color_net") else 1e-5) * float(a.abs().max()) + 1e-12
+        assert float((a - b).abs().max()) <= tol, (n, float((a - b).abs().max()), float(a.abs().max()))

@@ -373,8 +373,14 @@ def test_round5_host_logic_of_the_tensorf_step_on_cpu(oracle_wrappers):
     net = trf.NeRFNetwork(resolution=[9, 8, 7], sigma_rank=[2, 3, 2], color_rank=[3, 3, 3], bound=1, cuda_ray=True)
     assert abs(float(net.density_loss_value()) - float(net.density_loss())) <= 1e-6 * float(net.density_loss())
     assert not net.density_loss_value().requires_grad and net.density_loss().requires_grad
-    st = net.__getstate__()
-    assert "_l1_inv" not in st and "_vm_bins" not in st and "_s3d_found_inf" not in st
+    from tensoRF import network_cp as trf_cp
+    cp_net = trf_cp.NeRFNetwork(resolution=[9, 8, 7], sigma_rank=[2, 2, 2], color_rank=[3, 3, 3], bound=1, cuda_ray=True)
+    for n in (net, cp_net):  # (both backbones keep the sorted-point cache under the one key: a forward creates it)
+        with torch.no_grad():
+            n(torch.rand(5, 3) * 2 - 1, torch.nn.functional.normalize(torch.randn(5, 3), dim=-1))
+        assert trf.BINS in n.__dict__
+        st = n.__getstate__()
+        assert "_l1_inv" not in st and trf.BINS not in st and "_s3d_found_inf" not in st
     # trainers on a device without the HIP path
     from tensoRF.utils import Trainer
     tr = Trainer(net, lr0=2e-2, lr1=1e-3, l1_reg_weight=1e-3, fp16=False, update_extra_interval=10 ** 9, native_optim=False)

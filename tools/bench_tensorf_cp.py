@@ -63,6 +63,7 @@ def _marched_samples(n_rays=4096):
 
 
 def features(reps):
+    from tensoRF.network import BINS
     net = _cp()
     x = _marched_samples()
     m = x.shape[0]
@@ -75,7 +76,7 @@ def features(reps):
 
     def fwd_bwd():
         net.zero_grad(set_to_none=True)
-        net.__dict__["_cp_bins"] = {}
+        net.__dict__[BINS] = {}
         with torch.autocast("cuda", dtype=torch.float16):
             s, c = net.get_sigma_feat(x), net.get_color_feat(x)
         ((s * gs).sum() + (c.float() * gc).sum()).backward()
