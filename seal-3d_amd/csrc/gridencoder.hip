@@ -2130,23 +2130,35 @@ inline BinLayout3 bin_layout3(uint32_t B, uint32_t D, uint32_t C, uint32_t L, ui
 // control block of the third generation: hdr[kMaxLevels] | ticket (byte 128) | cursor[L][smax][NSUB] (x kCurStride words) | ovn[L][smax]
 inline size_t bin3_control_bytes(const BinLayout3& lay, uint32_t L) { return align256(lay.ovn + (size_t)L * lay.smax * 4); }
 
-// One backward call as the launch helpers below see it: the entry point's arguments, table and gradient pointers still
-// untyped (the templated leaves cast them to T), and what the path taken reports back
+// One backward call: the entry point's arguments in the order of s3d_grid_encode_backward (seal3d_hip.h), which the three
+// exported functions fill in; table and gradient pointers still untyped (the templated leaves cast them to T)
 struct GridBwd {
-    const void *grad, *dy_dx;
-    void *grad_emb, *grad_inputs;
+    const void* grad;
     const float* inputs;
     const int32_t* offsets;
-    uint32_t B, C, L, max_level_rows, gridtype, interp;
+    void* grad_emb;
+    uint32_t max_level_rows, B, D, C, L;
+    float S;
+    uint32_t H;
+    const void* dy_dx;  // (the entry points with the update inside take no input Jacobian: nullptr)
+    void* grad_inputs;
+    uint32_t gridtype;
     bool ac;
-    LevelScales sc;
-    unsigned char *ws, *control;
-    size_t ws_bytes, control_bytes;
+    uint32_t interp;
+    int dtype;
+    unsigned char* ws;
+    size_t ws_bytes;
+    float bound;
+    const int32_t* n_valid;
     int force_path;  // 0 auto: binned for large batches; 1 direct atomics; 2 binned
+    float* found_inf;  // s3d_grid_encode_backward(found_inf), or nullptr
+    unsigned char* control;
+    size_t control_bytes;
     hipStream_t st;
-    float* found_inf;      // s3d_grid_encode_backward(found_inf), or nullptr
-    const GridAdam* adam;  // s3d_grid_encode_backward_adam: the update to apply in the accumulate, or nullptr
     const s3d_step_tail* tail;  // s3d_grid_encode_backward_adam_tail: work to run inside the two binned launches, or nullptr
+    // made of them by grid_backward(), for the launch helpers below
+    LevelScales sc;
+    const GridAdam* adam;  // s3d_grid_encode_backward_adam: the update to apply in the accumulate, or nullptr
 };
 struct GridBwdResult {
     bool reported;  // the path taken has written found_inf while it accumulated (otherwise the caller checks the table)
@@ -2213,14 +2225,20 @@ int tail_in_front(const s3d_step_tail& t, hipStream_t st) {
     return S3D_OK;
 }
 
-// `control`: the caller's control block if it is large enough for this layout, else nullptr
-template <typename T, uint32_t D, uint32_t C, bool FIXED24>
-int launch_binned3(const GridBwd& a, const BinLayout3& lay, unsigned char* control, GridBwdResult& res, const TailPlan* tp = nullptr) {
-    const T* grad = (const T*)a.grad;
-    T* grad_emb = (T*)a.grad_emb;
-    const uint32_t B = a.B, L = a.L;
-    unsigned char* ws = a.ws;
-    hipStream_t st = a.st;
+// where the third generation's two kernels find their buffers: control words (the caller's block, or the head of the workspace)
+// and record arrays (workspace)
+struct Bin3Buffers {
+    uint32_t *hdr, *done, *cursor, *ovn;
+    uint2* ovl;
+    uint16_t *keys, *skeys;
+    uint32_t *vals, *svals;
+};
+
+// the scatter + accumulate pair of levels [l0, l0 + nl): plain, with the table's update in the accumulate (ADAM), with a step
+// tail's riders in both launches as well (ADAM, TAIL: one more row of scatter workgroups for them)
+template <typename T, uint32_t D, uint32_t C, bool FIXED24, bool ADAM, bool TAIL>
+int launch_bin_pair6(const GridBwd& a, const BinLayout3& lay, const Bin3Buffers& b, uint32_t l0, uint32_t nl, const GridAdam& adam,
+                     const ScatterTail& scatter_tail, const AccTail& acc_tail) {
     constexpr uint32_t P = S3D_BIN3_P;
     constexpr uint32_t K = 1u << D;
     constexpr uint32_t stage_max = 4 * kBinMaxSlices * 4 + P * K * 8;  // counters, run starts, run table (8 B), staged records
@@ -2228,83 +2246,57 @@ int launch_binned3(const GridBwd& a, const BinLayout3& lay, unsigned char* contr
     static std::atomic<uint64_t> attr_devs{0};
     int dev;
     if (device_needs_setup(attr_devs, &dev)) {
-        S3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bin_scatter6<T, D, C, FIXED24, P>),
+        S3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bin_scatter6<T, D, C, FIXED24, P, TAIL>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage_max));
-        S3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bin_accumulate6<T, D, C, FIXED24, P>),
+        S3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bin_accumulate6<T, D, C, FIXED24, P, ADAM, TAIL>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBinAccBytes));
         device_setup_done(attr_devs, dev);
     }
+    hipLaunchKernelGGL((k_bin_scatter6<T, D, C, FIXED24, P, TAIL>), dim3(lay.chunks, nl + (TAIL ? 1 : 0)), dim3(P), stage, a.st,
+                       (const T*)a.grad, a.inputs, a.offsets, a.B, l0, a.sc, b.hdr, b.cursor, b.ovn, b.ovl, lay.smax, lay.chunks, lay.cap,
+                       b.keys, b.vals, b.skeys, b.svals, a.gridtype, a.ac, a.interp, scatter_tail);
+    hipLaunchKernelGGL((k_bin_accumulate6<T, D, C, FIXED24, P, ADAM, TAIL>), dim3(std::min(lay.smax * nl, device_cus() * kBinAccPerCu)),
+                       dim3(kBinAccThreads), kBinAccBytes, a.st, (const uint16_t*)b.keys, (const uint32_t*)b.vals,
+                       (const uint16_t*)b.skeys, (const uint32_t*)b.svals, a.offsets, (T*)a.grad_emb, a.B, l0, nl, b.hdr, b.done, b.cursor,
+                       b.ovn, (const uint2*)b.ovl, lay.smax, lay.chunks, lay.cap, a.found_inf, adam, acc_tail);
+    return S3D_OK;
+}
+
+// `control`: the caller's control block if it is large enough for this layout, else nullptr
+template <typename T, uint32_t D, uint32_t C, bool FIXED24>
+int launch_binned3(const GridBwd& a, const BinLayout3& lay, unsigned char* control, GridBwdResult& res, const TailPlan* tp = nullptr) {
+    const uint32_t B = a.B, L = a.L;
+    unsigned char* ws = a.ws;
     // a caller-owned control block is all zero between calls (the accumulate leaves it so); without one the words live at
     // the head of the workspace and are cleared by a launch of their own
     unsigned char* cb = control ? control : ws;
-    uint32_t* hdr = reinterpret_cast<uint32_t*>(cb);
-    uint32_t* done = reinterpret_cast<uint32_t*>(cb + 128);
-    uint32_t* cursor = reinterpret_cast<uint32_t*>(cb + lay.cursor);
-    uint32_t* ovn = reinterpret_cast<uint32_t*>(cb + lay.ovn);
-    uint2* ovl = reinterpret_cast<uint2*>(ws + lay.ovl);
-    uint16_t* keys = reinterpret_cast<uint16_t*>(ws + lay.keys);
-    uint32_t* vals = reinterpret_cast<uint32_t*>(ws + lay.vals);
-    uint16_t* skeys = reinterpret_cast<uint16_t*>(ws + lay.skeys);
-    uint32_t* svals = reinterpret_cast<uint32_t*>(ws + lay.svals);
+    const Bin3Buffers b{reinterpret_cast<uint32_t*>(cb), reinterpret_cast<uint32_t*>(cb + 128), reinterpret_cast<uint32_t*>(cb + lay.cursor),
+                        reinterpret_cast<uint32_t*>(cb + lay.ovn), reinterpret_cast<uint2*>(ws + lay.ovl),
+                        reinterpret_cast<uint16_t*>(ws + lay.keys), reinterpret_cast<uint16_t*>(ws + lay.skeys),
+                        reinterpret_cast<uint32_t*>(ws + lay.vals), reinterpret_cast<uint32_t*>(ws + lay.svals)};
     if (!control) {
         const uint32_t clear_words = (uint32_t)(bin3_control_bytes(lay, L) / 4);
-        hipLaunchKernelGGL(k_zero_words, dim3(div_up<uint32_t>(clear_words, 1024)), dim3(1024), 0, st, hdr, clear_words);
+        hipLaunchKernelGGL(k_zero_words, dim3(div_up<uint32_t>(clear_words, 1024)), dim3(1024), 0, a.st, b.hdr, clear_words);
     }
     if constexpr (!FIXED24)
-        hipLaunchKernelGGL((k_bin_amax<T, D, C>), dim3(std::min<uint32_t>(div_up<uint32_t>(B, 1024), 64u), L), dim3(1024), 0, st, grad,
-                           a.inputs, B, a.sc, hdr);
-    const uint32_t cus = device_cus();
+        hipLaunchKernelGGL((k_bin_amax<T, D, C>), dim3(std::min<uint32_t>(div_up<uint32_t>(B, 1024), 64u), L), dim3(1024), 0, a.st,
+                           (const T*)a.grad, a.inputs, B, a.sc, b.hdr);
     for (uint32_t l0 = 0; l0 < L; l0 += lay.levels_per_pass) {
         const uint32_t nl = (L - l0 < lay.levels_per_pass) ? L - l0 : lay.levels_per_pass;
-        const uint32_t items = lay.smax * nl;
+        int rc = S3D_OK;
         bool fused = false;
         if constexpr (FIXED24 && sizeof(T) == 2 && C == 2) {
-            if (tp && a.adam && nl == L) {  // (launch_backward_c checked it: one pass, the fused update) both launches with riders
-                static std::atomic<uint64_t> attr_tail{0};
-                int dev3;
-                if (device_needs_setup(attr_tail, &dev3)) {
-                    S3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bin_scatter6<T, D, C, FIXED24, P, true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage_max));
-                    S3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bin_accumulate6<T, D, C, FIXED24, P, true, true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBinAccBytes));
-                    device_setup_done(attr_tail, dev3);
-                }
-                hipLaunchKernelGGL((k_bin_scatter6<T, D, C, FIXED24, P, true>), dim3(lay.chunks, nl + 1), dim3(P), stage, st, grad, a.inputs,
-                                   a.offsets, B, l0, a.sc, hdr, cursor, ovn, ovl, lay.smax, lay.chunks, lay.cap, keys, vals, skeys, svals,
-                                   a.gridtype, a.ac, a.interp, tp->sc);
-                hipLaunchKernelGGL((k_bin_accumulate6<T, D, C, FIXED24, P, true, true>), dim3(std::min(items, cus * kBinAccPerCu)),
-                                   dim3(kBinAccThreads), kBinAccBytes, st, (const uint16_t*)keys, (const uint32_t*)vals, (const uint16_t*)skeys,
-                                   (const uint32_t*)svals, a.offsets, grad_emb, B, l0, nl, hdr, done, cursor, ovn, (const uint2*)ovl, lay.smax,
-                                   lay.chunks, lay.cap, a.found_inf, *a.adam, tp->ac);
-                res.applied = true;
+            fused = a.adam && nl == L;  // (one pass covers every level: the skip decision needs all poison words up front)
+            if (fused && tp) {  // (launch_backward_c checked it: one pass, the fused update) both launches with riders
+                rc = launch_bin_pair6<T, D, C, FIXED24, true, true>(a, lay, b, l0, nl, *a.adam, tp->sc, tp->ac);
                 res.tail = tp->want;
-                continue;
+            } else if (fused) {
+                rc = launch_bin_pair6<T, D, C, FIXED24, true, false>(a, lay, b, l0, nl, *a.adam, ScatterTail{}, AccTail{});
             }
         }
-        hipLaunchKernelGGL((k_bin_scatter6<T, D, C, FIXED24, P>), dim3(lay.chunks, nl), dim3(P), stage, st, grad, a.inputs, a.offsets, B,
-                           l0, a.sc, hdr, cursor, ovn, ovl, lay.smax, lay.chunks, lay.cap, keys, vals, skeys, svals, a.gridtype, a.ac,
-                           a.interp, ScatterTail{});
-        if constexpr (FIXED24 && sizeof(T) == 2 && C == 2) {
-            if (a.adam && nl == L) {  // (one pass covers every level: the skip decision needs all poison words up front)
-                static std::atomic<uint64_t> attr_adam{0};
-                int dev2;
-                if (device_needs_setup(attr_adam, &dev2)) {
-                    S3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bin_accumulate6<T, D, C, FIXED24, P, true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBinAccBytes));
-                    device_setup_done(attr_adam, dev2);
-                }
-                hipLaunchKernelGGL((k_bin_accumulate6<T, D, C, FIXED24, P, true>), dim3(std::min(items, cus * kBinAccPerCu)), dim3(kBinAccThreads),
-                                   kBinAccBytes, st, (const uint16_t*)keys, (const uint32_t*)vals, (const uint16_t*)skeys, (const uint32_t*)svals,
-                                   a.offsets, grad_emb, B, l0, nl, hdr, done, cursor, ovn, (const uint2*)ovl, lay.smax, lay.chunks, lay.cap,
-                                   a.found_inf, *a.adam, AccTail{});
-                fused = true;
-                res.applied = true;
-            }
-        }
-        if (!fused)
-        hipLaunchKernelGGL((k_bin_accumulate6<T, D, C, FIXED24, P>), dim3(std::min(items, cus * kBinAccPerCu)), dim3(kBinAccThreads), kBinAccBytes, st,
-                           (const uint16_t*)keys, (const uint32_t*)vals, (const uint16_t*)skeys, (const uint32_t*)svals, a.offsets,
-                           grad_emb, B, l0, nl, hdr, done, cursor, ovn, (const uint2*)ovl, lay.smax, lay.chunks, lay.cap, a.found_inf, GridAdam{}, AccTail{});
+        if (!fused) rc = launch_bin_pair6<T, D, C, FIXED24, false, false>(a, lay, b, l0, nl, GridAdam{}, ScatterTail{}, AccTail{});
+        if (rc != S3D_OK) return rc;
+        res.applied = res.applied || fused;
     }
     res.reported = true;
     return check_launch("grid_encode_backward");
@@ -2548,38 +2540,46 @@ S3D_EXPORT size_t s3d_grid_encode_backward_control_size(uint32_t D, uint32_t C, 
 }
 
 namespace {
-// s3d_grid_encode_backward, and with `adam` the fused update of s3d_grid_encode_backward_adam (*applied: whether it ran)
-int grid_backward(const void* grad, const float* inputs, const int32_t* offsets, void* grad_embeddings, uint32_t max_level_rows,
-                  uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, const void* dy_dx, void* grad_inputs,
-                  uint32_t gridtype, int align_corners, uint32_t interp, int dtype, void* workspace, size_t workspace_bytes, float bound,
-                  const int32_t* n_valid, int path, float* found_inf, void* control, size_t control_bytes, s3d_stream_t stream,
-                  const GridAdam* adam, bool* applied, const s3d_step_tail* tail = nullptr, uint32_t* tail_applied = nullptr) {
+// the three backward entry points.  `update`: s3d_grid_encode_backward_adam[_tail], which hand in the optimizer state `adam` for
+// the fused update and learn through *applied whether it ran (and through *tail_applied which parts of a.tail rode)
+int grid_backward(GridBwd a, bool update, const s3d_grid_adam* adam = nullptr, int* applied = nullptr, uint32_t* tail_applied = nullptr) {
+    GridAdam ga;
+    if (update) {
+        S3D_REQUIRE(adam && applied, "grid_encode_backward_adam: null pointer");
+        S3D_REQUIRE(adam->param && adam->exp_avg && adam->exp_avg_sq && adam->step, "grid_encode_backward_adam: null optimizer state");
+        *applied = 0;
+        ga.p = adam->param; ga.m = adam->exp_avg; ga.v = adam->exp_avg_sq; ga.ph = reinterpret_cast<__half*>(adam->param_half);
+        ga.lr = adam->lr; ga.beta1 = adam->beta1; ga.beta2 = adam->beta2; ga.eps = adam->eps;
+        ga.step = adam->step; ga.grad_scale = adam->grad_scale; ga.lr_scale = adam->lr_scale;
+        a.adam = &ga;
+        if (a.B == 0 && a.tail) {  // (nothing to scatter: the tail's launches still have to happen)
+            const int rc = tail_in_front(*a.tail, a.st);
+            if (rc != S3D_OK) return rc;
+        }
+    }
     // path: 0 = auto (binned from 8,192 points), 1 = direct global atomics, 2 = binned (partition + LDS accumulate)
-    S3D_REQUIRE(path >= 0 && path <= 2, "grid_encode_backward: path must be 0 (auto), 1 (atomics) or 2 (binned)");
-    S3D_REQUIRE(bound >= 0.0f && !(bound != 0.0f && dy_dx), "grid_encode_backward: bound must be >= 0 and 0 with an input Jacobian");
-    if (B == 0) return S3D_OK;
-    S3D_REQUIRE(grad && inputs && offsets && grad_embeddings, "grid_encode_backward: null pointer");
-    S3D_REQUIRE(L >= 1 && L <= kMaxLevels, "grid_encode_backward: L must be in [1, %u]", kMaxLevels);
-    S3D_REQUIRE(dtype == S3D_F32 || dtype == S3D_F16, "grid_encode_backward: dtype must be f32 or f16");
-    if (path >= 2) {
-        const BinLayout lay = bin_layout(B, D, C, L, max_level_rows, dtype == S3D_F16 ? 2u : 4u);
-        S3D_REQUIRE(lay.ok && workspace && workspace_bytes >= lay.total,
+    S3D_REQUIRE(a.force_path >= 0 && a.force_path <= 2, "grid_encode_backward: path must be 0 (auto), 1 (atomics) or 2 (binned)");
+    S3D_REQUIRE(a.bound >= 0.0f && !(a.bound != 0.0f && a.dy_dx), "grid_encode_backward: bound must be >= 0 and 0 with an input Jacobian");
+    if (a.B == 0) return S3D_OK;
+    S3D_REQUIRE(a.grad && a.inputs && a.offsets && a.grad_emb, "grid_encode_backward: null pointer");
+    S3D_REQUIRE(a.L >= 1 && a.L <= kMaxLevels, "grid_encode_backward: L must be in [1, %u]", kMaxLevels);
+    S3D_REQUIRE(a.dtype == S3D_F32 || a.dtype == S3D_F16, "grid_encode_backward: dtype must be f32 or f16");
+    if (a.force_path >= 2) {
+        const BinLayout lay = bin_layout(a.B, a.D, a.C, a.L, a.max_level_rows, a.dtype == S3D_F16 ? 2u : 4u);
+        S3D_REQUIRE(lay.ok && a.ws && a.ws_bytes >= lay.total,
                     "grid_encode_backward: the binned path needs max_level_rows and a workspace of "
                     "s3d_grid_encode_backward_workspace_size() bytes");
     }
-    GridBwd a{grad, dy_dx, grad_embeddings, grad_inputs, inputs, offsets, B, C, L, max_level_rows, gridtype, interp, align_corners != 0,
-              LevelScales{}, (unsigned char*)workspace, (unsigned char*)control, workspace_bytes, control_bytes, path, as_stream(stream),
-              found_inf, adam, tail};
-    host_scales(L, S, H, a.sc, bound, n_valid);
+    host_scales(a.L, a.S, a.H, a.sc, a.bound, a.n_valid);
     GridBwdResult res{false, false, 0u};
-    const int rc = [&]() -> int { S3D_DISPATCH_TD(dtype, D, launch_backward, a, res) }();
-    if (applied) *applied = res.applied;
+    const int rc = [&]() -> int { S3D_DISPATCH_TD(a.dtype, a.D, launch_backward, a, res) }();
+    if (applied) *applied = res.applied ? 1 : 0;
     if (tail_applied) *tail_applied = res.tail;
-    if (rc != S3D_OK || !found_inf || res.reported) return rc;
-    if (dtype == S3D_F32)
-        hipLaunchKernelGGL(k_table_nonfinite<float>, dim3(kMaxStreamBlocks), dim3(256), 0, a.st, (const float*)grad_embeddings, offsets, L, C, found_inf);
+    if (rc != S3D_OK || !a.found_inf || res.reported) return rc;
+    if (a.dtype == S3D_F32)
+        hipLaunchKernelGGL(k_table_nonfinite<float>, dim3(kMaxStreamBlocks), dim3(256), 0, a.st, (const float*)a.grad_emb, a.offsets, a.L, a.C, a.found_inf);
     else
-        hipLaunchKernelGGL(k_table_nonfinite<__half>, dim3(kMaxStreamBlocks), dim3(256), 0, a.st, (const __half*)grad_embeddings, offsets, L, C, found_inf);
+        hipLaunchKernelGGL(k_table_nonfinite<__half>, dim3(kMaxStreamBlocks), dim3(256), 0, a.st, (const __half*)a.grad_emb, a.offsets, a.L, a.C, a.found_inf);
     return check_launch("grid_encode_backward (gradient check)");
 }
 }  // namespace
@@ -2592,36 +2592,10 @@ S3D_EXPORT int s3d_grid_encode_backward(const void* grad, const float* inputs, c
                                         float bound, const int32_t* n_valid, int path, float* found_inf,
                                         void* control, size_t control_bytes, s3d_stream_t stream) {
     (void)embeddings;
-    return grid_backward(grad, inputs, offsets, grad_embeddings, max_level_rows, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype,
-                         align_corners, interp, dtype, workspace, workspace_bytes, bound, n_valid, path, found_inf, control,
-                         control_bytes, stream, nullptr, nullptr);
+    return grid_backward({grad, inputs, offsets, grad_embeddings, max_level_rows, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype,
+                          align_corners != 0, interp, dtype, (unsigned char*)workspace, workspace_bytes, bound, n_valid, path, found_inf,
+                          (unsigned char*)control, control_bytes, as_stream(stream), nullptr}, false);
 }
-
-namespace {
-int grid_backward_adam(const void* grad, const float* inputs, const int32_t* offsets, void* grad_embeddings, uint32_t max_level_rows,
-                       uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype, int align_corners,
-                       uint32_t interp, int dtype, void* workspace, size_t workspace_bytes, float bound, const int32_t* n_valid,
-                       float* found_inf, void* control, size_t control_bytes, const s3d_grid_adam* adam, int* applied,
-                       const s3d_step_tail* tail, uint32_t* tail_applied, s3d_stream_t stream) {
-    S3D_REQUIRE(adam && applied, "grid_encode_backward_adam: null pointer");
-    S3D_REQUIRE(adam->param && adam->exp_avg && adam->exp_avg_sq && adam->step, "grid_encode_backward_adam: null optimizer state");
-    *applied = 0;
-    GridAdam ga;
-    ga.p = adam->param; ga.m = adam->exp_avg; ga.v = adam->exp_avg_sq; ga.ph = reinterpret_cast<__half*>(adam->param_half);
-    ga.lr = adam->lr; ga.beta1 = adam->beta1; ga.beta2 = adam->beta2; ga.eps = adam->eps;
-    ga.step = adam->step; ga.grad_scale = adam->grad_scale; ga.lr_scale = adam->lr_scale;
-    bool ran = false;
-    if (B == 0 && tail) {  // (nothing to scatter: the tail's launches still have to happen)
-        const int rc = tail_in_front(*tail, as_stream(stream));
-        if (rc != S3D_OK) return rc;
-    }
-    const int rc = grid_backward(grad, inputs, offsets, grad_embeddings, max_level_rows, B, D, C, L, S, H, nullptr, nullptr, gridtype,
-                                 align_corners, interp, dtype, workspace, workspace_bytes, bound, n_valid, 0, found_inf, control,
-                                 control_bytes, stream, &ga, &ran, tail, tail_applied);
-    *applied = ran ? 1 : 0;
-    return rc;
-}
-}  // namespace
 
 S3D_EXPORT int s3d_grid_encode_backward_adam_tail(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
                                                   void* grad_embeddings, uint32_t max_level_rows, uint32_t B, uint32_t D, uint32_t C,
@@ -2632,9 +2606,9 @@ S3D_EXPORT int s3d_grid_encode_backward_adam_tail(const void* grad, const float*
     (void)embeddings;
     S3D_REQUIRE(tail && tail_applied, "grid_encode_backward_adam_tail: null pointer");
     *tail_applied = 0;
-    return grid_backward_adam(grad, inputs, offsets, grad_embeddings, max_level_rows, B, D, C, L, S, H, gridtype, align_corners, interp,
-                              dtype, workspace, workspace_bytes, bound, n_valid, found_inf, control, control_bytes, adam, applied, tail,
-                              tail_applied, stream);
+    return grid_backward({grad, inputs, offsets, grad_embeddings, max_level_rows, B, D, C, L, S, H, nullptr, nullptr, gridtype,
+                          align_corners != 0, interp, dtype, (unsigned char*)workspace, workspace_bytes, bound, n_valid, 0, found_inf,
+                          (unsigned char*)control, control_bytes, as_stream(stream), tail}, true, adam, applied, tail_applied);
 }
 
 S3D_EXPORT int s3d_grid_encode_backward_adam(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
@@ -2644,9 +2618,9 @@ S3D_EXPORT int s3d_grid_encode_backward_adam(const void* grad, const float* inpu
                                              void* control, size_t control_bytes, const s3d_grid_adam* adam, int* applied,
                                              s3d_stream_t stream) {
     (void)embeddings;
-    return grid_backward_adam(grad, inputs, offsets, grad_embeddings, max_level_rows, B, D, C, L, S, H, gridtype, align_corners, interp,
-                              dtype, workspace, workspace_bytes, bound, n_valid, found_inf, control, control_bytes, adam, applied, nullptr,
-                              nullptr, stream);
+    return grid_backward({grad, inputs, offsets, grad_embeddings, max_level_rows, B, D, C, L, S, H, nullptr, nullptr, gridtype,
+                          align_corners != 0, interp, dtype, (unsigned char*)workspace, workspace_bytes, bound, n_valid, 0, found_inf,
+                          (unsigned char*)control, control_bytes, as_stream(stream), nullptr}, true, adam, applied);
 }
 
 S3D_EXPORT int s3d_grad_total_variation(const float* inputs, const float* embeddings, float* grad,

@@ -1862,25 +1862,38 @@ S3D_EXPORT int s3d_composite_rays_train_backward(const float* grad_weights_sum, 
     return check_launch("composite_rays_train_backward");
 }
 
+namespace {
+// s3d_composite_rays_train_loss (`bg_rgb`, a constant background) and s3d_composite_rays_train_loss_bg (`bg`, one per ray, and its
+// optional gradient `grad_bg`): exactly one of the two backgrounds is given; `name`: the entry point, for the messages
+int composite_train_loss(const char* name, const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
+                         uint32_t N, float T_thresh, const float* gt, const float* bg_rgb, const float* bg, const float* grad_loss,
+                         const float* gt_depth, float depth_weight, float* weights_sum, float* depth, float* image, float* grad_sigmas,
+                         float* grad_rgbs, float* grad_image, float* grad_weights_sum, float* grad_bg, float* loss, float* workspace,
+                         s3d_stream_t stream) {
+    if (N == 0) return S3D_OK;
+    S3D_REQUIRE(rays && weights_sum && depth && image && gt && (bg_rgb || bg) && grad_loss && workspace, "%s: null pointer", name);
+    S3D_REQUIRE(M == 0 || (sigmas && rgbs && deltas && grad_sigmas && grad_rgbs), "%s: null sample buffer", name);
+    S3D_REQUIRE((grad_image == nullptr) == (grad_weights_sum == nullptr), "%s: grad_image and grad_weights_sum come together", name);
+    hipLaunchKernelGGL(k_composite_train_loss_wave, dim3(div_up<uint32_t>(N, 4)), dim3(256), 0, as_stream(stream), sigmas, rgbs, deltas,
+                       rays, M, N, T_thresh, gt, bg ? 0.0f : bg_rgb[0], bg ? 0.0f : bg_rgb[1], bg ? 0.0f : bg_rgb[2], grad_loss, gt_depth,
+                       depth_weight, weights_sum, depth, image, grad_sigmas, grad_rgbs, grad_image, grad_weights_sum, workspace, bg,
+                       grad_bg);
+    if (loss)  // (NULL: the caller sums the terms later — s3d_loss_terms_reduce, or a step tail of the grid backward)
+        hipLaunchKernelGGL(k_bg_mse_reduce, dim3(1), dim3(1024), 0, as_stream(stream), (const float*)workspace,
+                           gt_depth ? (const float*)(workspace + (size_t)3 * N) : nullptr, N, depth_weight, loss);
+    return check_launch(name);
+}
+}  // namespace
+
 S3D_EXPORT int s3d_composite_rays_train_loss(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
                                              uint32_t M, uint32_t N, float T_thresh, const float* gt, const float* bg_rgb,
                                              const float* grad_loss, const float* gt_depth, float depth_weight,
                                              float* weights_sum, float* depth, float* image, float* grad_sigmas, float* grad_rgbs,
                                              float* grad_image, float* grad_weights_sum, float* loss, float* workspace,
                                              s3d_stream_t stream) {
-    if (N == 0) return S3D_OK;
-    S3D_REQUIRE(rays && weights_sum && depth && image && gt && bg_rgb && grad_loss && workspace,
-                "composite_rays_train_loss: null pointer");
-    S3D_REQUIRE(M == 0 || (sigmas && rgbs && deltas && grad_sigmas && grad_rgbs), "composite_rays_train_loss: null sample buffer");
-    S3D_REQUIRE((grad_image == nullptr) == (grad_weights_sum == nullptr), "composite_rays_train_loss: grad_image and grad_weights_sum "
-                "come together");
-    hipLaunchKernelGGL(k_composite_train_loss_wave, dim3(div_up<uint32_t>(N, 4)), dim3(256), 0, as_stream(stream), sigmas, rgbs, deltas,
-                       rays, M, N, T_thresh, gt, bg_rgb[0], bg_rgb[1], bg_rgb[2], grad_loss, gt_depth, depth_weight, weights_sum, depth,
-                       image, grad_sigmas, grad_rgbs, grad_image, grad_weights_sum, workspace);
-    if (loss)  // (NULL: the caller sums the terms later — s3d_loss_terms_reduce, or a step tail of the grid backward)
-        hipLaunchKernelGGL(k_bg_mse_reduce, dim3(1), dim3(1024), 0, as_stream(stream), (const float*)workspace,
-                           gt_depth ? (const float*)(workspace + (size_t)3 * N) : nullptr, N, depth_weight, loss);
-    return check_launch("composite_rays_train_loss");
+    return composite_train_loss("composite_rays_train_loss", sigmas, rgbs, deltas, rays, M, N, T_thresh, gt, bg_rgb, nullptr, grad_loss,
+                                gt_depth, depth_weight, weights_sum, depth, image, grad_sigmas, grad_rgbs, grad_image, grad_weights_sum,
+                                nullptr, loss, workspace, stream);
 }
 
 S3D_EXPORT int s3d_composite_rays_train_loss_bg(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
@@ -1889,19 +1902,9 @@ S3D_EXPORT int s3d_composite_rays_train_loss_bg(const float* sigmas, const float
                                                 float* weights_sum, float* depth, float* image, float* grad_sigmas, float* grad_rgbs,
                                                 float* grad_image, float* grad_weights_sum, float* grad_bg, float* loss, float* workspace,
                                                 s3d_stream_t stream) {
-    if (N == 0) return S3D_OK;
-    S3D_REQUIRE(rays && weights_sum && depth && image && gt && bg && grad_loss && workspace,
-                "composite_rays_train_loss_bg: null pointer");
-    S3D_REQUIRE(M == 0 || (sigmas && rgbs && deltas && grad_sigmas && grad_rgbs), "composite_rays_train_loss_bg: null sample buffer");
-    S3D_REQUIRE((grad_image == nullptr) == (grad_weights_sum == nullptr), "composite_rays_train_loss_bg: grad_image and "
-                "grad_weights_sum come together");
-    hipLaunchKernelGGL(k_composite_train_loss_wave, dim3(div_up<uint32_t>(N, 4)), dim3(256), 0, as_stream(stream), sigmas, rgbs, deltas,
-                       rays, M, N, T_thresh, gt, 0.0f, 0.0f, 0.0f, grad_loss, gt_depth, depth_weight, weights_sum, depth,
-                       image, grad_sigmas, grad_rgbs, grad_image, grad_weights_sum, workspace, bg, grad_bg);
-    if (loss)  // (NULL: the caller sums the terms later — s3d_loss_terms_reduce, or a step tail of the grid backward)
-        hipLaunchKernelGGL(k_bg_mse_reduce, dim3(1), dim3(1024), 0, as_stream(stream), (const float*)workspace,
-                           gt_depth ? (const float*)(workspace + (size_t)3 * N) : nullptr, N, depth_weight, loss);
-    return check_launch("composite_rays_train_loss_bg");
+    return composite_train_loss("composite_rays_train_loss_bg", sigmas, rgbs, deltas, rays, M, N, T_thresh, gt, nullptr, bg, grad_loss,
+                                gt_depth, depth_weight, weights_sum, depth, image, grad_sigmas, grad_rgbs, grad_image, grad_weights_sum,
+                                grad_bg, loss, workspace, stream);
 }
 
 S3D_EXPORT int s3d_loss_terms_reduce(const float* workspace, uint32_t N, int with_depth, float depth_weight, float* loss,

@@ -77,34 +77,20 @@ class _GridEncode(Function):
         S = float(np.log2(per_level_scale))
         H = base_resolution
 
-        param = embeddings
-        if torch.is_autocast_enabled("cuda") and C % 2 == 0:
-            half = getattr(param, "_s3d_half", None)  # fp16 copy maintained by nerf.optim.NativeAdam
-            if half is not None and param._s3d_half_version == param._version:
-                embeddings = half
-            else:
-                embeddings = _half_table(embeddings, cache_half)
-        embeddings = embeddings.contiguous()
+        param, embeddings = embeddings, _table_for_kernels(embeddings, cache_half)
 
         outputs = torch.empty(L, B, C, device=inputs.device, dtype=embeddings.dtype)  # level-major
         dy_dx = (torch.empty(B, L * D * C, device=inputs.device, dtype=embeddings.dtype)
                  if calc_grad_inputs else None)
-        # (keywords only when used: a backend without the fused normalisation / padded batches is never asked for them)
-        extra = {}
-        if bound:
-            extra["bound"] = bound
-        if n_valid is not None:
-            extra["n_valid"] = n_valid  # device sample count of a padded batch: rows beyond it are not produced
-        fwd_extra = dict(extra)
-        if live is not None and not torch.is_grad_enabled():
-            fwd_extra["live"] = live  # inference: rows marked dead are written as zeros without reading the table
+        extra, fwd_extra = _kernel_keywords(bound, n_valid, live)
         _backend.grid_encode_forward(inputs, embeddings, offsets, outputs, B, D, C, L, S, H, dy_dx, gridtype,
                                      align_corners, interpolation, **fwd_extra)
         if not level_major:  # (a fused consumer reads the kernel's own [L, B, C] layout in place: ffmlp input_layout=1)
             outputs = outputs.permute(1, 0, 2).reshape(B, L * C)
 
         ctx.save_for_backward(inputs, embeddings, offsets, dy_dx)
-        ctx.meta = (B, D, C, L, S, H, gridtype, interpolation, align_corners, level_major, bound)
+        ctx.geometry = (B, D, C, L, S, H, gridtype, align_corners, interpolation)
+        ctx.level_major = level_major
         ctx.param = param
         ctx.extra = extra
         return outputs
@@ -113,67 +99,91 @@ class _GridEncode(Function):
     @custom_bwd(device_type="cuda")
     def backward(ctx, grad):
         inputs, embeddings, offsets, dy_dx = ctx.saved_tensors
-        B, D, C, L, S, H, gridtype, interpolation, align_corners, level_major, bound = ctx.meta
-        if level_major:
+        B, _, C, L = ctx.geometry[:4]
+        if ctx.level_major:
             grad = grad.contiguous()  # already [L, B, C]
         else:
             grad = grad.view(B, L, C).permute(1, 0, 2).contiguous()  # [L, B, C]
-        # fp16 hand-over (nerf.optim.NativeAdam): the table gradient is ACCUMULATED into the optimizer's fp16 buffer and
-        # not returned to autograd, which would cast it to fp32 and add it into `.grad` (220 MB of traffic per step)
-        stash = getattr(ctx.param, "_s3d_grad", None)
-        if stash is not None and stash.dtype == embeddings.dtype and stash.shape == embeddings.shape:
-            grad_embeddings = stash
-            was_touched = getattr(ctx.param, "_s3d_grad_touched", False)
-            ctx.param._s3d_grad_touched = True
-            found_inf = getattr(ctx.param, "_s3d_found_inf", None)  # GradScaler's check made by the writing kernel
-        else:
-            stash = None
-            grad_embeddings = torch.zeros_like(embeddings)
-        grad_inputs = torch.zeros_like(inputs, dtype=embeddings.dtype) if dy_dx is not None else None
-        extra = ctx.extra
-        if stash is not None and found_inf is not None:
-            extra = dict(extra, found_inf=found_inf)
-        # the optimizer armed this table for THIS backward pass (nerf/optim.py: NativeAdam.arm_fused_tables): the accumulate
-        # kernel applies the update itself and no gradient is written
-        armed = ctx.param.__dict__.pop("_s3d_fused_arm", None) if stash is not None else None
-        # ... and, with a step tail attached to the arm (s3d_hip.StepTail), the step's small closing launches as well
-        tail = armed.pop("tail", None) if armed is not None else None
-        if tail is not None and not (dy_dx is None and hasattr(_backend, "grid_encode_backward_adam_tail")):
-            tail.flush()
-            tail = None
-        if armed is not None and dy_dx is None and hasattr(_backend, "grid_encode_backward_adam"):
-            if tail is not None:
-                done, parts = _backend.grid_encode_backward_adam_tail(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S,
-                                                                      H, gridtype, align_corners, interpolation, armed, tail.take(),
-                                                                      **extra)
-                tail.done(parts)
-            else:
-                done = _backend.grid_encode_backward_adam(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, gridtype,
-                                                          align_corners, interpolation, armed, **extra)
-            if done:
-                ctx.param._s3d_grad_touched = was_touched  # (nothing was written into the hand-over buffer)
-                ctx.param._s3d_fused_done = True
-            return None, None, None, None, None, None, None, None, None, None, None, None, None, None
-        _backend.grid_encode_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx,
-                                      grad_inputs, gridtype, align_corners, interpolation, **extra)
+        grad_inputs, grad_embeddings = _table_backward(ctx.param, embeddings, grad, inputs, offsets, ctx.geometry, ctx.extra,
+                                                       dy_dx=dy_dx, tail_may_ride=True)
         if grad_inputs is not None:
             grad_inputs = grad_inputs.to(inputs.dtype)
-        return grad_inputs, (None if stash is not None else grad_embeddings), None, None, None, None, None, None, None, None, None, None, None, None
+        return grad_inputs, grad_embeddings, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 grid_encode = _GridEncode.apply
 
 
 def _table_for_kernels(param, cache_half):
-    """(table the kernels read, Parameter): the optimizer's fp16 copy, a cached cast, or the parameter itself (_GridEncode.forward)"""
+    """the table the kernels read for `param`: the optimizer's fp16 copy, a cached cast, or the parameter itself"""
     emb = param
     if torch.is_autocast_enabled("cuda") and param.shape[1] % 2 == 0:
-        half = getattr(param, "_s3d_half", None)
+        half = getattr(param, "_s3d_half", None)  # fp16 copy maintained by nerf.optim.NativeAdam
         if half is not None and param._s3d_half_version == param._version:
             emb = half
         else:
             emb = _half_table(param, cache_half)
     return emb.contiguous()
+
+
+def _kernel_keywords(bound, n_valid, live):
+    """(keywords of the backward calls, keywords of the forward call) — only those in use: a backend without the fused
+    normalisation / padded batches is never asked for them"""
+    extra = {}
+    if bound:
+        extra["bound"] = bound
+    if n_valid is not None:
+        extra["n_valid"] = n_valid  # device sample count of a padded batch: rows beyond it are not produced
+    fwd_extra = dict(extra)
+    if live is not None and not torch.is_grad_enabled():
+        fwd_extra["live"] = live  # inference: rows marked dead are written as zeros without reading the table
+    return extra, fwd_extra
+
+
+def _table_backward(param, table, grad, inputs, offsets, geometry, extra, dy_dx=None, may_fuse=True, tail_may_ride=False):
+    """One table's backward with the optimizer's hand-over, for both Functions.  `param`: the Parameter, `table`: what the kernels
+    read for it, `grad`: level-major [L, B, C], `dy_dx`: the input Jacobian or None.  `may_fuse`: an armed update may run inside
+    this backward; `tail_may_ride`: and a step tail attached to the arm with it.  Returns (grad_inputs in the table's dtype or None,
+    what autograd gets for the table)."""
+    B, D, C, L, S, H, gridtype, align_corners, interpolation = geometry
+    # fp16 hand-over (nerf.optim.NativeAdam): the table gradient is ACCUMULATED into the optimizer's fp16 buffer and
+    # not returned to autograd, which would cast it to fp32 and add it into `.grad` (220 MB of traffic per step)
+    stash = getattr(param, "_s3d_grad", None)
+    if stash is not None and stash.dtype == table.dtype and stash.shape == table.shape:
+        grad_embeddings = stash
+        was_touched = getattr(param, "_s3d_grad_touched", False)
+        param._s3d_grad_touched = True
+        found_inf = getattr(param, "_s3d_found_inf", None)  # GradScaler's check made by the writing kernel
+        if found_inf is not None:
+            extra = dict(extra, found_inf=found_inf)
+    else:
+        stash = None
+        grad_embeddings = torch.zeros_like(table)
+    # the optimizer armed this table for THIS backward pass (nerf/optim.py: NativeAdam.arm_fused_tables): the accumulate
+    # kernel applies the update itself and no gradient is written
+    armed = param.__dict__.pop("_s3d_fused_arm", None) if stash is not None else None
+    # ... and, with a step tail attached to the arm (s3d_hip.StepTail), the step's small closing launches as well.  (Where no
+    # tail may ride, one attached to the arm stays there: the trainer's close() flushes it.)
+    tail = armed.pop("tail", None) if (armed is not None and tail_may_ride) else None
+    if tail is not None and not (dy_dx is None and hasattr(_backend, "grid_encode_backward_adam_tail")):
+        tail.flush()
+        tail = None
+    if armed is not None and may_fuse and dy_dx is None and hasattr(_backend, "grid_encode_backward_adam"):
+        if tail is not None:
+            done, parts = _backend.grid_encode_backward_adam_tail(grad, inputs, table, offsets, grad_embeddings, B, D, C, L, S, H,
+                                                                  gridtype, align_corners, interpolation, armed, tail.take(), **extra)
+            tail.done(parts)
+        else:
+            done = _backend.grid_encode_backward_adam(grad, inputs, table, offsets, grad_embeddings, B, D, C, L, S, H, gridtype,
+                                                      align_corners, interpolation, armed, **extra)
+        if done:
+            param._s3d_grad_touched = was_touched  # (nothing was written into the hand-over buffer)
+            param._s3d_fused_done = True
+        return None, None
+    grad_inputs = torch.zeros_like(inputs, dtype=table.dtype) if dy_dx is not None else None
+    _backend.grid_encode_backward(grad, inputs, table, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype,
+                                  align_corners, interpolation, **extra)
+    return grad_inputs, (None if stash is not None else grad_embeddings)
 
 
 class _GridEncodePair(Function):
@@ -195,18 +205,11 @@ class _GridEncodePair(Function):
         ta, tb = _table_for_kernels(pa, cache_half), _table_for_kernels(pb, cache_half)
         out_a = torch.empty(L, B, C, device=inputs.device, dtype=ta.dtype)
         out_b = torch.empty(L, B, C, device=inputs.device, dtype=ta.dtype)
-        extra = {}
-        if bound:
-            extra["bound"] = bound
-        if n_valid is not None:
-            extra["n_valid"] = n_valid
-        fwd_extra = dict(extra)
-        if live is not None and not torch.is_grad_enabled():
-            fwd_extra["live"] = live
+        extra, fwd_extra = _kernel_keywords(bound, n_valid, live)
         _backend.grid_encode_forward_pair(inputs, ta, tb, offsets, out_a, out_b, B, D, C, L, S, H, gridtype, align_corners,
                                           interpolation, **fwd_extra)
         ctx.save_for_backward(inputs, ta, tb, offsets)
-        ctx.meta = (B, D, C, L, S, H, gridtype, interpolation, align_corners)
+        ctx.geometry = (B, D, C, L, S, H, gridtype, align_corners, interpolation)
         ctx.params = (pa, pb)
         ctx.extra = extra
         ctx.set_materialize_grads(False)
@@ -216,40 +219,15 @@ class _GridEncodePair(Function):
     @custom_bwd(device_type="cuda")
     def backward(ctx, ga, gb):
         inputs, ta, tb, offsets = ctx.saved_tensors
-        B, D, C, L, S, H, gridtype, interpolation, align_corners = ctx.meta
         outs = []
         for k, (grad, table, param) in enumerate(((ga, ta, ctx.params[0]), (gb, tb, ctx.params[1]))):
             if grad is None or not ctx.needs_input_grad[1 + k]:  # (a frozen table of the pair: no scatter, no hand-over mark)
                 outs.append(None)
                 continue
-            grad = grad.contiguous()
-            stash = getattr(param, "_s3d_grad", None)
-            extra = ctx.extra
-            if stash is not None and stash.dtype == table.dtype and stash.shape == table.shape:
-                grad_embeddings = stash
-                param._s3d_fused_prev_touched = getattr(param, "_s3d_grad_touched", False)
-                param._s3d_grad_touched = True
-                found_inf = getattr(param, "_s3d_found_inf", None)
-                if found_inf is not None:
-                    extra = dict(extra, found_inf=found_inf)
-            else:
-                stash = None
-                grad_embeddings = torch.zeros_like(table)
             # in-backward update (nerf/optim.py: arm_fused_tables) for the LAST table of the pair only: its kernel takes the step's
             # skip decision when every poison word of the pair is known — the first table's scatter has run by then, but not
             # vice versa — so the first table keeps the separate update
-            armed = param.__dict__.pop("_s3d_fused_arm", None) if stash is not None else None
-            if armed is not None and k == 1 and hasattr(_backend, "grid_encode_backward_adam"):
-                was = getattr(param, "_s3d_fused_prev_touched", False)
-                if _backend.grid_encode_backward_adam(grad, inputs, table, offsets, grad_embeddings, B, D, C, L, S, H, gridtype,
-                                                      align_corners, interpolation, armed, **extra):
-                    param._s3d_grad_touched = was
-                    param._s3d_fused_done = True
-                outs.append(None)
-                continue
-            _backend.grid_encode_backward(grad, inputs, table, offsets, grad_embeddings, B, D, C, L, S, H, None, None, gridtype,
-                                          align_corners, interpolation, **extra)
-            outs.append(None if stash is not None else grad_embeddings)
+            outs.append(_table_backward(param, table, grad.contiguous(), inputs, offsets, ctx.geometry, ctx.extra, may_fuse=k == 1)[1])
         return (None, outs[0], outs[1]) + (None,) * 10
 
 

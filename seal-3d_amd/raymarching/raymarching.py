@@ -6,6 +6,8 @@ the native work goes to libseal3d_hip through `_backend`
 (s3d_hip.RaymarchingBackend).  Tests may swap `_backend` for the CPU oracle;
 the product path never does.
 """
+from types import SimpleNamespace
+
 import torch
 from torch.autograd import Function
 from torch.amp import custom_bwd, custom_fwd
@@ -243,6 +245,63 @@ class _CompositeRaysTrain(Function):
 composite_rays_train = _CompositeRaysTrain.apply
 
 
+def _loss_prologue(sigmas, rgbs, deltas, rays, gt, workspace, gt_depth, depth_weight, zero_grads):
+    """what both fused loss Functions prepare in front of their launch: the fp32 casts, the outputs, the gradient buffers, the
+    workspace, and the step tail that takes the sum of the terms (`kwargs`: the launch's keyword arguments)"""
+    p = SimpleNamespace(sigmas=sigmas.float().contiguous(), rgbs=rgbs.float().contiguous(), deltas=deltas.contiguous(),
+                        gt=gt.float().contiguous().view(-1, 3))
+    p.M, p.N = M, N = p.sigmas.shape[0], rays.shape[0]
+    dev = p.sigmas.device
+    p.weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
+    p.depth = torch.empty(N, dtype=torch.float32, device=dev)
+    p.image = torch.empty(N, 3, dtype=torch.float32, device=dev)
+    p.loss = torch.empty((), dtype=torch.float32, device=dev)
+    # zero_grads=False: as for composite_rays_train — the kernel zeroes the rows a count-bounded consumer still reads itself
+    flat = (torch.zeros if zero_grads else torch.empty)(4 * M, dtype=torch.float32, device=dev)
+    p.grad_sigmas, p.grad_rgbs = flat[:M], flat[M:].view(M, 3)
+    p.workspace = torch.empty(4 * N, dtype=torch.float32, device=dev) if workspace is None else workspace
+    p.gt_depth = None if gt_depth is None else gt_depth.float().contiguous().view(-1)
+    p.depth_weight = float(depth_weight)
+    p.tail = _loss_tail()
+    p.kwargs = dict(gt_depth=p.gt_depth, depth_weight=p.depth_weight, **({} if p.tail is None else {"defer_reduce": True}))
+    return p
+
+
+def _loss_filed(ctx, p, rays, T_thresh, expected_grad, grad_bg, *bg):
+    """after the launch: file the sum of the terms with the step tail, keep what backward() needs (`bg`: a per-ray background to
+    save), return the Function's outputs"""
+    if p.tail is not None:  # the sum of the terms rides in the hash table's backward (s3d_hip.StepTail)
+        p.tail.loss = (p.workspace, p.N, p.gt_depth is not None, p.depth_weight, p.loss)
+    ctx.pre = (p.grad_sigmas, p.grad_rgbs, grad_bg, expected_grad.data_ptr(), expected_grad._version)
+    ctx.save_for_backward(p.sigmas, p.rgbs, p.deltas, rays, p.weights_sum, p.image, p.gt, *bg)
+    ctx.dims = (p.M, p.N, T_thresh)
+    ctx.set_materialize_grads(False)
+    return p.loss, p.weights_sum, p.depth, p.image
+
+
+def _loss_backward(ctx, g_loss, g_ws, g_image, mse_backward):
+    """(grad_sigmas, grad_rgbs, grad_bg) of a fused loss Function: the forward launch's own for the announced upstream gradient,
+    else composite_rays_train's backward behind `mse_backward(image, weights_sum, gt, gi, gw[, bg]) -> (gi, gw, gb)`, the
+    criterion's gradient for `g_loss` (zeros when there is none)"""
+    if g_loss is None and g_ws is None and g_image is None:
+        return None, None, None
+    if (g_ws is None and g_image is None and g_loss is not None and g_loss.dtype == torch.float32
+            and g_loss.data_ptr() == ctx.pre[3] and g_loss._version == ctx.pre[4]):
+        return ctx.pre[:3]  # (the announced upstream gradient: already computed)
+    sigmas, rgbs, deltas, rays, weights_sum, image, gt, *bg = ctx.saved_tensors
+    M, N, T_thresh = ctx.dims
+    gi, gw, gb = mse_backward(image, weights_sum, gt, torch.zeros_like(image), torch.zeros_like(weights_sum), *bg)
+    if g_image is not None:
+        gi = gi + g_image
+    if g_ws is not None:
+        gw = gw + g_ws
+    flat = torch.zeros(4 * M, dtype=torch.float32, device=sigmas.device)
+    grad_sigmas, grad_rgbs = flat[:M], flat[M:].view(M, 3)
+    _backend.composite_rays_train_backward(gw.contiguous(), gi.contiguous(), sigmas, rgbs, deltas, rays, weights_sum, image, M, N,
+                                           T_thresh, grad_sigmas, grad_rgbs)
+    return grad_sigmas, grad_rgbs, gb
+
+
 class _CompositeRaysTrainLoss(Function):
     """Build extension (HIP backend): composite_rays_train, the background + MSE criterion of the training step
     (nerf/renderer.py:316 `image + (1 - weights_sum) * bg_color`, nerf/utils.py:484-489) and composite_rays_train's backward for
@@ -255,56 +314,21 @@ class _CompositeRaysTrainLoss(Function):
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, sigmas, rgbs, deltas, rays, T_thresh, gt, bg, expected_grad, workspace=None, gt_depth=None, depth_weight=1.0,
                 zero_grads=True):
-        sigmas, rgbs, deltas = sigmas.float().contiguous(), rgbs.float().contiguous(), deltas.contiguous()
-        gt = gt.float().contiguous().view(-1, 3)
-        M, N = sigmas.shape[0], rays.shape[0]
-        dev = sigmas.device
-        weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
-        depth = torch.empty(N, dtype=torch.float32, device=dev)
-        image = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        # zero_grads=False: as for composite_rays_train — the kernel zeroes the rows a count-bounded consumer still reads itself
-        flat = (torch.zeros if zero_grads else torch.empty)(4 * M, dtype=torch.float32, device=dev)
-        grad_sigmas, grad_rgbs = flat[:M], flat[M:].view(M, 3)
-        if workspace is None:
-            workspace = torch.empty(4 * N, dtype=torch.float32, device=dev)
-        if gt_depth is not None:
-            gt_depth = gt_depth.float().contiguous().view(-1)
-        tail = _loss_tail()
-        _backend.composite_rays_train_loss(sigmas, rgbs, deltas, rays, M, N, T_thresh, gt, bg, expected_grad, weights_sum, depth,
-                                           image, grad_sigmas, grad_rgbs, loss, workspace, gt_depth=gt_depth,
-                                           depth_weight=float(depth_weight), **({} if tail is None else {"defer_reduce": True}))
-        if tail is not None:  # the sum of the terms rides in the hash table's backward (s3d_hip.StepTail)
-            tail.loss = (workspace, N, gt_depth is not None, float(depth_weight), loss)
-        ctx.pre = (grad_sigmas, grad_rgbs, expected_grad.data_ptr(), expected_grad._version)
-        ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, image, gt)
-        ctx.dims = (M, N, T_thresh, bg)
-        ctx.set_materialize_grads(False)
-        return loss, weights_sum, depth, image
+        p = _loss_prologue(sigmas, rgbs, deltas, rays, gt, workspace, gt_depth, depth_weight, zero_grads)
+        _backend.composite_rays_train_loss(p.sigmas, p.rgbs, p.deltas, rays, p.M, p.N, T_thresh, p.gt, bg, expected_grad, p.weights_sum,
+                                           p.depth, p.image, p.grad_sigmas, p.grad_rgbs, p.loss, p.workspace, **p.kwargs)
+        ctx.bg = bg
+        return _loss_filed(ctx, p, rays, T_thresh, expected_grad, None)
 
     @staticmethod
     @custom_bwd(device_type="cuda")
     def backward(ctx, g_loss, g_ws, g_depth, g_image):
-        none = (None,) * 10
-        if g_loss is None and g_ws is None and g_image is None:
-            return (None, None) + none
-        if (g_ws is None and g_image is None and g_loss is not None and g_loss.dtype == torch.float32
-                and g_loss.data_ptr() == ctx.pre[2] and g_loss._version == ctx.pre[3]):
-            return (ctx.pre[0], ctx.pre[1]) + none  # (the announced upstream gradient: already computed)
-        sigmas, rgbs, deltas, rays, weights_sum, image, gt = ctx.saved_tensors
-        M, N, T_thresh, bg = ctx.dims
-        gi, gw = torch.zeros_like(image), torch.zeros_like(weights_sum)
-        if g_loss is not None:
-            _head().bg_mse_backward(image, weights_sum, gt, bg, g_loss.float().contiguous(), gi, gw)
-        if g_image is not None:
-            gi = gi + g_image
-        if g_ws is not None:
-            gw = gw + g_ws
-        flat = torch.zeros(4 * M, dtype=torch.float32, device=sigmas.device)
-        grad_sigmas, grad_rgbs = flat[:M], flat[M:].view(M, 3)
-        _backend.composite_rays_train_backward(gw.contiguous(), gi.contiguous(), sigmas, rgbs, deltas, rays, weights_sum, image, M, N,
-                                               T_thresh, grad_sigmas, grad_rgbs)
-        return (grad_sigmas, grad_rgbs) + none
+        def mse_backward(image, weights_sum, gt, gi, gw):
+            if g_loss is not None:
+                _head().bg_mse_backward(image, weights_sum, gt, ctx.bg, g_loss.float().contiguous(), gi, gw)
+            return gi, gw, None
+        grad_sigmas, grad_rgbs, _ = _loss_backward(ctx, g_loss, g_ws, g_image, mse_backward)
+        return (grad_sigmas, grad_rgbs) + (None,) * 10
 
 
 class _CompositeRaysTrainLossBg(Function):
@@ -317,59 +341,25 @@ class _CompositeRaysTrainLossBg(Function):
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, sigmas, rgbs, deltas, rays, T_thresh, gt, bg, expected_grad, workspace=None, gt_depth=None, depth_weight=1.0,
                 zero_grads=True):
-        sigmas, rgbs, deltas = sigmas.float().contiguous(), rgbs.float().contiguous(), deltas.contiguous()
-        gt = gt.float().contiguous().view(-1, 3)
+        p = _loss_prologue(sigmas, rgbs, deltas, rays, gt, workspace, gt_depth, depth_weight, zero_grads)
         bg = bg.float().contiguous().view(-1, 3)
-        M, N = sigmas.shape[0], rays.shape[0]
-        dev = sigmas.device
-        weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
-        depth = torch.empty(N, dtype=torch.float32, device=dev)
-        image = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        flat = (torch.zeros if zero_grads else torch.empty)(4 * M, dtype=torch.float32, device=dev)
-        grad_sigmas, grad_rgbs = flat[:M], flat[M:].view(M, 3)
-        grad_bg = torch.empty(N, 3, dtype=torch.float32, device=dev) if ctx.needs_input_grad[6] else None
-        if workspace is None:
-            workspace = torch.empty(4 * N, dtype=torch.float32, device=dev)
-        if gt_depth is not None:
-            gt_depth = gt_depth.float().contiguous().view(-1)
-        tail = _loss_tail()
-        _backend.composite_rays_train_loss_bg(sigmas, rgbs, deltas, rays, M, N, T_thresh, gt, bg, expected_grad, weights_sum, depth,
-                                              image, grad_sigmas, grad_rgbs, grad_bg, loss, workspace, gt_depth=gt_depth,
-                                              depth_weight=float(depth_weight), **({} if tail is None else {"defer_reduce": True}))
-        if tail is not None:
-            tail.loss = (workspace, N, gt_depth is not None, float(depth_weight), loss)
-        ctx.pre = (grad_sigmas, grad_rgbs, grad_bg, expected_grad.data_ptr(), expected_grad._version)
-        ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, image, gt, bg)
-        ctx.dims = (M, N, T_thresh)
-        ctx.set_materialize_grads(False)
-        return loss, weights_sum, depth, image
+        grad_bg = torch.empty(p.N, 3, dtype=torch.float32, device=p.sigmas.device) if ctx.needs_input_grad[6] else None
+        _backend.composite_rays_train_loss_bg(p.sigmas, p.rgbs, p.deltas, rays, p.M, p.N, T_thresh, p.gt, bg, expected_grad, p.weights_sum,
+                                              p.depth, p.image, p.grad_sigmas, p.grad_rgbs, grad_bg, p.loss, p.workspace, **p.kwargs)
+        return _loss_filed(ctx, p, rays, T_thresh, expected_grad, grad_bg, bg)
 
     @staticmethod
     @custom_bwd(device_type="cuda")
     def backward(ctx, g_loss, g_ws, g_depth, g_image):
-        none = (None,) * 4
-        if g_loss is None and g_ws is None and g_image is None:
-            return (None,) * 12
-        if (g_ws is None and g_image is None and g_loss is not None and g_loss.dtype == torch.float32
-                and g_loss.data_ptr() == ctx.pre[3] and g_loss._version == ctx.pre[4]):
-            return (ctx.pre[0], ctx.pre[1]) + none + (ctx.pre[2],) + (None,) * 5  # (the announced upstream gradient)
-        sigmas, rgbs, deltas, rays, weights_sum, image, gt, bg = ctx.saved_tensors
-        M, N, T_thresh = ctx.dims
-        gi, gw, gb = torch.zeros_like(image), torch.zeros_like(weights_sum), torch.zeros_like(bg)
-        if g_loss is not None:  # (the MSE's gradient, as s3d_bg_mse_backward forms it, with a per-ray background)
-            w = (1 - weights_sum).unsqueeze(-1)
-            k = g_loss.float() * (2.0 / (3.0 * N)) * ((image + w * bg) - gt)
-            gi, gw, gb = k, -(k * bg).sum(-1), k * w
-        if g_image is not None:
-            gi = gi + g_image
-        if g_ws is not None:
-            gw = gw + g_ws
-        flat = torch.zeros(4 * M, dtype=torch.float32, device=sigmas.device)
-        grad_sigmas, grad_rgbs = flat[:M], flat[M:].view(M, 3)
-        _backend.composite_rays_train_backward(gw.contiguous(), gi.contiguous(), sigmas, rgbs, deltas, rays, weights_sum, image, M, N,
-                                               T_thresh, grad_sigmas, grad_rgbs)
-        return (grad_sigmas, grad_rgbs) + none + (gb,) + (None,) * 5
+        def mse_backward(image, weights_sum, gt, gi, gw, bg):
+            gb = torch.zeros_like(bg)
+            if g_loss is not None:  # (the MSE's gradient, as s3d_bg_mse_backward forms it, with a per-ray background)
+                w = (1 - weights_sum).unsqueeze(-1)
+                k = g_loss.float() * (2.0 / (3.0 * image.shape[0])) * ((image + w * bg) - gt)
+                gi, gw, gb = k, -(k * bg).sum(-1), k * w
+            return gi, gw, gb
+        grad_sigmas, grad_rgbs, grad_bg = _loss_backward(ctx, g_loss, g_ws, g_image, mse_backward)
+        return (grad_sigmas, grad_rgbs) + (None,) * 4 + (grad_bg,) + (None,) * 5
 
 
 def composite_rays_train_loss_bg(sigmas, rgbs, deltas, rays, T_thresh, gt, bg, expected_grad, workspace=None, gt_depth=None,

@@ -268,6 +268,50 @@ def _need(t, dtype, name):
         raise RuntimeError(f"{name} must be {dtype}, got {t.dtype}")
 
 
+# The four parts of a step's tail (StepTail), each validated in one place: its stand-alone entry point passes the result on as C
+# arguments, GridBackend.grid_encode_backward_adam_tail files it in the s3d_step_tail.  `who`: the caller, for the messages.
+
+def _reduce_job_args(job, who):
+    """one job of FFMLPBackend.wgrad_reduce_pair: (workspace, B, input_dim, hidden_dim, num_layers, grad_weights, accumulate, found_inf)"""
+    ws, B, input_dim, hidden_dim, num_layers, grad_weights, accumulate, found_inf = job
+    _need(grad_weights, torch.float16, f"{who}: grad_weights")
+    return (_p(ws), _u(B), _u(input_dim), _u(hidden_dim), _u(num_layers), _p(grad_weights), C.c_int(int(bool(accumulate))),
+            _p(found_inf))
+
+
+def _loss_terms_args(workspace, N, with_depth, depth_weight, loss, who):
+    """the arguments of RaymarchingBackend.loss_terms_reduce"""
+    _need(workspace, torch.float32, f"{who}: workspace"); _need(loss, torch.float32, f"{who}: loss")
+    if workspace.numel() < 4 * N:
+        raise RuntimeError(f"{who}: the loss workspace holds 4N floats")
+    return _p(workspace), _u(N), C.c_int(int(bool(with_depth))), _f(depth_weight), _p(loss)
+
+
+def _scaler_update_args(scale, growth_tracker, found_inf, growth_factor, backoff_factor, growth_interval, adam_step, who):
+    """the arguments of OptimBackend.scaler_update"""
+    _need(scale, torch.float32, f"{who}: scale"); _need(growth_tracker, torch.int32, f"{who}: growth_tracker")
+    if adam_step is not None:
+        _need(adam_step, torch.float32, f"{who}: adam_step")
+    return (_p(scale), _p(growth_tracker), _p(found_inf), _f(growth_factor), _f(backoff_factor), C.c_int32(int(growth_interval)),
+            _p(adam_step))
+
+
+def _ring_push_args(loss, counter, loss_ring, counter_ring, cursor, who):
+    """the arguments of OptimBackend.step_ring_push, with the rings' sizes (ring, loss_slots) behind them"""
+    _need(counter, torch.int32, f"{who}: counter"); _need(counter_ring, torch.int32, f"{who}: counter_ring")
+    _need(cursor, torch.int32, f"{who}: cursor")
+    if cursor.numel() < 2:
+        raise RuntimeError(f"{who}: cursor is int32[2] = {{slot, running step number}}")
+    if loss is not None:
+        _need(loss, torch.float32, f"{who}: loss"); _need(loss_ring, torch.float32, f"{who}: loss_ring")
+    ring = counter_ring.shape[0]
+    if not counter_ring.is_contiguous() or counter_ring.numel() != 2 * ring or (loss is not None and loss_ring.numel() < 1):
+        raise RuntimeError(f"{who}: rings must be contiguous [ring, 2] / [loss_slots]")
+    slots = 0 if loss is None or loss_ring.numel() == ring else loss_ring.numel()
+    return (_p(loss), _p(counter), _p(loss_ring if loss is not None else None), _p(counter_ring), _p(cursor), C.c_int32(ring),
+            C.c_int32(slots))
+
+
 def _background_workspace(size_fn, N, device, found_inf):
     """both background backward bindings: found_inf's dtype check, the workspace query -> (uint8 workspace on `device`, its c_size_t size)"""
     if found_inf is not None:
@@ -556,10 +600,7 @@ class RaymarchingBackend:
     @staticmethod
     def loss_terms_reduce(workspace, N, with_depth, depth_weight, loss):
         """the one-workgroup sum a composite_rays_train_loss(defer_reduce=True) call left out (seal3d_hip.h)"""
-        _need(workspace, torch.float32, "workspace"); _need(loss, torch.float32, "loss")
-        if workspace.numel() < 4 * N:
-            raise RuntimeError("loss_terms_reduce: workspace holds 4N floats")
-        _check(lib().s3d_loss_terms_reduce(_p(workspace), _u(N), C.c_int(int(bool(with_depth))), _f(depth_weight), _p(loss), _stream()),
+        _check(lib().s3d_loss_terms_reduce(*_loss_terms_args(workspace, N, with_depth, depth_weight, loss, "loss_terms_reduce"), _stream()),
                "loss_terms_reduce")
 
     @staticmethod
@@ -645,6 +686,21 @@ def _max_level_rows(offsets):
     return v
 
 
+# the runs of C arguments that s3d_grid_encode_backward, _adam and _adam_tail have in common (seal3d_hip.h), in their order
+def _bwd_tables(grad, inputs, embeddings, offsets, grad_embeddings, max_level_rows, B, D, Cc, L, S, H):
+    return (_p(grad), _p(inputs), _p(embeddings), _p(offsets), _p(grad_embeddings), _u(max_level_rows), _u(B), _u(D), _u(Cc), _u(L),
+            _f(S), _u(H))
+
+
+def _bwd_options(gridtype, align_corners, interp, grad, ws, bound, n_valid):
+    return (_u(gridtype), C.c_int(int(align_corners)), _u(interp), C.c_int(_dt(grad)), _p(ws), C.c_size_t(ws.numel()), _f(bound),
+            _nv(n_valid))
+
+
+def _bwd_flags(found_inf, ctl):
+    return _p(found_inf), _p(ctl), C.c_size_t(ctl.numel() if ctl is not None else 0)
+
+
 class GridBackend:
     """gridencoder/src/gridencoder.h:12-15"""
 
@@ -692,21 +748,27 @@ class GridBackend:
         return mlr, ws, ctl
 
     @staticmethod
-    def grid_encode_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, D, Cc, L, S, H, dy_dx,
-                             grad_inputs, gridtype, align_corners, interp, bound=0.0, n_valid=None, found_inf=None):
+    def _backward_call(grad, inputs, embeddings, offsets, grad_embeddings, B, D, Cc, L, found_inf, adam=None):
+        """what the three backward methods do in front of their library call: the argument check, with `adam` that of the
+        optimizer state -> (max_level_rows, workspace, control block or None, s3d_grid_adam or None)"""
         _need(inputs, torch.float32, "inputs")
         if found_inf is not None:
             _need(found_inf, torch.float32, "found_inf")
         if grad_embeddings.dtype != grad.dtype:
             raise RuntimeError("grad_embeddings must have the dtype of grad")
-        mlr, ws, ctl = GridBackend._backward_buffers(grad, offsets, B, D, Cc, L)
-        _check(lib().s3d_grid_encode_backward(_p(grad), _p(inputs), _p(embeddings), _p(offsets),
-                                              _p(grad_embeddings), _u(mlr), _u(B), _u(D),
-                                              _u(Cc), _u(L), _f(S), _u(H), _p(dy_dx), _p(grad_inputs), _u(gridtype),
-                                              C.c_int(int(align_corners)), _u(interp), C.c_int(_dt(grad)), _p(ws),
-                                              C.c_size_t(ws.numel()), _f(bound), _nv(n_valid),
-                                              C.c_int(GridBackend._backward_path), _p(found_inf), _p(ctl),
-                                              C.c_size_t(ctl.numel() if ctl is not None else 0), _stream()),
+        for k in ("param", "exp_avg", "exp_avg_sq") if adam is not None else ():
+            _need(adam[k], torch.float32, k)
+            if adam[k].shape != embeddings.shape or not adam[k].is_contiguous():
+                raise RuntimeError(f"adam[{k!r}] must be a contiguous fp32 tensor of the table's shape")
+        return GridBackend._backward_buffers(grad, offsets, B, D, Cc, L) + (GridBackend._grid_adam(adam) if adam is not None else None,)
+
+    @staticmethod
+    def grid_encode_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, D, Cc, L, S, H, dy_dx,
+                             grad_inputs, gridtype, align_corners, interp, bound=0.0, n_valid=None, found_inf=None):
+        mlr, ws, ctl, _ = GridBackend._backward_call(grad, inputs, embeddings, offsets, grad_embeddings, B, D, Cc, L, found_inf)
+        _check(lib().s3d_grid_encode_backward(*_bwd_tables(grad, inputs, embeddings, offsets, grad_embeddings, mlr, B, D, Cc, L, S, H),
+                                              _p(dy_dx), _p(grad_inputs), *_bwd_options(gridtype, align_corners, interp, grad, ws, bound, n_valid),
+                                              C.c_int(GridBackend._backward_path), *_bwd_flags(found_inf, ctl), _stream()),
                "grid_encode_backward")
 
     class _GridAdam(C.Structure):
@@ -732,23 +794,12 @@ class GridBackend:
         s3d_grid_encode_backward_adam).  `adam`: dict(param, exp_avg, exp_avg_sq, param_half, lr, betas, eps, step, grad_scale,
         lr_scale).  Returns True when the update was applied there, False when the plain backward ran (the gradient is in
         `grad_embeddings`)."""
-        _need(inputs, torch.float32, "inputs")
-        if found_inf is not None:
-            _need(found_inf, torch.float32, "found_inf")
-        if grad_embeddings.dtype != grad.dtype:
-            raise RuntimeError("grad_embeddings must have the dtype of grad")
-        for k in ("param", "exp_avg", "exp_avg_sq"):
-            _need(adam[k], torch.float32, k)
-            if adam[k].shape != embeddings.shape or not adam[k].is_contiguous():
-                raise RuntimeError(f"adam[{k!r}] must be a contiguous fp32 tensor of the table's shape")
-        mlr, ws, ctl = GridBackend._backward_buffers(grad, offsets, B, D, Cc, L)
-        ga = GridBackend._grid_adam(adam)
+        mlr, ws, ctl, ga = GridBackend._backward_call(grad, inputs, embeddings, offsets, grad_embeddings, B, D, Cc, L, found_inf, adam)
         applied = C.c_int(0)
-        _check(lib().s3d_grid_encode_backward_adam(_p(grad), _p(inputs), _p(embeddings), _p(offsets), _p(grad_embeddings), _u(mlr), _u(B),
-                                                   _u(D), _u(Cc), _u(L), _f(S), _u(H), _u(gridtype), C.c_int(int(align_corners)), _u(interp),
-                                                   C.c_int(_dt(grad)), _p(ws), C.c_size_t(ws.numel()), _f(bound), _nv(n_valid),
-                                                   _p(found_inf), _p(ctl), C.c_size_t(ctl.numel() if ctl is not None else 0),
-                                                   C.byref(ga), C.byref(applied), _stream()), "grid_encode_backward_adam")
+        _check(lib().s3d_grid_encode_backward_adam(*_bwd_tables(grad, inputs, embeddings, offsets, grad_embeddings, mlr, B, D, Cc, L, S, H),
+                                                   *_bwd_options(gridtype, align_corners, interp, grad, ws, bound, n_valid),
+                                                   *_bwd_flags(found_inf, ctl), C.byref(ga), C.byref(applied), _stream()),
+               "grid_encode_backward_adam")
         return bool(applied.value)
 
     class _StepTail(C.Structure):
@@ -764,6 +815,12 @@ class GridBackend:
             ("loss_ring", C.c_void_p), ("counter_ring", C.c_void_p), ("cursor", C.c_void_p), ("ring", C.c_int32),
             ("loss_slots", C.c_int32)]
 
+        def fill(self, names, c_args):
+            """file a part: the C arguments its stand-alone entry point would pass, under the fields' names (None: not a field)"""
+            for name, v in zip(names, c_args):
+                if name is not None:
+                    setattr(self, name, v.value)
+
     TAIL_WGRAD_REDUCE, TAIL_LOSS, TAIL_ADAM, TAIL_EPILOGUE = 1, 2, 4, 8
 
     @staticmethod
@@ -775,59 +832,26 @@ class GridBackend:
         growth_tracker, growth_factor, backoff_factor, growth_interval, adam_step[, loss, counter, loss_ring, counter_ring,
         cursor]) as for OptimBackend.scaler_update / step_epilogue.  Returns (applied, TAIL_* bits of the parts that ran inside
         the backward's launches); a call that falls back has issued reduce and loss as ordinary launches in front."""
-        _need(inputs, torch.float32, "inputs")
-        if found_inf is not None:
-            _need(found_inf, torch.float32, "found_inf")
-        if grad_embeddings.dtype != grad.dtype:
-            raise RuntimeError("grad_embeddings must have the dtype of grad")
-        for k in ("param", "exp_avg", "exp_avg_sq"):
-            _need(adam[k], torch.float32, k)
-            if adam[k].shape != embeddings.shape or not adam[k].is_contiguous():
-                raise RuntimeError(f"adam[{k!r}] must be a contiguous fp32 tensor of the table's shape")
-        mlr, ws, ctl = GridBackend._backward_buffers(grad, offsets, B, D, Cc, L)
-        ga = GridBackend._grid_adam(adam)
-        st = GridBackend._StepTail()
+        mlr, ws, ctl, ga = GridBackend._backward_call(grad, inputs, embeddings, offsets, grad_embeddings, B, D, Cc, L, found_inf, adam)
+        st, who = GridBackend._StepTail(), "step tail"
         if tail.get("reduce") is not None:
-            for x, (ws_x, B_x, in_x, hid_x, nl_x, gw_x, acc_x, fi_x) in zip("ab", tail["reduce"]):
-                _need(gw_x, torch.float16, "grad_weights")
-                for name, v in (("workspace_", _p(ws_x)), ("B_", int(B_x)), ("input_dim_", int(in_x)), ("hidden_dim_", int(hid_x)),
-                                ("num_layers_", int(nl_x)), ("grad_weights_", _p(gw_x)), ("accumulate_", int(bool(acc_x))),
-                                ("found_inf_", _p(fi_x))):
-                    setattr(st, name + x, v)
+            for x, job in zip("ab", tail["reduce"]):
+                st.fill([name for name, _ in GridBackend._StepTail._net(x)], _reduce_job_args(job, who))
         if tail.get("loss") is not None:
-            lws, lN, ldepth, lw, loss = tail["loss"]
-            _need(lws, torch.float32, "workspace"); _need(loss, torch.float32, "loss")
-            if lws.numel() < 4 * lN:
-                raise RuntimeError("step tail: the loss workspace holds 4N floats")
-            st.loss_workspace, st.loss_N, st.loss_with_depth, st.loss_depth_weight, st.loss = _p(lws), int(lN), int(bool(ldepth)), float(lw), _p(loss)
+            st.fill(("loss_workspace", "loss_N", "loss_with_depth", "loss_depth_weight", "loss"), _loss_terms_args(*tail["loss"], who))
         arr = OptimBackend._adam_tensors(tail.get("adam") or [])
         st.tensors, st.n_tensors = C.cast(arr, C.c_void_p), len(arr)
         if tail.get("epilogue") is not None:
-            ep = tail["epilogue"]
-            scale, tracker, growth, backoff, interval, adam_step = ep[:6]
-            _need(scale, torch.float32, "scale"); _need(tracker, torch.int32, "growth_tracker")
-            if adam_step is not None:
-                _need(adam_step, torch.float32, "adam_step")
-            st.scale, st.growth_tracker, st.growth_factor, st.backoff_factor = _p(scale), _p(tracker), float(growth), float(backoff)
-            st.growth_interval, st.adam_step = int(interval), _p(adam_step)
+            ep = tail["epilogue"]  # (no found_inf in the struct: the riders take the call's own)
+            st.fill(("scale", "growth_tracker", None, "growth_factor", "backoff_factor", "growth_interval", "adam_step"),
+                    _scaler_update_args(*ep[:2], None, *ep[2:6], who))
             if len(ep) > 6:
-                loss, counter, loss_ring, counter_ring, cursor = ep[6:11]
-                _need(counter, torch.int32, "counter"); _need(counter_ring, torch.int32, "counter_ring"); _need(cursor, torch.int32, "cursor")
-                if loss is not None:
-                    _need(loss, torch.float32, "loss"); _need(loss_ring, torch.float32, "loss_ring")
-                ring = counter_ring.shape[0]
-                if cursor.numel() < 2 or counter_ring.numel() != 2 * ring or (loss is not None and loss_ring.numel() < 1):
-                    raise RuntimeError("step tail: cursor is int32[2], rings are [ring, 2] / [loss_slots]")
-                st.ring_loss, st.counter, st.loss_ring = _p(loss), _p(counter), _p(loss_ring if loss is not None else None)
-                st.counter_ring, st.cursor, st.ring = _p(counter_ring), _p(cursor), int(ring)
-                st.loss_slots = 0 if loss is None or loss_ring.numel() == ring else loss_ring.numel()
+                st.fill(("ring_loss", "counter", "loss_ring", "counter_ring", "cursor", "ring", "loss_slots"), _ring_push_args(*ep[6:11], who))
         applied, parts = C.c_int(0), C.c_uint32(0)
-        _check(lib().s3d_grid_encode_backward_adam_tail(_p(grad), _p(inputs), _p(embeddings), _p(offsets), _p(grad_embeddings), _u(mlr),
-                                                        _u(B), _u(D), _u(Cc), _u(L), _f(S), _u(H), _u(gridtype),
-                                                        C.c_int(int(align_corners)), _u(interp), C.c_int(_dt(grad)), _p(ws),
-                                                        C.c_size_t(ws.numel()), _f(bound), _nv(n_valid), _p(found_inf), _p(ctl),
-                                                        C.c_size_t(ctl.numel() if ctl is not None else 0), C.byref(ga), C.byref(st),
-                                                        C.byref(applied), C.byref(parts), _stream()), "grid_encode_backward_adam_tail")
+        _check(lib().s3d_grid_encode_backward_adam_tail(*_bwd_tables(grad, inputs, embeddings, offsets, grad_embeddings, mlr, B, D, Cc, L, S, H),
+                                                        *_bwd_options(gridtype, align_corners, interp, grad, ws, bound, n_valid),
+                                                        *_bwd_flags(found_inf, ctl), C.byref(ga), C.byref(st), C.byref(applied),
+                                                        C.byref(parts), _stream()), "grid_encode_backward_adam_tail")
         return bool(applied.value), int(parts.value)
 
     _backward_path = 0  # `path` argument of s3d_grid_encode_backward (binding-side state for tests / experiments)
@@ -988,11 +1012,8 @@ class FFMLPBackend:
     @staticmethod
     def wgrad_reduce_pair(a, b):
         """finish two deferred backward calls: a, b = (workspace, B, input_dim, hidden_dim, num_layers, grad_weights, accumulate, found_inf)"""
-        (ws_a, B_a, in_a, hid_a, nl_a, gw_a, acc_a, fi_a), (ws_b, B_b, in_b, hid_b, nl_b, gw_b, acc_b, fi_b) = a, b
-        _need(gw_a, torch.float16, "grad_weights"); _need(gw_b, torch.float16, "grad_weights")
-        _check(lib().s3d_ffmlp_wgrad_reduce_pair(_p(ws_a), _u(B_a), _u(in_a), _u(hid_a), _u(nl_a), _p(gw_a), C.c_int(int(bool(acc_a))),
-                                                 _p(fi_a), _p(ws_b), _u(B_b), _u(in_b), _u(hid_b), _u(nl_b), _p(gw_b),
-                                                 C.c_int(int(bool(acc_b))), _p(fi_b), _stream()), "ffmlp_wgrad_reduce_pair")
+        _check(lib().s3d_ffmlp_wgrad_reduce_pair(*_reduce_job_args(a, "wgrad_reduce_pair"), *_reduce_job_args(b, "wgrad_reduce_pair"),
+                                                 _stream()), "ffmlp_wgrad_reduce_pair")
 
 
 def _mid_fwd_args(mid, B):
@@ -1092,11 +1113,8 @@ class OptimBackend:
 
     @staticmethod
     def scaler_update(scale, growth_tracker, found_inf, growth_factor, backoff_factor, growth_interval, adam_step=None):
-        _need(scale, torch.float32, "scale"); _need(growth_tracker, torch.int32, "growth_tracker")
-        if adam_step is not None:
-            _need(adam_step, torch.float32, "adam_step")
-        _check(lib().s3d_scaler_update(_p(scale), _p(growth_tracker), _p(found_inf), _f(growth_factor), _f(backoff_factor),
-                                       C.c_int32(int(growth_interval)), _p(adam_step), _stream()), "scaler_update")
+        _check(lib().s3d_scaler_update(*_scaler_update_args(scale, growth_tracker, found_inf, growth_factor, backoff_factor,
+                                                            growth_interval, adam_step, "scaler_update"), _stream()), "scaler_update")
 
     @staticmethod
     def adam_advance(step, found_inf):
@@ -1106,36 +1124,16 @@ class OptimBackend:
     def step_epilogue(scale, growth_tracker, found_inf, growth_factor, backoff_factor, growth_interval, adam_step, loss, counter,
                       loss_ring, counter_ring, cursor):
         """scaler_update + step_ring_push in one launch (seal3d_hip.h)"""
-        _need(scale, torch.float32, "scale"); _need(growth_tracker, torch.int32, "growth_tracker")
-        _need(counter, torch.int32, "counter"); _need(counter_ring, torch.int32, "counter_ring"); _need(cursor, torch.int32, "cursor")
-        if adam_step is not None:
-            _need(adam_step, torch.float32, "adam_step")
-        if loss is not None:
-            _need(loss, torch.float32, "loss"); _need(loss_ring, torch.float32, "loss_ring")
-        ring = counter_ring.shape[0]
-        if cursor.numel() < 2 or counter_ring.numel() != 2 * ring or (loss is not None and loss_ring.numel() < 1):
-            raise RuntimeError("step_epilogue: cursor is int32[2], rings are [ring, 2] / [loss_slots]")
-        slots = 0 if loss is None or loss_ring.numel() == ring else loss_ring.numel()
-        _check(lib().s3d_step_epilogue(_p(scale), _p(growth_tracker), _p(found_inf), _f(growth_factor), _f(backoff_factor),
-                                       C.c_int32(int(growth_interval)), _p(adam_step), _p(loss),
-                                       _p(counter), _p(loss_ring if loss is not None else None), _p(counter_ring), _p(cursor),
-                                       C.c_int32(ring), C.c_int32(slots), _stream()), "step_epilogue")
+        _check(lib().s3d_step_epilogue(*_scaler_update_args(scale, growth_tracker, found_inf, growth_factor, backoff_factor,
+                                                            growth_interval, adam_step, "step_epilogue"),
+                                       *_ring_push_args(loss, counter, loss_ring, counter_ring, cursor, "step_epilogue"), _stream()),
+               "step_epilogue")
 
     @staticmethod
     def step_ring_push(loss, counter, loss_ring, counter_ring, cursor):
         """file `loss` [] / `counter` [2] in slot *cursor of the rings, clear the counter, advance the cursor (seal3d_hip.h)"""
-        _need(counter, torch.int32, "counter"); _need(counter_ring, torch.int32, "counter_ring")
-        _need(cursor, torch.int32, "cursor")
-        if cursor.numel() < 2:
-            raise RuntimeError("step_ring_push: cursor is int32[2] = {slot, running step number}")
-        if loss is not None:
-            _need(loss, torch.float32, "loss"); _need(loss_ring, torch.float32, "loss_ring")
-        ring = counter_ring.shape[0]
-        if not counter_ring.is_contiguous() or counter_ring.numel() != 2 * ring or (loss is not None and loss_ring.numel() < 1):
-            raise RuntimeError("step_ring_push: rings must be contiguous [ring, 2] / [loss_slots]")
-        slots = 0 if loss is None or loss_ring.numel() == ring else loss_ring.numel()
-        _check(lib().s3d_step_ring_push(_p(loss), _p(counter), _p(loss_ring if loss is not None else None), _p(counter_ring),
-                                        _p(cursor), C.c_int32(ring), C.c_int32(slots), _stream()), "step_ring_push")
+        _check(lib().s3d_step_ring_push(*_ring_push_args(loss, counter, loss_ring, counter_ring, cursor, "step_ring_push"), _stream()),
+               "step_ring_push")
 
 
 class NgpHeadBackend:

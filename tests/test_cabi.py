@@ -66,7 +66,9 @@ def test_ctypes_call_sites_pass_as_many_arguments_as_the_header_declares():
         args = m.group(2).strip()
         declared[m.group(1)] = 0 if args in ("", "void") else args.count(",") + 1
     src = open(os.path.join(REPO, "seal-3d_amd", "s3d_hip", "__init__.py")).read()
-    starred_width = {"_live": 2, "_mid_fwd_args": 4, "_mid_bwd_args": 3, "_shadow2": 2, "_shadow1": 1}  # helpers that expand to several C arguments
+    starred_width = {"_live": 2, "_mid_fwd_args": 4, "_mid_bwd_args": 3, "_shadow2": 2, "_shadow1": 1,  # helpers that expand to several C arguments
+                     "_reduce_job_args": 8, "_loss_terms_args": 5, "_scaler_update_args": 7, "_ring_push_args": 7,
+                     "_bwd_tables": 12, "_bwd_options": 8, "_bwd_flags": 3}
     seen = set()
     for node in ast.walk(ast.parse(src)):
         if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr.startswith("s3d_") \

@@ -153,6 +153,60 @@ def test_tail_falls_back_below_the_binned_path(hip):
     assert float(s["step"]) == 3.0 and int(s["cursor"][1]) == 1030 and float(s["ge"].abs().max()) > 0
 
 
+def _malformed(what, s):
+    """(reduce pair, loss terms, scaler, ring) of `s` with ONE part malformed.  Wrong dtypes of at least the right byte size, or
+    views one element short of the right one: a launch that went unchecked would still stay inside the tensors' allocations."""
+    pair, loss, _, scaler, ring, _ = _pieces(s)
+    N = s["meta"][2]
+    if what == "fp32_grad_weights":
+        pair = (pair[0][:5] + (pair[0][5].float(),) + pair[0][6:], pair[1])
+    elif what == "fp16_loss_workspace":
+        loss = (loss[0].half(),) + loss[1:]
+    elif what == "short_loss_workspace":
+        loss = (loss[0][:4 * N - 1],) + loss[1:]
+    elif what == "int64_growth_tracker":
+        scaler = (scaler[0], scaler[1].long()) + scaler[2:]
+    elif what == "fp16_adam_step":
+        scaler = scaler[:5] + (scaler[5].half(),)
+    elif what == "int64_cursor":
+        ring = ring[:4] + (ring[4].long(),)
+    elif what == "one_element_cursor":
+        ring = ring[:4] + (ring[4][:1],)
+    elif what == "counter_ring_16x3":
+        ring = ring[:3] + (torch.zeros(16, 3, dtype=torch.int32, device="cuda"), ring[4])
+    else:
+        raise AssertionError(what)
+    return pair, loss, scaler, ring
+
+
+@pytest.mark.parametrize("what", ["fp32_grad_weights", "fp16_loss_workspace", "short_loss_workspace", "int64_growth_tracker",
+                                  "fp16_adam_step", "int64_cursor", "one_element_cursor", "counter_ring_16x3"])
+def test_a_malformed_tail_part_is_refused_like_its_own_entry_point(hip, what):
+    """every part of a step tail is checked as its stand-alone entry point checks it: both refuse the same malformed part with a
+    RuntimeError, and the refused tail call has launched nothing — no gradient, no loss, no Adam, no scaler update, no ring push"""
+    G, O, F, R = hip.GridBackend, hip.OptimBackend, hip.FFMLPBackend, hip.RaymarchingBackend
+    offs, S = _encoder()
+    shape = (8192, 128, 1, True)
+    s = _state(*shape, "clean", int(offs[-1]))
+    adam = _pieces(s)[5]
+    pair, loss, scaler, ring = _malformed(what, s)
+    with pytest.raises(RuntimeError):
+        if what == "fp32_grad_weights":
+            F.wgrad_reduce_pair(*pair)
+        elif what in ("fp16_loss_workspace", "short_loss_workspace"):
+            R.loss_terms_reduce(*loss)
+        elif what in ("int64_growth_tracker", "fp16_adam_step"):
+            O.scaler_update(*scaler[:2], s["flag"], *scaler[2:])
+        else:
+            O.step_ring_push(*ring)
+    with pytest.raises(RuntimeError):
+        G.grid_encode_backward_adam_tail(s["grad"], s["x"], s["table"][3].clone(), offs, s["ge"], shape[0], 3, 2, L, S, BASE, 0, False, 0,
+                                         adam, dict(reduce=pair, loss=loss, epilogue=scaler + ring), found_inf=s["flag"])
+    torch.cuda.synchronize()
+    assert int(s["ge"].count_nonzero()) == 0 and float(s["loss"]) == -1.0
+    assert float(s["step"]) == 3.0 and float(s["scale"]) == 1024.0 and s["cursor"].tolist() == [4, 1030]
+
+
 class _Count:
     """call counters on the binding's entry points (class attributes: every module's `_backend` is the class itself)"""
     NAMES = [("FFMLPBackend", "wgrad_reduce_pair"), ("OptimBackend", "adam_step_multi"), ("OptimBackend", "step_epilogue"),
