@@ -37,6 +37,29 @@ class _ParamRef:
         self.param = param
 
 
+def _wgrad_target(ref, w):
+    """Where a backward writes the gradient of the weights `w` its forward was handed with `ref` (a _ParamRef, or None):
+    (grad_weights, the writing call's `accumulate` / `found_inf` keywords, what autograd gets for the weights).
+    fp16 hand-over (nerf.optim.NativeAdam): the reduce kernel writes the optimizer's fp16 buffer instead of returning the gradient
+    to autograd (fp32 cast + accumulate), and raises the attached GradScaler's flag itself.  A `ref` is made for adopted weights
+    only: a Parameter's record (s3d_hip.Handover) is ADDED to; a PackedWeights (nerf/network.py) has its region replaced by the
+    first backward of a step.  The target is marked written here, on the host, ahead of the launch that writes it."""
+    if ref is None:
+        grad_weights = torch.empty_like(w)  # every element is written
+        return grad_weights, {}, grad_weights
+    h = getattr(ref.param, "_s3d", None)
+    if h is not None:
+        stash, accumulate, found_inf = h.grad, True, h.found_inf
+        h.touched = True
+    else:
+        stash, accumulate, found_inf = ref.param.grad, not ref.param.overwrite, ref.param.found_inf
+        ref.param.mark_written()
+    extra = {"accumulate": accumulate}
+    if found_inf is not None:
+        extra["found_inf"] = found_inf
+    return stash.view(w.shape), extra, None
+
+
 class _FFMLPForward(Function):
     """ffmlp.py:15-83"""
 
@@ -118,27 +141,15 @@ class _FFMLPForward(Function):
         # build allocates them uninitialised (saves two B x hidden x num_layers memsets per MLP per step)
         grad_inputs = (torch.empty_like(inputs) if calc_grad_inputs
                        else torch.zeros(1, device=grad.device, dtype=inputs.dtype))
-        # fp16 hand-over (nerf.optim.NativeAdam): the reduce kernel ADDS the weight gradient to the optimizer's fp16 buffer
-        # instead of returning it to autograd (fp32 cast + accumulate)
-        stash = getattr(ctx.param_ref.param, "_s3d_grad", None) if ctx.param_ref is not None else None
-        grad_weights = stash.view(weights.shape) if stash is not None else torch.empty_like(weights)  # every element is written
+        grad_weights, handover, to_autograd = _wgrad_target(ctx.param_ref, weights)
         backward_buffer = None if fused else torch.empty(num_layers, B, hidden_dim, device=grad.device, dtype=grad.dtype)
-        extra = dict(ctx.extra)
+        extra = dict(ctx.extra, **handover)
         if rgb is not None:
             extra["grad_rgb"], extra["rgb_head"], grad = grad, rgb, None
-        if stash is not None:
-            # (a packed nn.Linear pack, nerf/network.py: PackedWeights, is OVERWRITTEN: one backward per step writes it)
-            extra["accumulate"] = not getattr(ctx.param_ref.param, "_s3d_overwrite", False)
-            found_inf = getattr(ctx.param_ref.param, "_s3d_found_inf", None)  # GradScaler's check made by the writing kernel
-            if found_inf is not None:
-                extra["found_inf"] = found_inf
         _backend.ffmlp_backward(grad, inputs, weights, forward_buffer, B, input_dim, output_dim, hidden_dim,
                                 num_layers, activation, output_activation, calc_grad_inputs, backward_buffer,
                                 grad_inputs, grad_weights, **extra)
-        if stash is not None:
-            ctx.param_ref.param._s3d_grad_touched = True
-            grad_weights = None
-        return ((grad_inputs if calc_grad_inputs else None), grad_weights) + (None,) * 13
+        return ((grad_inputs if calc_grad_inputs else None), to_autograd) + (None,) * 13
 
 
 ffmlp_forward = _FFMLPForward.apply
@@ -185,20 +196,11 @@ class _FFMLPNgpMid(Function):
         g_sigma = None if g_sigma is None else g_sigma.float().contiguous()
         calc = ctx.calc_grad_inputs
         grad_inputs = torch.empty_like(inputs) if calc else torch.zeros(1, device=h0.device, dtype=inputs.dtype)
-        stash = getattr(ctx.param_ref.param, "_s3d_grad", None) if ctx.param_ref is not None else None
-        grad_weights = stash.view(weights.shape) if stash is not None else torch.empty_like(weights)
-        extra = dict(ctx.extra)
-        if stash is not None:
-            extra["accumulate"] = True
-            found_inf = getattr(ctx.param_ref.param, "_s3d_found_inf", None)
-            if found_inf is not None:
-                extra["found_inf"] = found_inf
+        grad_weights, handover, to_autograd = _wgrad_target(ctx.param_ref, weights)
         _backend.ffmlp_backward(None, inputs, weights, None, B, input_dim, 16, hidden_dim, num_layers, activation,
-                                output_activation, calc, None, grad_inputs, grad_weights, mid=(g_sigma, g_cin, h0), **extra)
-        if stash is not None:
-            ctx.param_ref.param._s3d_grad_touched = True
-            grad_weights = None
-        return ((grad_inputs if calc else None), grad_weights) + (None,) * 7
+                                output_activation, calc, None, grad_inputs, grad_weights, mid=(g_sigma, g_cin, h0), **ctx.extra,
+                                **handover)
+        return ((grad_inputs if calc else None), to_autograd) + (None,) * 7
 
 
 class _FFMLPNgpPair(Function):
@@ -231,16 +233,6 @@ class _FFMLPNgpPair(Function):
         inputs, w_sigma, w_color, h0, cin, rgb = ctx.saved_tensors
         B = h0.shape[0]
         dev = h0.device
-
-        def target(ref, w):
-            stash = getattr(ref.param, "_s3d_grad", None) if ref is not None else None
-            extra = {}
-            if stash is not None:
-                extra["accumulate"] = not getattr(ref.param, "_s3d_overwrite", False)
-                found_inf = getattr(ref.param, "_s3d_found_inf", None)
-                if found_inf is not None:
-                    extra["found_inf"] = found_inf
-            return stash, (stash.view(w.shape) if stash is not None else torch.empty_like(w)), extra
         ref_s, ref_c = ctx.refs
         nv = {"n_valid": ctx.extra["n_valid"]} if "n_valid" in ctx.extra else {}
         # both calls leave their weight-gradient partial sums in their half of one scratch tensor: ONE reduce launch for the two
@@ -251,14 +243,14 @@ class _FFMLPNgpPair(Function):
         scratch = torch.empty(nb_c + nb_s, dtype=torch.uint8, device=dev)
         ws_c, ws_s = scratch[:nb_c], scratch[nb_c:]
         # colour network: gradient w.r.t. its fp32 head output -> gradient of the colour-net input rows
-        stash_c, gw_c, extra_c = target(ref_c, w_color)
+        gw_c, extra_c, auto_c = _wgrad_target(ref_c, w_color)
         g_cin = torch.empty_like(cin)
         if g_rgb is None:
             g_rgb = torch.zeros_like(rgb)
         _backend.ffmlp_backward(None, cin, w_color, None, B, in_c, 16, W_c, nl_c, act_c, oact_c, True, None, g_cin, gw_c,
                                 grad_rgb=g_rgb.float().contiguous(), rgb_head=rgb, workspace=ws_c, defer_reduce=True, **nv, **extra_c)
         # density network: the head's two gradients
-        stash_s, gw_s, extra_s = target(ref_s, w_sigma)
+        gw_s, extra_s, auto_s = _wgrad_target(ref_s, w_sigma)
         calc = ctx.calc_grad_inputs
         grad_inputs = torch.empty_like(inputs) if calc else torch.zeros(1, device=dev, dtype=inputs.dtype)
         g_sigma = None if g_sigma is None else g_sigma.float().contiguous()
@@ -271,14 +263,11 @@ class _FFMLPNgpPair(Function):
             # the reduce rides in the hash table's backward, which runs behind this node; the holder keeps `scratch` (ws_c / ws_s
             # are views of it) alive until that call has issued its launches
             tail.reduce = pair
-            if stash_s is not None and stash_c is not None:
+            if ref_s is not None and ref_c is not None:
                 tail.adam_params += [ref_s.param, ref_c.param]  # their update may ride as well (nerf/optim.py)
         else:
             _backend.wgrad_reduce_pair(*pair)
-        for stash, ref in ((stash_s, ref_s), (stash_c, ref_c)):
-            if stash is not None:
-                ref.param._s3d_grad_touched = True
-        return ((grad_inputs if calc else None), (None if stash_s is not None else gw_s), (None if stash_c is not None else gw_c)) + (None,) * 8
+        return ((grad_inputs if calc else None), auto_s, auto_c) + (None,) * 8
 
 
 def _cached_half(w):
@@ -353,22 +342,16 @@ class FFMLP(nn.Module):
         B = inputs.shape[1] if level_major else inputs.shape[0]
         if B % 128 != 0 or self.padded_output_dim != 16:
             raise RuntimeError("FFMLP.forward_ngp_mid: needs B % 128 == 0 and a 16-column output")
-        w, ref, hook = self.weights, None, None
-        if getattr(w, "_s3d_grad", None) is not None and getattr(w, "_s3d_half_version", None) == w._version:
-            if torch.is_grad_enabled() and w.requires_grad:
-                ref = _ParamRef(w)
-                hook = self._autograd_hook
-            w = w._s3d_half
-        elif not torch.is_grad_enabled() and w.is_cuda:
-            w = _cached_half(w)
+        w, ref, hook = self._train_weights()
         dims = (self.input_dim, self.hidden_dim, self.num_layers, self.activation, self.output_activation)
         return _FFMLPNgpMid.apply(inputs, w, dirs, dims, not self.training, ref, hook, 1 if level_major else 0, n_valid)
 
     def _inference_weights(self):
         """fp16 weights for a call that takes no gradient: the optimizer's copy while it is current, else one cast per version"""
-        w = self.weights
-        if getattr(w, "_s3d_grad", None) is not None and getattr(w, "_s3d_half_version", None) == w._version:
-            return w._s3d_half
+        w, h = self.weights, getattr(self.weights, "_s3d", None)
+        half = h.fresh_half(w) if h is not None else None
+        if half is not None:
+            return half
         return _cached_half(w) if w.is_cuda else w.half()
 
     def pair_supported(self, color_net):
@@ -380,13 +363,17 @@ class FFMLP(nn.Module):
                 and color_net.output_activation == 6)
 
     def _train_weights(self):
-        """(weights tensor for a call that records a gradient, _ParamRef for the fp16 hand-over, hook)"""
-        w = self.weights
-        if getattr(w, "_s3d_grad", None) is not None and getattr(w, "_s3d_half_version", None) == w._version:
-            if torch.is_grad_enabled() and w.requires_grad:
-                return w._s3d_half, _ParamRef(w), self._autograd_hook
-            return w._s3d_half, None, None
-        return w, None, None
+        """(weights tensor for a call that may record a gradient, _ParamRef for the fp16 hand-over, hook).  A native optimizer
+        maintains the fp16 copy of the weights and takes their gradient as an fp16 buffer; the copy carries no autograd history:
+        a 0-dim CPU leaf (never cast, never read) keeps the node in the graph when the inputs require no gradient either."""
+        w, h = self.weights, getattr(self.weights, "_s3d", None)
+        half = h.fresh_half(w) if h is not None else None
+        if half is None:
+            # (no-grad call without an optimizer's copy: one cast per weight version, not one per call)
+            return (_cached_half(w) if not torch.is_grad_enabled() and w.is_cuda else w), None, None
+        if torch.is_grad_enabled() and w.requires_grad:
+            return half, _ParamRef(w), self._autograd_hook
+        return half, None, None
 
     def forward_ngp_pair(self, inputs, dirs, color_net, level_major=False, n_valid=None):
         """density network + head + colour network + sigmoid in ONE launch (s3d_ffmlp_ngp_pair_inference): returns
@@ -448,17 +435,7 @@ class FFMLP(nn.Module):
         return out
 
     def _run(self, inputs, input_layout, n_valid=None, rgb_head=False):
-        w, ref, hook = self.weights, None, None
-        if getattr(w, "_s3d_grad", None) is not None and getattr(w, "_s3d_half_version", None) == w._version:
-            # a native optimizer maintains the fp16 copy of the weights and takes their gradient as an fp16 buffer
-            if torch.is_grad_enabled() and w.requires_grad:
-                ref = _ParamRef(w)
-                # the fp16 copy carries no autograd history: a 0-dim CPU leaf (never cast, never read) keeps the node
-                # in the graph when the inputs do not require a gradient either
-                hook = self._autograd_hook
-            w = w._s3d_half
-        elif not torch.is_grad_enabled() and w.is_cuda:
-            w = _cached_half(w)  # (inference without an optimizer: one cast per weight version, not one per call)
+        w, ref, hook = self._train_weights()
         out = ffmlp_forward(inputs, w, self.input_dim, self.padded_output_dim, self.hidden_dim,
                             self.num_layers, self.activation, self.output_activation, not self.training,
                             inputs.requires_grad, ref, hook, input_layout, n_valid, rgb_head)

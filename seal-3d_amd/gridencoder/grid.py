@@ -118,10 +118,9 @@ def _table_for_kernels(param, cache_half):
     """the table the kernels read for `param`: the optimizer's fp16 copy, a cached cast, or the parameter itself"""
     emb = param
     if torch.is_autocast_enabled("cuda") and param.shape[1] % 2 == 0:
-        half = getattr(param, "_s3d_half", None)  # fp16 copy maintained by nerf.optim.NativeAdam
-        if half is not None and param._s3d_half_version == param._version:
-            emb = half
-        else:
+        h = getattr(param, "_s3d", None)
+        emb = h.fresh_half(param) if h is not None else None  # fp16 copy maintained by nerf.optim.NativeAdam
+        if emb is None:
             emb = _half_table(param, cache_half)
     return emb.contiguous()
 
@@ -148,20 +147,20 @@ def _table_backward(param, table, grad, inputs, offsets, geometry, extra, dy_dx=
     B, D, C, L, S, H, gridtype, align_corners, interpolation = geometry
     # fp16 hand-over (nerf.optim.NativeAdam): the table gradient is ACCUMULATED into the optimizer's fp16 buffer and
     # not returned to autograd, which would cast it to fp32 and add it into `.grad` (220 MB of traffic per step)
-    stash = getattr(param, "_s3d_grad", None)
-    if stash is not None and stash.dtype == table.dtype and stash.shape == table.shape:
-        grad_embeddings = stash
-        was_touched = getattr(param, "_s3d_grad_touched", False)
-        param._s3d_grad_touched = True
-        found_inf = getattr(param, "_s3d_found_inf", None)  # GradScaler's check made by the writing kernel
-        if found_inf is not None:
-            extra = dict(extra, found_inf=found_inf)
+    h = getattr(param, "_s3d", None)
+    if h is not None and h.grad.dtype == table.dtype and h.grad.shape == table.shape:
+        grad_embeddings = h.grad
+        was_touched, h.touched = h.touched, True
+        if h.found_inf is not None:  # GradScaler's check made by the writing kernel
+            extra = dict(extra, found_inf=h.found_inf)
     else:
-        stash = None
+        h = None
         grad_embeddings = torch.zeros_like(table)
     # the optimizer armed this table for THIS backward pass (nerf/optim.py: NativeAdam.arm_fused_tables): the accumulate
     # kernel applies the update itself and no gradient is written
-    armed = param.__dict__.pop("_s3d_fused_arm", None) if stash is not None else None
+    armed = None
+    if h is not None:
+        armed, h.arm = h.arm, None
     # ... and, with a step tail attached to the arm (s3d_hip.StepTail), the step's small closing launches as well.  (Where no
     # tail may ride, one attached to the arm stays there: the trainer's close() flushes it.)
     tail = armed.pop("tail", None) if (armed is not None and tail_may_ride) else None
@@ -177,13 +176,13 @@ def _table_backward(param, table, grad, inputs, offsets, geometry, extra, dy_dx=
             done = _backend.grid_encode_backward_adam(grad, inputs, table, offsets, grad_embeddings, B, D, C, L, S, H, gridtype,
                                                       align_corners, interpolation, armed, **extra)
         if done:
-            param._s3d_grad_touched = was_touched  # (nothing was written into the hand-over buffer)
-            param._s3d_fused_done = True
+            h.touched = was_touched  # (nothing was written into the hand-over buffer)
+            h.fused_done = True
         return None, None
     grad_inputs = torch.zeros_like(inputs, dtype=table.dtype) if dy_dx is not None else None
     _backend.grid_encode_backward(grad, inputs, table, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype,
                                   align_corners, interpolation, **extra)
-    return grad_inputs, (None if stash is not None else grad_embeddings)
+    return grad_inputs, (None if h is not None else grad_embeddings)
 
 
 class _GridEncodePair(Function):
@@ -342,16 +341,16 @@ class GridEncoder(nn.Module):
         else:
             inputs = ((inputs + bound) / (2 * bound)).view(-1, self.input_dim)
             B = inputs.shape[0]
-        stash = getattr(self.embeddings, "_s3d_grad", None)
-        if stash is not None and getattr(self.embeddings, "_s3d_grad_touched", False):
+        h = getattr(self.embeddings, "_s3d", None)
+        if h is not None and h.touched:
             if grad_scale is None:
                 raise ValueError("grad_total_variation: this table's gradient is the optimizer's loss-scaled fp16 buffer "
                                  "(nerf.optim.NativeAdam); pass grad_scale=<the scaler's scale>")
             tv = torch.zeros_like(self.embeddings, dtype=torch.float32)
             _backend.grad_total_variation(inputs.contiguous(), self.embeddings.detach().float(), tv, self.offsets, weight, B, D, C, L,
                                           S, H, self.gridtype_id, self.align_corners)
-            stash.add_((tv * grad_scale).to(stash.dtype))
-            self.embeddings._s3d_unchecked = True  # written by a torch op: the scaler checks the buffer itself
+            h.grad.add_((tv * grad_scale).to(h.grad.dtype))
+            h.unchecked = True  # written by a torch op: the scaler checks the buffer itself
             return
         if self.embeddings.grad is None:
             raise ValueError("grad is None, should be called after loss.backward() and before optimizer.step()!")

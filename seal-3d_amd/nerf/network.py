@@ -10,7 +10,7 @@ import s3d_hip
 from activation import trunc_exp
 _ffb = s3d_hip.FFMLPBackend
 from encoding import get_encoder
-from ffmlp.ffmlp import _ParamRef, ffmlp_forward
+from ffmlp.ffmlp import _ParamRef, _wgrad_target, ffmlp_forward
 from gridencoder.grid import grid_encode_pair
 
 from .network_ff import _NgpRgb
@@ -80,40 +80,27 @@ class _SealPair(Function):
         e0, w_sigma, w_color, h0, cin, rgb = ctx.saved_tensors
         B, dev = h0.shape[0], h0.device
         nv = {"n_valid": ctx.n_valid} if ctx.n_valid is not None else {}
-
-        def target(ref, w):
-            stash = getattr(ref.param, "_s3d_grad", None) if ref is not None else None
-            acc, fi = False, None
-            if stash is not None:
-                acc = not getattr(ref.param, "_s3d_overwrite", False)
-                fi = getattr(ref.param, "_s3d_found_inf", None)
-            return stash, (stash.view(w.shape) if stash is not None else torch.empty_like(w)), acc, fi
         ref_s, ref_c = ctx.refs
         nb_c = (_ffb.backward_workspace_bytes(64, 16, 64, 2) + 255) // 256 * 256
         nb_s = _ffb.backward_workspace_bytes(32, 16, 64, 2)
         scratch = torch.empty(nb_c + nb_s, dtype=torch.uint8, device=dev)
         ws_c, ws_s = scratch[:nb_c], scratch[nb_c:]
-        stash_c, gw_c, acc_c, fi_c = target(ref_c, w_color)
+        gw_c, ex_c, auto_c = _wgrad_target(ref_c, w_color)
         g_cin = torch.empty_like(cin)
         if g_rgb is None:
             g_rgb = torch.zeros_like(rgb)
-        ex_c = {"found_inf": fi_c} if fi_c is not None else {}
         _ffb.ffmlp_backward(None, cin, w_color, None, B, 64, 16, 64, 2, 0, 6, True, None, g_cin, gw_c,
                             grad_rgb=g_rgb.float().contiguous(), rgb_head=rgb, workspace=ws_c, defer_reduce=True, **nv, **ex_c)
         g_h = torch.empty(B, 16, dtype=torch.half, device=dev)
         g_e1 = torch.empty(16, B, 2, dtype=torch.half, device=dev) if ctx.need[1] else None
         _head.mid2_backward(g_cin, None if g_sigma is None else g_sigma.float().contiguous(), h0, g_h, g_e1, ctx.n_valid)
-        stash_s, gw_s, acc_s, fi_s = target(ref_s, w_sigma)
+        gw_s, ex_s, auto_s = _wgrad_target(ref_s, w_sigma)
         g_e0 = torch.empty_like(e0) if ctx.need[0] else torch.zeros(1, device=dev, dtype=e0.dtype)
-        ex_s = {"found_inf": fi_s} if fi_s is not None else {}
         _ffb.ffmlp_backward(g_h, e0, w_sigma, None, B, 32, 16, 64, 2, 0, 6, ctx.need[0], None, g_e0, gw_s, input_layout=1,
                             workspace=ws_s, defer_reduce=True, **nv, **ex_s)
-        _ffb.wgrad_reduce_pair((ws_c, B, 64, 64, 2, gw_c, acc_c, fi_c), (ws_s, B, 32, 64, 2, gw_s, acc_s, fi_s))
-        for stash, ref in ((stash_s, ref_s), (stash_c, ref_c)):
-            if stash is not None:
-                ref.param._s3d_grad_touched = True
-        return ((g_e0 if ctx.need[0] else None), g_e1, (None if stash_s is not None else gw_s),
-                (None if stash_c is not None else gw_c)) + (None,) * 6
+        _ffb.wgrad_reduce_pair((ws_c, B, 64, 64, 2, gw_c, ex_c.get("accumulate", False), ex_c.get("found_inf")),
+                               (ws_s, B, 32, 64, 2, gw_s, ex_s.get("accumulate", False), ex_s.get("found_inf")))
+        return ((g_e0 if ctx.need[0] else None), g_e1, auto_s, auto_c) + (None,) * 6
 
 
 class _Background(Function):
@@ -141,15 +128,14 @@ class _Background(Function):
         sph, dirs, table, w0, w1, rgb = ctx.saved_tensors
         offsets, S, H = ctx.meta
         param = ctx.param
-        stash = getattr(param, "_s3d_grad", None)
+        h = getattr(param, "_s3d", None)
         found_inf = None
-        if stash is not None and stash.dtype == table.dtype and stash.shape == table.shape and ctx.needs_input_grad[2]:
-            grad_table = stash
-            param._s3d_grad_touched = True
-            found_inf = getattr(param, "_s3d_found_inf", None)
-            param.__dict__.pop("_s3d_fused_arm", None)  # (no in-backward Adam here: the optimizer's step updates this table)
+        if h is not None and h.grad.dtype == table.dtype and h.grad.shape == table.shape and ctx.needs_input_grad[2]:
+            grad_table, found_inf = h.grad, h.found_inf
+            h.touched = True
+            h.arm = None  # (no in-backward Adam here: the optimizer's step updates this table)
         else:
-            stash = None
+            h = None
             grad_table = torch.zeros_like(table) if ctx.needs_input_grad[2] else None  # (frozen table: no scatter)
         gw0 = torch.empty(64, 24, dtype=torch.float32, device=rgb.device)
         gw1 = torch.empty(3, 64, dtype=torch.float32, device=rgb.device)
@@ -158,7 +144,7 @@ class _Background(Function):
         if found_inf is not None:  # (the reduce launch checked the weight gradients against the scaler's flag)
             for w in (w0, w1):
                 w._s3d_grad_checked = found_inf
-        return (None, None, (grad_table if stash is None and ctx.needs_input_grad[2] else None),
+        return (None, None, (grad_table if h is None and ctx.needs_input_grad[2] else None),
                 gw0 if ctx.needs_input_grad[3] else None, gw1 if ctx.needs_input_grad[4] else None, None)
 
 
@@ -169,27 +155,26 @@ class PackedWeights:
     object holds their fp16 image `half` [numel]: member (parameter, offset, row stride) sits at rows `offset + r * stride`,
     constant blocks (an identity layer, zero padding) in between.  Two ways to keep it current:
       * adopted by nerf.optim.NativeAdam: the MLP backward writes the packed fp16 weight gradient into the pack's twin inside
-        the optimizer's flat gradient buffer (`_s3d_grad`, overwritten each call), and the Adam launch reads it through a
+        the optimizer's flat gradient buffer (`grad`, overwritten each call), and the Adam launch reads it through a
         row-strided view per member and writes the updated fp16 weights into `half` through the same view — the step never
         assembles (cat / pad / cast) or splits anything;
       * otherwise (teacher, evaluation, frozen MLPs): `refreshed()` re-copies the members when one of them has changed (tensor
         version or optimizer epoch), i.e. once per weight update instead of once per call."""
 
     @property
-    def _s3d_overwrite(self):
+    def overwrite(self):
         """What the MLP backward asks before it writes the gradient twin.  The twin is never cleared (Adam reads it through the
         member views only, constant blocks would pile up under blind accumulation): the FIRST backward of a step replaces it,
         any further backward before the step — the two `density()` calls of `NeRFRenderer.run`, gradient accumulation over
         several batches — adds to it.  "Of a step": since the last zero_grad() / consuming step(), the same host-side flags
         the optimizer's own clearing decision uses (nerf/optim.py: zero_grad, clear_unconsumed)."""
-        return not any(getattr(p, "_s3d_grad_touched", False) and not getattr(p, "_s3d_grad_consumed", False)
-                       for p, _, _ in self.members)
+        return not any(p._s3d.dirty for p, _, _ in self.members)
 
     def __init__(self, members, numel, constants=()):
         self.members, self.numel, self.constants = list(members), int(numel), list(constants)
         self.half = None
         self.adopted = False
-        self._s3d_grad = None
+        self.grad = None  # this pack's region of the optimizer's flat fp16 gradient buffer once adopted
         self._key = None
         self.hook = torch.zeros((), requires_grad=True)  # keeps the autograd node alive when only the pack needs a gradient
         for p, off, stride in self.members:
@@ -213,33 +198,25 @@ class PackedWeights:
     def adopt(self, grad_region, flat, flat_range):
         """nerf.optim.NativeAdam: `grad_region` = this pack's [numel] slice of the optimizer's flat fp16 gradient buffer"""
         self._ensure(grad_region.device)
-        self._s3d_grad = grad_region
+        self.grad = grad_region
         for p, off, stride in self.members:
             rows, cols = p.shape
-            p._s3d_grad = self._view(grad_region, p, off, stride)
-            p._s3d_half = self._view(self.half, p, off, stride)
-            p._s3d_half.copy_(p.detach())
-            p._s3d_half_version = p._version
-            p._s3d_grad_flat = flat
-            p._s3d_flat_range = (flat_range[0] + off, flat_range[0] + off + (rows - 1) * stride + cols)
-            p._s3d_grad_touched = False
-            p._s3d_grad_consumed = False
+            half = self._view(self.half, p, off, stride)
+            half.copy_(p.detach())
+            p._s3d = s3d_hip.Handover(grad=self._view(grad_region, p, off, stride), flat=flat, half=half, half_version=p._version,
+                                      flat_range=(flat_range[0] + off, flat_range[0] + off + (rows - 1) * stride + cols))
         self.adopted = True
 
-    # what the MLP backward reads / sets on the object it is handed as `param_ref.param` (ffmlp/ffmlp.py)
+    # what the MLP backward asks of the pack it is handed as `param_ref.param` (ffmlp/ffmlp.py: _wgrad_target), beside `grad`
+    # and `overwrite`
     @property
-    def _s3d_found_inf(self):
-        return getattr(self.members[0][0], "_s3d_found_inf", None)
+    def found_inf(self):
+        return self.members[0][0]._s3d.found_inf
 
-    @property
-    def _s3d_grad_touched(self):
-        return any(getattr(p, "_s3d_grad_touched", False) for p, _, _ in self.members)
-
-    @_s3d_grad_touched.setter
-    def _s3d_grad_touched(self, v):
+    def mark_written(self):
         for p, _, _ in self.members:
-            if p.requires_grad or not v:
-                p._s3d_grad_touched = v
+            if p.requires_grad:
+                p._s3d.touched = True
 
     def trainable(self):
         return any(p.requires_grad for p, _, _ in self.members)
@@ -248,7 +225,7 @@ class PackedWeights:
         """the pack as maintained by the optimizer, or None when a member was written from outside since (or never adopted)"""
         if not self.adopted or self.half is None or self.half.device != self.members[0][0].device:
             return None
-        if any(getattr(p, "_s3d_half_version", None) != p._version for p, _, _ in self.members):
+        if any(p._s3d.fresh_half(p) is None for p, _, _ in self.members):
             return None
         return self.half
 

@@ -5,12 +5,14 @@ The reference's step is `torch.optim.Adam(betas=(0.9, 0.99), eps=1e-15)` under `
 rule and the same loss-scale schedule, re-plumbed for a 12.2 M-row hash table whose gradient is fp16:
 
 * a `GridEncoder` whose parameter has been adopted by `NativeAdam` hands its table gradient over as the fp16 buffer
-  the backward kernel wrote (`param._s3d_grad`), instead of returning it to autograd (which would cast it to fp32,
+  the backward kernel wrote (`param._s3d.grad`), instead of returning it to autograd (which would cast it to fp32,
   73 MB, and accumulate it into `.grad`, 147 MB);
 * `NativeGradScaler.step` = one read of every gradient for the non-finite check, then `s3d_adam_step` per tensor —
-  unscale, Adam and the fp16 copy of the updated table for the next autocast forward (`param._s3d_half`) in one pass;
+  unscale, Adam and the fp16 copy of the updated table for the next autocast forward (`param._s3d.half`) in one pass;
   all of it skipped when a gradient is non-finite, exactly like `GradScaler.step`;
 * everything stays on the device (step count, scale, found_inf), so the step is HIP-graph capturable.
+
+`param._s3d` is the adoption's record (s3d_hip.Handover): a parameter is adopted exactly when it has one.
 
 Both classes exist only for GPU training with libseal3d_hip; the torch optimizer + GradScaler path of the trainers is
 unchanged and remains the reference behaviour (CPU tests, A/B runs).
@@ -69,19 +71,23 @@ class NativeAdam(torch.optim.Optimizer):
             self.flat_half._s3d_param_cuts = []  # parameter boundaries (elements): where a chunked all-reduce may cut
             for p, n in zip(adopted, sizes):
                 self.flat_half._s3d_param_cuts.append(off)
-                p._s3d_flat_range = (off, off + p.numel())
-                p._s3d_grad = self.flat_half[off:off + p.numel()].view(p.shape)
-                p._s3d_grad_flat = self.flat_half
-                p._s3d_grad_touched = False
-                p._s3d_grad_consumed = False
-                p._s3d_half = p.detach().to(torch.float16)
-                p._s3d_half_version = p._version
+                p._s3d = s3d_hip.Handover(grad=self.flat_half[off:off + p.numel()].view(p.shape), flat=self.flat_half,
+                                          flat_range=(off, off + p.numel()), half=p.detach().to(torch.float16),
+                                          half_version=p._version)
                 off += n
             for pk, n in zip(packs, psizes):
                 self.flat_half._s3d_param_cuts.append(off)
                 pk.adopt(self.flat_half[off:off + pk.numel], self.flat_half, (off, off + pk.numel))
                 off += n
         self.packs = packs
+
+    def _records(self):
+        """(param, its hand-over record) for every adopted parameter"""
+        for group in self.param_groups:
+            for p in group["params"]:
+                h = getattr(p, "_s3d", None)
+                if h is not None:
+                    yield p, h
 
     fuse_table_updates = True  # single replica: a hash table's update rides in its backward's accumulate kernel (arm_fused_tables)
 
@@ -99,43 +105,43 @@ class NativeAdam(torch.optim.Optimizer):
             lr_of = {id(g): lr for g, lr in zip(self.param_groups, self._lr_captured)}
         for group in self.param_groups:
             for p in group["params"]:
-                half = getattr(p, "_s3d_half", None)
-                if (getattr(p, "_s3d_grad", None) is None or getattr(p, "_s3d_pack_spec", None) is not None or not p.requires_grad
-                        or p.dim() != 2 or p.shape[1] != 2 or half is None or p._s3d_half_version != p._version
-                        or getattr(p, "_s3d_found_inf", None) is None or float(p.__dict__.get("_s3d_l1", 0.0)) != 0.0):
+                h = getattr(p, "_s3d", None)
+                half = h.fresh_half(p) if h is not None else None
+                if (half is None or getattr(p, "_s3d_pack_spec", None) is not None or not p.requires_grad or p.dim() != 2
+                        or p.shape[1] != 2 or h.found_inf is None or float(p.__dict__.get("_s3d_l1", 0.0)) != 0.0):
                     continue
                 st = self.state[p]
                 b1, b2 = group["betas"]
-                p._s3d_fused_arm = dict(param=p.data, exp_avg=st["exp_avg"], exp_avg_sq=st["exp_avg_sq"], param_half=half,
-                                        lr=lr_of.get(id(group), group["lr"]), betas=(b1, b2), eps=group["eps"], step=self.step_count,
-                                        grad_scale=grad_scale, lr_scale=self.lr_scale)
+                h.arm = dict(param=p.data, exp_avg=st["exp_avg"], exp_avg_sq=st["exp_avg_sq"], param_half=half,
+                             lr=lr_of.get(id(group), group["lr"]), betas=(b1, b2), eps=group["eps"], step=self.step_count,
+                             grad_scale=grad_scale, lr_scale=self.lr_scale)
                 n += 1
         return n
 
     def _tail_item(self, p, lr_of):
         """adam_step_multi's item for parameter p exactly as step() would form it on the one-launch route, or None when step()
         would do more than that launch for it (packed weights, a stale fp16 copy, an L1 term)"""
-        g = getattr(p, "_s3d_grad", None)
-        if g is None or getattr(p, "_s3d_pack_spec", None) is not None or not p.requires_grad:
+        h = getattr(p, "_s3d", None)
+        if h is None or getattr(p, "_s3d_pack_spec", None) is not None or not p.requires_grad:
             return None
-        half = getattr(p, "_s3d_half", None)
-        if hasattr(p, "_s3d_half") and (half is None or p._s3d_half_version != p._version or not half.is_contiguous()):
+        half = h.fresh_half(p)
+        if half is None or not half.is_contiguous():
             return None
         if float(p.__dict__.get("_s3d_l1", 0.0)) != 0.0:
             return None
         group = next(gr for gr in self.param_groups if any(q is p for q in gr["params"]))
         st = self.state[p]
         b1, b2 = group["betas"]
-        return (p.data, g, st["exp_avg"], st["exp_avg_sq"], half, lr_of.get(id(group), group["lr"]), b1, b2, group["eps"],
+        return (p.data, h.grad, st["exp_avg"], st["exp_avg_sq"], half, lr_of.get(id(group), group["lr"]), b1, b2, group["eps"],
                 self.consume_grads, 0.0)
 
     def arm_step_tail(self, tail, scaler=None, ring_push=None):
         """Called right after `arm_fused_tables` armed exactly ONE table: attach the step tail (s3d_hip.StepTail) to that arm.  The
         table's backward then also runs, inside its own launches, the weight-gradient reduce and the criterion's sum that were
         filed in the tail, the update of the parameters whose backward filed them there (`tail.adam_params`: `step()` skips them
-        through `_s3d_fused_done`) and — when no other parameter is left for `step()` — the scaler's update with `ring_push`.
+        through `fused_done`) and — when no other parameter is left for `step()` — the scaler's update with `ring_push`.
         Returns False (nothing attached) when this step's launches would not carry the arguments step() would use."""
-        armed = [p for g in self.param_groups for p in g["params"] if "_s3d_fused_arm" in p.__dict__]
+        armed = [p for p, h in self._records() if h.arm is not None]
         if len(armed) != 1:
             return False
         lr_of = {}
@@ -161,9 +167,9 @@ class NativeAdam(torch.optim.Optimizer):
         def applied(t, parts):
             if parts & s3d_hip.GridBackend.TAIL_ADAM:
                 for p in t.adam_params:
-                    p._s3d_fused_done = True
+                    p._s3d.fused_done = True
                     if self.consume_grads:
-                        p._s3d_grad_consumed = True
+                        p._s3d.consumed = True
             if parts & s3d_hip.GridBackend.TAIL_EPILOGUE:
                 scaler._tail_done = True
 
@@ -171,24 +177,23 @@ class NativeAdam(torch.optim.Optimizer):
         ep = scaler.tail_epilogue(self) if scaler is not None and hasattr(scaler, "tail_epilogue") else None
         if ep is not None:
             tail.epilogue = (covers, ep + (tuple(ring_push) if ring_push is not None else ()))
-        table._s3d_fused_arm["tail"] = tail
+        table._s3d.arm["tail"] = tail
         tail.armed = True
         return True
 
     def disarm_fused_tables(self):
-        for group in self.param_groups:
-            for p in group["params"]:
-                p.__dict__.pop("_s3d_fused_arm", None)
+        for _, h in self._records():
+            h.arm = None
 
     def grads(self):
         """(param, gradient tensor) for every parameter that has one: the fp16 hand-over buffer or `.grad`"""
         for group in self.param_groups:
             for p in group["params"]:
-                if getattr(p, "_s3d_fused_done", False):
+                h = getattr(p, "_s3d", None)
+                if h is not None and h.fused_done:
                     continue  # (updated inside its backward's accumulate kernel this step)
-                g = getattr(p, "_s3d_grad", None)
-                if g is None or not getattr(p, "_s3d_grad_touched", False):
-                    g = p.grad  # (a table no backward pass touched this step has no gradient, like `.grad is None`)
+                # (a table no backward pass touched this step has no gradient, like `.grad is None`)
+                g = h.grad if h is not None and h.touched else p.grad
                 if g is not None:
                     yield group, p, g
 
@@ -196,19 +201,16 @@ class NativeAdam(torch.optim.Optimizer):
         if self.flat_half is not None:
             # the backward kernels ACCUMULATE into it (several calls per step are summed).  Written since the last clear and not
             # consumed by step(): fill; otherwise it is still all zeros
-            dirty = any(getattr(p, "_s3d_grad_touched", False) and not getattr(p, "_s3d_grad_consumed", False)
-                        for group in self.param_groups for p in group["params"] if getattr(p, "_s3d_grad", None) is not None)
-            if dirty:
+            if any(h.dirty for _, h in self._records()):
                 self.flat_half.zero_()
             # (under graph capture this decision is frozen into the graph: a capture that finds the buffer clean records no
             #  fill and relies on every replay being preceded by a consuming step — GraphedTrainer._replay checks the flags
             #  again on the host before each replay, clear_unconsumed())
         for group in self.param_groups:
             for p in group["params"]:
-                if getattr(p, "_s3d_grad", None) is not None:
-                    p._s3d_grad_touched = False
-                    p._s3d_grad_consumed = False
-                    p._s3d_unchecked = False
+                h = getattr(p, "_s3d", None)
+                if h is not None:
+                    h.touched = h.consumed = h.unchecked = False
                 p.__dict__.pop("_s3d_grad_checked", None)  # (a producer's "checked at the source" mark never outlives its step)
                 if p.grad is not None:
                     if set_to_none:
@@ -223,23 +225,19 @@ class NativeAdam(torch.optim.Optimizer):
         if self.flat_half is None:
             return False
         dirty = False
-        for group in self.param_groups:
-            for p in group["params"]:
-                if getattr(p, "_s3d_grad", None) is not None and getattr(p, "_s3d_grad_touched", False) \
-                        and not getattr(p, "_s3d_grad_consumed", False):
-                    dirty = True
-                    p._s3d_grad_touched = False
+        for _, h in self._records():
+            if h.dirty:
+                dirty = True
+                h.touched = False
         if dirty:
             self.flat_half.zero_()
         return dirty
 
     def resync_half(self):
         """re-make the fp16 copies after the fp32 parameters were written from outside (checkpoint load)"""
-        for group in self.param_groups:
-            for p in group["params"]:
-                if hasattr(p, "_s3d_half"):
-                    p._s3d_half.copy_(p.detach())
-                    p._s3d_half_version = p._version
+        for p, h in self._records():
+            h.half.copy_(p.detach())
+            h.half_version = p._version
 
     def state_dict(self):
         """torch.optim.Adam's layout: per-parameter `step` next to exp_avg / exp_avg_sq (one shared count here)"""
@@ -296,10 +294,9 @@ class NativeAdam(torch.optim.Optimizer):
     def mark_all_touched(self):
         """after a gradient all-reduce every stashed gradient is the replicas' mean on EVERY rank, also on a rank whose own
         batch never reached that table: all ranks must take the same update"""
-        for group in self.param_groups:
-            for p in group["params"]:
-                if getattr(p, "_s3d_grad", None) is not None and p.requires_grad:  # (frozen MLPs of Seal's pretraining stay put)
-                    p._s3d_grad_touched = True
+        for p, h in self._records():
+            if p.requires_grad:  # (frozen MLPs of Seal's pretraining stay put)
+                h.touched = True
 
     @torch.no_grad()
     def step(self, grad_scale=None, found_inf=None, before_param=None, advance=True):
@@ -318,11 +315,11 @@ class NativeAdam(torch.optim.Optimizer):
             if before_param is not None:
                 before_param(p)
             st = self.state[p]
-            half = getattr(p, "_s3d_half", None)
-            if half is not None and p._s3d_half_version != p._version:
-                half = None  # somebody wrote the parameter through torch: the fp16 copy is re-made below
+            h = getattr(p, "_s3d", None)
+            mine = h is not None and g is h.grad  # (the hand-over buffer, not a plain `.grad`)
+            half = h.fresh_half(p) if h is not None else None  # (None: written through torch, the fp16 copy is re-made below)
             b1, b2 = group["betas"]
-            packed = getattr(p, "_s3d_pack_spec", None) is not None and g is getattr(p, "_s3d_grad", None)
+            packed = mine and getattr(p, "_s3d_pack_spec", None) is not None
             if half is not None and not packed and not half.is_contiguous():
                 half = None  # a pack member updated from a plain `.grad` (nn.Linear route): its strided fp16 image is re-copied below
             item = (p.data, g, st["exp_avg"], st["exp_avg_sq"], half, lr_of.get(id(group), group["lr"]), b1, b2, group["eps"])
@@ -334,33 +331,31 @@ class NativeAdam(torch.optim.Optimizer):
                 # (row-strided views of the pack: the multi-tensor entry point knows the layout.  The MLP backward OVERWRITES
                 #  the pack's gradient twin, so nothing is cleared behind the read)
                 _backend.adam_step_multi([item + (False,)], self.step_count, grad_scale, found_inf, lr_scale=self.lr_scale)
-                p._s3d_grad_consumed = True
+                h.consumed = True
             elif before_param is not None:
                 _backend.adam_step(*item, self.step_count, grad_scale, found_inf, self.lr_scale)
             elif packed:
                 batch.append(item + (False,))
-                consumed.append(p)  # (nothing to clear: the next backward overwrites the pack's gradient twin)
+                consumed.append(h)  # (nothing to clear: the next backward overwrites the pack's gradient twin)
             else:
                 # (a hand-over buffer is cleared behind the read; a `.grad` stays readable after the step)
-                mine = self.consume_grads and g is getattr(p, "_s3d_grad", None)
-                batch.append(item + (mine, l1))
-                if mine:
-                    consumed.append(p)
-            if half is None and hasattr(p, "_s3d_half"):
-                stale.append(p)
+                clear = self.consume_grads and mine
+                batch.append(item + (clear, l1))
+                if clear:
+                    consumed.append(h)
+            if half is None and h is not None:
+                stale.append((p, h))
         if batch:
             _backend.adam_step_multi(batch, self.step_count, grad_scale, found_inf, lr_scale=self.lr_scale)
-            for p in consumed:
-                p._s3d_grad_consumed = True
-        for p in stale:
-            p._s3d_half.copy_(p.detach())  # (a strided view into the pack for packed parameters)
-            p._s3d_half_version = p._version
+            for h in consumed:
+                h.consumed = True
+        for p, h in stale:
+            h.half.copy_(p.detach())  # (a strided view into the pack for packed parameters)
+            h.half_version = p._version
         if advance:
             _backend.adam_advance(self.step_count, found_inf)
-        for group in self.param_groups:  # (the marks of this step's in-backward updates; an arm nobody consumed goes with them)
-            for p in group["params"]:
-                p.__dict__.pop("_s3d_fused_done", None)
-                p.__dict__.pop("_s3d_fused_arm", None)
+        for _, h in self._records():  # (the marks of this step's in-backward updates; an arm nobody consumed goes with them)
+            h.fused_done, h.arm = False, None
 
 
 class NativeGradScaler:
@@ -411,14 +406,14 @@ class NativeGradScaler:
         buffer per step.  Single replica only: after an averaging all-reduce the REDUCED gradient is what must be checked."""
         for group in optimizer.param_groups:
             for p in group["params"]:
-                if getattr(p, "_s3d_grad", None) is not None:
-                    p._s3d_found_inf = self._found_inf
-                    p._s3d_unchecked = False
+                h = getattr(p, "_s3d", None)
+                if h is not None:
+                    h.found_inf = self._found_inf
+                    h.unchecked = False
 
     def _checked_at_source(self, optimizer):
-        adopted = [p for group in optimizer.param_groups for p in group["params"] if getattr(p, "_s3d_grad", None) is not None]
-        return bool(adopted) and all(getattr(p, "_s3d_found_inf", None) is self._found_inf and
-                                     not getattr(p, "_s3d_unchecked", False) for p in adopted)
+        adopted = [p._s3d for group in optimizer.param_groups for p in group["params"] if getattr(p, "_s3d", None) is not None]
+        return bool(adopted) and all(h.found_inf is self._found_inf and not h.unchecked for h in adopted)
 
     def _check(self, optimizer):
         flat = getattr(optimizer, "flat_half", None)
@@ -435,7 +430,7 @@ class NativeGradScaler:
         # (the mark is popped from EVERY parameter first: a mark whose backward was not followed by this scaler's step — a loss
         #  evaluated without a step, an exception, another scaler — must not excuse a later gradient made by another route)
         marks = {id(p): p.__dict__.pop("_s3d_grad_checked", None) for _, p, _ in optimizer.grads()}
-        rest = [g for _, p, g in optimizer.grads() if (flat is None or g is not getattr(p, "_s3d_grad", None))
+        rest = [g for _, p, g in optimizer.grads() if (flat is None or getattr(p, "_s3d", None) is None or g is not p._s3d.grad)
                 and marks.get(id(p)) is not self._found_inf]
         if len(rest) > 1 and all(g.is_cuda and g.dtype == rest[0].dtype and g.layout == torch.strided for g in rest):
             torch._amp_foreach_non_finite_check_and_unscale_(rest, self._found_inf, self._one)
@@ -480,13 +475,12 @@ class NativeGradScaler:
             optimizer.mark_all_touched()
 
         def before_param(p):
-            rng = getattr(p, "_s3d_flat_range", None)
-            buf = getattr(p, "_s3d_grad_flat", None)
+            h = getattr(p, "_s3d", None)
             while pending:
-                h = pending[0]
+                piece = pending[0]
                 # pieces were issued in buffer order: everything up to the end of p's range (or, for a parameter of the
                 # fp32 bucket, everything) must have arrived
-                if rng is not None and h[0] is buf and h[1] >= rng[1]:
+                if h is not None and piece[0] is h.flat and piece[1] >= h.flat_range[1]:
                     break
                 dist.finish_chunk(pending.pop(0))
         optimizer.step(grad_scale=self._scale if self.enabled else None, found_inf=self._found_inf, before_param=before_param,

@@ -2,6 +2,8 @@
 Adam, with fp16 autocast + GradScaler (`-O`), `update_extra_state` every 16 steps (nerf/utils.py:845-848),
 Adam(betas=(0.9, 0.99), eps=1e-15) and lr 1e-2 (main_SealNeRF.py:283-288), PSNR as in nerf/utils.py:226-233.
 Optional data parallelism over rays: gradients are all-reduced through one flat bucket (parallel/dist.py)."""
+import contextlib
+import gc
 import math
 import os
 
@@ -315,7 +317,7 @@ class Trainer:
                 and hasattr(sc, "_checked_at_source")):
             return False
         params = [p for g in opt.param_groups for p in g["params"]]
-        return all(getattr(p, "_s3d_grad", None) is not None for p in params) and sc._checked_at_source(opt)
+        return all(getattr(p, "_s3d", None) is not None for p in params) and sc._checked_at_source(opt)
 
     def _arm_fused_tables(self):
         """single replica, native optimizer + scaler, every gradient of the step a hand-over buffer whose producer raises the
@@ -408,6 +410,23 @@ class Trainer:
 # polls its work events (hipEventQuery) at any time, and under the default "global" mode such a poll during one of the
 # captures below aborts the process ("operation not permitted when stream is capturing").
 _CAPTURE_MODE = "thread_local"
+
+
+@contextlib.contextmanager
+def _capturing(graph, pool=None):
+    """`torch.cuda.graph` under _CAPTURE_MODE with Python's cycle collector held off.  A collection that starts inside a capture
+    runs, on the capturing thread, the destructors of whatever dead cycle it finds — an earlier trainer with its CUDAGraph and
+    that graph's private memory pool among them (a trainer is part of a cycle: tests that need one gone call gc.collect()) — and
+    a HIP call that stream capture does not permit aborts the process.  When a collection falls is a matter of allocation counts,
+    so it moves with any change of host code.  Garbage waits until the capture has ended."""
+    held = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, capture_error_mode=_CAPTURE_MODE, **({} if pool is None else {"pool": pool})):
+            yield
+    finally:
+        if held:
+            gc.enable()
 _RING_PUSH = __import__("os").environ.get("S3D_RING_PUSH", "1") != "0"  # A/B switch: 0 = host-side ring bookkeeping
 
 
@@ -547,7 +566,7 @@ class GraphedTrainer(Trainer):
         self.graph = torch.cuda.CUDAGraph()
         model.local_step = 0
         if self.dist is None:
-            with torch.cuda.graph(self.graph, capture_error_mode=_CAPTURE_MODE):
+            with _capturing(self.graph):
                 self.s_loss = self._body_fb()
                 self._body_opt()
             self.graph_opt = None
@@ -558,7 +577,7 @@ class GraphedTrainer(Trainer):
             saved_chunk = self.dist.chunk_bytes
             self.dist.chunk_bytes = 1 << 40
             try:
-                with torch.cuda.graph(self.graph, capture_error_mode=_CAPTURE_MODE):
+                with _capturing(self.graph):
                     self.s_loss = self._body_fb()
                     self.dist.allreduce_grads(self.scaler)
                     self._body_opt()
@@ -567,10 +586,10 @@ class GraphedTrainer(Trainer):
             self.graph_opt = None
             self.collectives_in_graph = True
         else:
-            with torch.cuda.graph(self.graph, capture_error_mode=_CAPTURE_MODE):
+            with _capturing(self.graph):
                 self.s_loss = self._body_fb()
             self.graph_opt = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph_opt, pool=self.graph.pool(), capture_error_mode=_CAPTURE_MODE):
+            with _capturing(self.graph_opt, pool=self.graph.pool()):
                 self._body_opt()
             self.collectives_in_graph = False
         model.step_counter = ring
@@ -621,7 +640,7 @@ class GraphedTrainer(Trainer):
             else:
                 if self.ues_graph is None:
                     self.ues_graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self.ues_graph, capture_error_mode=_CAPTURE_MODE):
+                    with _capturing(self.ues_graph):
                         self.ues_mean = model.partial_grid_update_device()
                 model.stage_extra_state()
                 self.ues_graph.replay()

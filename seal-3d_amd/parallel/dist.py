@@ -85,12 +85,13 @@ class RayShardedDP:
         # bytes on the wire; everything else is re-homed inside the flat fp32 bucket
         self.half_grads, seen = [], set()
         for p in model.parameters():
-            if p.requires_grad and getattr(p, "_s3d_grad", None) is not None:
-                buf = getattr(p, "_s3d_grad_flat", p._s3d_grad)  # the optimizer's single flat buffer when there is one
+            h = getattr(p, "_s3d", None)
+            if p.requires_grad and h is not None:
+                buf = h.flat  # the optimizer's single flat buffer
                 if buf.data_ptr() not in seen:
                     seen.add(buf.data_ptr())
                     self.half_grads.append(buf)
-        self.params = [p for p in model.parameters() if p.requires_grad and getattr(p, "_s3d_grad", None) is None]
+        self.params = [p for p in model.parameters() if p.requires_grad and getattr(p, "_s3d", None) is None]
         if self.world > 1:
             for t in list(model.parameters()) + list(model.buffers()):
                 dist.broadcast(t.data, src=0, group=self.group)

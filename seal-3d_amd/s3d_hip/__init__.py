@@ -238,6 +238,33 @@ class StepTail:
             StepTail.current = None
 
 
+class Handover:
+    """What a parameter carries because a nerf.optim.NativeAdam adopted it: `p._s3d` is one of these, or p is not adopted.  Made
+    whole by the adoption (NativeAdam.__init__, PackedWeights.adopt), so nothing of an earlier optimizer or scaler survives one.
+      grad, flat, flat_range    the fp16 gradient the backward kernels write, the optimizer's flat buffer and p's elements of it
+      half, half_version        the fp16 copy the update launch maintains and the `p._version` it was made for
+      touched, consumed         written since the last clear / read (and cleared) by a step since: host-side flags
+      unchecked                 a torch op wrote `grad`: the scaler checks the buffer itself
+      found_inf                 the attached scaler's flag, raised by the kernels that write `grad` (NativeGradScaler.attach)
+      arm, fused_done           arguments of the update a table's backward applies itself (arm_fused_tables) / it did so"""
+    __slots__ = ("grad", "flat", "flat_range", "half", "half_version", "touched", "consumed", "unchecked", "found_inf", "arm",
+                 "fused_done")
+
+    def __init__(self, grad=None, flat=None, flat_range=None, half=None, half_version=None):
+        self.grad, self.flat, self.flat_range, self.half, self.half_version = grad, flat, flat_range, half, half_version
+        self.touched = self.consumed = self.unchecked = self.fused_done = False
+        self.found_inf = self.arm = None
+
+    def fresh_half(self, p):
+        """the fp16 copy while it is p's current value, else None (somebody wrote the parameter through torch)"""
+        return self.half if self.half_version == p._version else None
+
+    @property
+    def dirty(self):
+        """written since the last clear and not consumed by a step"""
+        return self.touched and not self.consumed
+
+
 def _shadow2(shadows):
     """(planes_t, lines_t) pointer arrays of VmBackend.transpose_factors()' result, or two NULLs"""
     if shadows is None:

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from nerf.trainer import _CAPTURE_MODE, GraphedTrainer, Trainer
+from nerf.trainer import GraphedTrainer, Trainer, _capturing
 
 
 def _euler_dirs(angle_step):
@@ -311,7 +311,7 @@ class SealSteps:
             sig = sig[:-1] + (getattr(self.optimizer, "lr_epoch", 0),)  # (the eager step may have rebased: store what the capture sees)
             g = torch.cuda.CUDAGraph()
             pool = next(iter(self._pt_graphs.values()))[0].pool() if self._pt_graphs else None
-            with torch.cuda.graph(g, pool=pool, capture_error_mode=_CAPTURE_MODE):
+            with _capturing(g, pool=pool):
                 loss = self.pretrain_step(*args, n_total=n_total)
             self._pt_graphs[key] = (g, loss, sig)
             return warm  # (the capture itself does not execute)
@@ -573,7 +573,7 @@ class GraphedSealTrainer(SealSteps, GraphedTrainer):
                 body()  # warm-up = this call's render
             torch.cuda.current_stream().wait_stream(side)
             self.proxy_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.proxy_graph, capture_error_mode=_CAPTURE_MODE):
+            with _capturing(self.proxy_graph):
                 body()
             return
         self.proxy_graph.replay()

@@ -98,6 +98,41 @@ def test_scaler_update_carries_the_step_count_advance(hip):
     assert float(sc._found_inf) == 0.0 and float(sc._scale) == 2.0 ** 15
 
 
+def test_a_second_adoption_starts_from_a_whole_record(hip):
+    """A parameter adopted by a second NativeAdam (what the data-parallel arrangement does: its own scaler, no attach) carries a
+    NEW record with nothing of the first adoption in it — in particular not the first scaler's flag: an overflow in a step of
+    the second pair raises the second scaler's flag only, and that step is skipped."""
+    import s3d_hip
+    from gridencoder import GridEncoder
+    from nerf.optim import NativeAdam, NativeGradScaler
+    torch.manual_seed(0)
+    enc = GridEncoder(input_dim=3, num_levels=2, level_dim=2, base_resolution=4, log2_hashmap_size=8).cuda()
+    p = enc.embeddings
+    opt_a, sc_a = NativeAdam([{"params": [p]}], lr=1e-2), NativeGradScaler("cuda")
+    sc_a.attach(opt_a)
+    first = p._s3d
+    assert isinstance(first, s3d_hip.Handover) and first.found_inf is sc_a._found_inf
+    first.unchecked = True  # (as after GridEncoder.grad_total_variation)
+    opt_b, sc_b = NativeAdam([{"params": [p]}], lr=1e-2), NativeGradScaler("cuda")
+    h = p._s3d
+    assert isinstance(h, s3d_hip.Handover) and h is not first
+    assert h.found_inf is None and h.arm is None
+    assert not (h.touched or h.consumed or h.unchecked or h.fused_done)
+    assert h.flat is opt_b.flat_half and h.grad.data_ptr() == opt_b.flat_half.data_ptr()
+    before, half_before = p.detach().clone(), h.half.clone()
+    x = (torch.rand(128, 3, generator=torch.Generator().manual_seed(1)) * 2 - 1).cuda()
+    opt_b.zero_grad()
+    with torch.autocast("cuda", dtype=torch.float16):
+        y = enc(x, bound=1)
+    g = torch.ones(y.shape, dtype=y.dtype)  # the upstream gradient, made on the host, one element non-finite
+    g[5, 1] = float("inf")
+    y.backward(g.cuda())
+    assert p.grad is None and h.touched
+    sc_b.step(opt_b)
+    assert float(sc_a._found_inf) == 0.0 and float(sc_b._found_inf) != 0.0
+    assert torch.equal(p.detach(), before) and torch.equal(h.half, half_before)
+
+
 def test_grid_encoder_half_grad_handover_matches_reference_update(hip):
     """Same data through (a) autograd fp32 grads + torch Adam + GradScaler and (b) fp16 hand-over + NativeAdam +
     NativeGradScaler: the tables must follow the same trajectory (the fp16 gradient values are identical, only their
@@ -113,7 +148,7 @@ def test_grid_encoder_half_grad_handover_matches_reference_update(hip):
     sa = NativeGradScaler("cuda", init_scale=1024.0)
     ob = torch.optim.Adam(eb.parameters(), lr=1e-2, betas=(0.9, 0.99), eps=1e-15)
     sb = torch.amp.GradScaler("cuda", init_scale=1024.0)
-    assert ea.embeddings._s3d_grad.dtype == torch.float16
+    assert ea.embeddings._s3d.grad.dtype == torch.float16
     for step in range(4):
         x = (torch.rand(9000, 3, generator=torch.Generator().manual_seed(step)) * 2 - 1).cuda()
         for enc, opt, sc in ((ea, oa, sa), (eb, ob, sb)):
@@ -129,7 +164,7 @@ def test_grid_encoder_half_grad_handover_matches_reference_update(hip):
         # and Adam with eps = 1e-15 turns gradient noise of rarely-hit rows (v ~ 1e-18) into percent-level changes of
         # their 1e-2-sized updates: trajectories are compared at 1e-3 of an update
         torch.testing.assert_close(ea.embeddings.detach(), eb.embeddings.detach(), rtol=1e-3, atol=(1e-8 if step == 0 else 2e-5))
-        assert torch.equal(ea.embeddings._s3d_half, ea.embeddings.detach().half())
+        assert torch.equal(ea.embeddings._s3d.half, ea.embeddings.detach().half())
         assert sa.get_scale() == sb.get_scale()
     assert sa.get_scale() == 512.0  # one overflow halved the scale
     # writing the parameter through torch invalidates the fp16 copy; the next forward must see the new values
@@ -169,15 +204,15 @@ def test_ffmlp_weight_grad_handover(hip):
     ma, mb = FFMLP(32, 16, 64, 2).cuda(), FFMLP(32, 16, 64, 2).cuda()
     mb.load_state_dict(ma.state_dict())
     opt = NativeAdam([{"params": ma.parameters()}], lr=1e-3)
-    assert opt.flat_half is not None and ma.weights._s3d_grad_flat is opt.flat_half
+    assert opt.flat_half is not None and ma.weights._s3d.flat is opt.flat_half
     x = torch.randn(1024, 32, device="cuda")
     opt.zero_grad()
     for m in (ma, mb):
         for _ in range(2):
             with torch.autocast("cuda", dtype=torch.float16):
                 (m(x).float() ** 2).mean().backward()
-    assert ma.weights.grad is None and ma.weights._s3d_grad_touched
-    torch.testing.assert_close(ma.weights._s3d_grad.float(), mb.weights.grad, rtol=2e-3, atol=1e-4)
+    assert ma.weights.grad is None and ma.weights._s3d.touched
+    torch.testing.assert_close(ma.weights._s3d.grad.float(), mb.weights.grad, rtol=2e-3, atol=1e-4)
 
 
 def _through_file(obj):

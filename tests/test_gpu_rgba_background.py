@@ -408,7 +408,7 @@ def test_tensorf_step_with_a_per_ray_background_matches_its_unfused_twin(hip, mo
         tr.global_step = 1
         seen = {}
         monkeypatch.setattr(tr, "_reduce_and_step", lambda seen=seen, net=net: seen.update(
-            {k: (p.grad if p.grad is not None else getattr(p, "_s3d_grad", None)).detach().float().clone() for k, p in net.named_parameters()}))
+            {k: (p.grad if p.grad is not None else p._s3d.grad).detach().float().clone() for k, p in net.named_parameters()}))
         torch.manual_seed(5)
         loss = tr.train_step(b["rays_o"][0], b["rays_d"][0], b["images"][0], bg_color=b["bg_color"][0])
         torch.cuda.synchronize()

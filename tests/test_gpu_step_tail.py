@@ -233,7 +233,7 @@ def _snapshot(tr, model, losses):
     out = [losses, tr.scaler._scale.clone(), tr.scaler._growth_tracker.clone(), opt.step_count.clone(), model.step_counter.clone()]
     for p in model.parameters():
         st = opt.state[p]
-        out += [p.detach().clone(), st["exp_avg"].clone(), st["exp_avg_sq"].clone(), p._s3d_half.clone(), p._s3d_grad.clone()]
+        out += [p.detach().clone(), st["exp_avg"].clone(), st["exp_avg_sq"].clone(), p._s3d.half.clone(), p._s3d.grad.clone()]
     return out
 
 

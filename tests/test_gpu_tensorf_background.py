@@ -289,7 +289,7 @@ def test_executed_train_step_with_background_vs_fixture(hip, monkeypatch, G):
     torch.manual_seed(5)
     seen = {}
     monkeypatch.setattr(tr, "_reduce_and_step", lambda: seen.update(
-        {k: (p.grad if p.grad is not None else getattr(p, "_s3d_grad", None)).detach().float().clone() for k, p in net.named_parameters()}))
+        {k: (p.grad if p.grad is not None else p._s3d.grad).detach().float().clone() for k, p in net.named_parameters()}))
     ro, rd, gt = (torch.from_numpy(G[k]).cuda() for k in ("ts_rays_o", "ts_rays_d", "ts_images"))
     loss = tr.train_step(ro[0].contiguous(), rd[0].contiguous(), gt[0].contiguous())
     assert np.array_equal(net.step_counter[0].cpu().numpy(), G["ts_counter"])

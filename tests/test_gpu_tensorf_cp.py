@@ -386,7 +386,7 @@ def test_cp_train_step_with_l1_term_vs_the_reference_trainer(hip, monkeypatch):
     torch.manual_seed(5)
     seen = {}
     monkeypatch.setattr(tr, "_reduce_and_step", lambda: seen.update(
-        {k: (p.grad if p.grad is not None else getattr(p, "_s3d_grad", None)).detach().float().clone() for k, p in net.named_parameters()}))
+        {k: (p.grad if p.grad is not None else p._s3d.grad).detach().float().clone() for k, p in net.named_parameters()}))
     ro, rd, gt = (torch.from_numpy(T[k]).cuda() for k in ("ts_rays_o", "ts_rays_d", "ts_images"))
     loss = tr.train_step(ro[0].contiguous(), rd[0].contiguous(), gt[0].contiguous())
     assert np.array_equal(net.step_counter[0].cpu().numpy(), T["ts_counter"])

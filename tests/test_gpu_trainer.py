@@ -50,10 +50,10 @@ def test_training_variants_converge_alike(hip, variant):
     if variant == "graph-native":
         assert tr.n_captures >= 1 and tr.graph is not None
         emb = model.encoder.embeddings
-        assert emb.grad is None and (emb._s3d_grad_touched or tr.fuse_table_updates)  # fp16 hand-over / in-backward update active inside the captured step
-        assert torch.equal(emb._s3d_half, emb.detach().half())      # the fp16 copy tracks the master weights
+        assert emb.grad is None and (emb._s3d.touched or tr.fuse_table_updates)  # fp16 hand-over / in-backward update active inside the captured step
+        assert torch.equal(emb._s3d.half, emb.detach().half())      # the fp16 copy tracks the master weights
     if variant == "eager-torch":
-        assert model.encoder.embeddings.grad is not None and not hasattr(model.encoder.embeddings, "_s3d_grad")
+        assert model.encoder.embeddings.grad is not None and not hasattr(model.encoder.embeddings, "_s3d")
 
 
 def test_second_graphed_trainer_after_the_first_is_gone(hip):
@@ -249,7 +249,7 @@ def test_checkpoint_resume_under_graph_replay(hip, tmp_path):
     assert tr2.scaler.get_scale() == tr.scaler.get_scale()
     assert torch.equal(tr2.render_image(ro, rd)["image"], img)
     emb = model2.encoder.embeddings
-    assert torch.equal(emb._s3d_half, emb.detach().half())
+    assert torch.equal(emb._s3d.half, emb.detach().half())
     before = float(_run(tr, batches, 8).mean())
     after = float(_run(tr2, batches, 8).mean())
     assert tr2.graph is not None and abs(after - before) < 0.5 * before + 1e-3, (before, after)
@@ -479,12 +479,12 @@ def test_table_update_inside_the_backward_equals_the_separate_update_bit_for_bit
         losses = _run(tr, batches, 40)
         emb = model.encoder.embeddings
         st = tr.optimizer.state[emb]
-        res[fuse] = (losses, emb.detach().clone(), st["exp_avg"].clone(), st["exp_avg_sq"].clone(), emb._s3d_half.clone(),
+        res[fuse] = (losses, emb.detach().clone(), st["exp_avg"].clone(), st["exp_avg_sq"].clone(), emb._s3d.half.clone(),
                      [p.detach().clone() for p in model.parameters()], float(tr.optimizer.step_count))
         if fuse:
-            assert not emb._s3d_grad_touched and float(emb._s3d_grad.abs().max()) == 0.0, "the gradient table must stay untouched"
+            assert not emb._s3d.touched and float(emb._s3d.grad.abs().max()) == 0.0, "the gradient table must stay untouched"
         else:
-            assert emb._s3d_grad_touched
+            assert emb._s3d.touched
     a, b = res[True], res[False]
     assert a[6] == b[6] == 40.0
     assert torch.equal(a[0], b[0]), (a[0] - b[0]).abs().max()

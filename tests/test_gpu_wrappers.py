@@ -414,7 +414,7 @@ def test_packed_linear_weights_in_the_native_optimizer_match_the_assembled_path(
             for pk in net._packs:
                 assert pk.current() is not None
                 for p, _, _ in pk.members:
-                    assert p.grad is None and p._s3d_grad_consumed  # the gradient never became a `.grad`
+                    assert p.grad is None and p._s3d.consumed  # the gradient never became a `.grad`
             ws, wc = net._packed_weights()
             assert torch.equal(net._packs[0].half, ws.half()) and torch.equal(net._packs[1].half, wc.half())
         out[packed] = (losses, {k: v.detach().clone() for k, v in net.named_parameters()})
@@ -426,7 +426,7 @@ def test_packed_linear_weights_in_the_native_optimizer_match_the_assembled_path(
 def test_two_backward_passes_of_one_step_add_up_in_the_packed_weight_gradient(hip):
     """`NeRFRenderer.run` (cuda_ray off, nerf/renderer.py:168-214) queries `density()` twice with gradients before one
     optimizer step, and gradient accumulation runs several backward passes per step.  The pack's gradient twin is never cleared,
-    so the FIRST backward since zero_grad() / step() replaces it and every further one adds to it (PackedWeights._s3d_overwrite):
+    so the FIRST backward since zero_grad() / step() replaces it and every further one adds to it (PackedWeights.overwrite):
     the twin must hold the SUM of both passes — against the same model without packs, where autograd sums the fp32 `.grad`s —
     and the next step must start from a replaced twin again."""
     from nerf import network
@@ -456,14 +456,14 @@ def test_two_backward_passes_of_one_step_add_up_in_the_packed_weight_gradient(hi
                 (sig.float().sum() * 4.0).backward()
             ws = [l.weight for l in net.sigma_net]
             if packed:
-                assert all(w.grad is None and w._s3d_grad_touched for w in ws)
-                out.append([w._s3d_grad.float().clone() for w in ws])
+                assert all(w.grad is None and w._s3d.touched for w in ws)
+                out.append([w._s3d.grad.float().clone() for w in ws])
             else:
                 out.append([w.grad.float().clone() for w in ws])
             if batches is not None and len(batches) == 2:
                 for w in ws:      # as a consuming step would leave the flags (the twin itself stays as it is: never cleared)
                     if packed:
-                        w._s3d_grad_consumed = True
+                        w._s3d.consumed = True
         res[packed] = out
     for step in range(2):
         for a, b in zip(res[True][step], res[False][step]):

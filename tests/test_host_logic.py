@@ -237,26 +237,53 @@ def test_scaler_skips_its_gradient_pass_only_when_every_writer_reports():
     written since zero_grad; a parameter attached to another scaler, or none adopted, keeps the pass."""
     import types
     import torch
+    import s3d_hip
     from nerf.optim import NativeGradScaler
     sc, other = NativeGradScaler("cpu"), NativeGradScaler("cpu")
 
     def param(adopted=True):
         p = types.SimpleNamespace()
         if adopted:
-            p._s3d_grad = torch.zeros(4, dtype=torch.float16)
+            p._s3d = s3d_hip.Handover(grad=torch.zeros(4, dtype=torch.float16))
         return p
     a, b, plain = param(), param(), param(adopted=False)
     opt = types.SimpleNamespace(param_groups=[{"params": [a, plain]}, {"params": [b]}])
     assert not sc._checked_at_source(opt)              # nobody attached
     sc.attach(opt)
-    assert a._s3d_found_inf is sc._found_inf and not hasattr(plain, "_s3d_found_inf")
+    assert a._s3d.found_inf is sc._found_inf and not hasattr(plain, "_s3d")
     assert sc._checked_at_source(opt) and not other._checked_at_source(opt)
-    b._s3d_unchecked = True                            # e.g. GridEncoder.grad_total_variation added to the buffer
+    b._s3d.unchecked = True                            # e.g. GridEncoder.grad_total_variation added to the buffer
     assert not sc._checked_at_source(opt)
-    b._s3d_unchecked = False
-    b._s3d_found_inf = other._found_inf                # attached elsewhere
+    b._s3d.unchecked = False
+    b._s3d.found_inf = other._found_inf                # attached elsewhere
     assert not sc._checked_at_source(opt)
     assert not sc._checked_at_source(types.SimpleNamespace(param_groups=[{"params": [plain]}]))  # nothing adopted
+
+
+def test_handover_record_refuses_unknown_fields_and_answers_its_two_questions():
+    """s3d_hip.Handover (what an adopted parameter carries, `p._s3d`): a misspelt field raises instead of reading as "not
+    adopted"; `fresh_half` is the fp16 copy exactly while the parameter's version is the one it was made for; `dirty` is
+    "written and not consumed" through all four combinations of the two flags."""
+    import pytest
+    import torch
+    import s3d_hip
+    p = torch.nn.Parameter(torch.arange(4.0))
+    h = s3d_hip.Handover(half=p.detach().half(), half_version=p._version)
+    with pytest.raises(AttributeError):
+        h.grad_touchd = True
+    with pytest.raises(AttributeError):
+        h.grad_touchd
+    assert h.found_inf is None and h.arm is None and not (h.touched or h.consumed or h.unchecked or h.fused_done)
+    assert h.fresh_half(p) is h.half
+    with torch.no_grad():
+        p.mul_(2.0)                                    # written through torch: the version moved
+    assert h.fresh_half(p) is None
+    h.half_version = p._version                        # (what resync_half / step do after re-making the copy)
+    assert h.fresh_half(p) is h.half
+    for touched in (False, True):
+        for consumed in (False, True):
+            h.touched, h.consumed = touched, consumed
+            assert h.dirty == (touched and not consumed)
 
 
 def test_sorted_uniform_stream_is_the_order_statistics_of_iid_uniforms():
