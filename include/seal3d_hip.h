@@ -577,6 +577,65 @@ int s3d_cp_color_backward(const float* x, uint32_t N, const float* const* lines,
                           float* grad_basis, float* found_inf, const float* const* lines_t, const int32_t* n_valid,
                           s3d_stream_t stream);
 
+/* ------------------------------------------------------------------ CCNeRF features (rank-residual TensoRF)
+ * tensoRF/network_cc.py:128-250 compute_features_density / compute_features and the SH contraction of :287-291, in one pass per
+ * call, csrc/tensorf_cc.hip.  The components are cut into n_groups <= 8 groups; a group holds a vector component (three lines,
+ * one rank index: l0[r] * l1[r] * l2[r]) and / or a matrix component (three planes, one rank index: p0[r] * p1[r] * p2[r]) and
+ * one matrix S per component.  groups: HOST array of n_groups records; an absent component is NULL / rank 0:
+ *   line[i]  device fp32 [rank_vec, res[vec_ids[i]]], vec_ids = 2,1,0;
+ *   plane[i] device fp32 [rank_mat, res[m1], res[m0]], (m0, m1) = mat_ids[i] = (0,1), (0,2), (1,2): x[m0] runs along the last axis;
+ *   s_vec / s_mat device fp32 [rows, rank]: rows = 1 (features) or 3 * degree^2 (colour).
+ * Level k is the sum over the groups g <= k of S_vec_g (l0 l1 l2) + S_mat_g (p0 p1 p2).  residual = 1: every level is returned
+ * (K_out = n_groups); residual = 0: the last one only (K_out = 1).
+ *   s3d_cc_features_forward: out fp32 [K_out, N].
+ *   s3d_cc_color_forward:    out fp32 [K_out, N, 3] = sum_j level[ch * degree^2 + j] * SH_j(dirs[n]) — the logits in front of the
+ *                            sigmoid; degree 1 .. 4, dirs [N,3] fp32.  The [K, N, 3 degree^2] tensor is never written.
+ * Arithmetic contract.  Sampling is grid_sample's bilinear, zeros padding, align_corners = FALSE: per axis of D cells
+ * p = ((u + 1) * D - 1) / 2 in fp32, i0 = floor(p), weights (i0 + 1) - p and p - i0, a tap outside [0, D - 1] counts as zero (a
+ * point up to one cell outside [-1, 1] still reads a value); plane taps in the order nw, ne, sw, se with weight wx * wy; the
+ * products are (a * b) * c in fp32.  half = 0: everything is fp32; a level is (vec + mat) + previous level.  half = 1 (the fp16
+ * autocast sequence): every S @ f is the autocast Linear's arithmetic as s3d_vm_color_forward defines it,
+ * half(sum_r half(S[c][r]) * half(f[r])) with fp32 accumulation; the level sums are fp16 adds in the reference's order (vec, then
+ * mat, then the previous level); the SH contraction and everything behind it is fp32.
+ * Limits (anything else is refused): n_groups <= 8, (rank_vec + rank_mat) * rows <= 7168 per group (the group's S sits in LDS),
+ * rank * extent < 2^31 per factor.
+ * n_valid (optional): as for the s3d_vm_* entry points — rows [round_up(*n_valid, 128), N) are neither written nor read.
+ *
+ * Backward (parameter gradients only; the coordinates' and directions' gradients are not computed).  grad: fp32 [K_out, N] /
+ * [K_out, N, 3].  The level gradients are folded into per-group gradients by a suffix sum over the levels in registers (group g
+ * receives every level >= g).  grads: HOST array of n_groups records of device fp32 buffers shaped like the factors and the S
+ * matrices, ZERO-INITIALISED by the caller (the kernels add).  half = 1: the gradient that reaches S @ f and the operands of
+ * both products are rounded to binary16, sums are fp32.  Factor gradients leave by global fp32 atomics: adjacent points of a
+ * wave that fall into the same cell (consecutive samples of a ray) are summed first and leave by one atomic per tap and rank, any
+ * other point by its own; the S gradients are summed over the 128 points of a workgroup in LDS and leave by one atomic per entry
+ * and workgroup.  The order of the adds is the only thing that varies between runs.
+ * A non-finite gradient of any live point — inside or outside the factors — raises found_inf (optional device float, set to 1)
+ * and makes the first S gradient's first entry NaN; inside the factors it also travels through the sums. */
+typedef struct s3d_cc_group {
+    const float* line[3];
+    const float* plane[3];
+    const float* s_vec;
+    const float* s_mat;
+    uint32_t rank_vec, rank_mat;
+} s3d_cc_group;
+typedef struct s3d_cc_group_grad {
+    float* line[3];
+    float* plane[3];
+    float* s_vec;
+    float* s_mat;
+} s3d_cc_group_grad;
+int s3d_cc_features_forward(const float* x, uint32_t N, const s3d_cc_group* groups, uint32_t n_groups, const uint32_t* resolution,
+                            int residual, int half, float* out, const int32_t* n_valid, s3d_stream_t stream);
+int s3d_cc_color_forward(const float* x, const float* dirs, uint32_t N, const s3d_cc_group* groups, uint32_t n_groups,
+                         const uint32_t* resolution, uint32_t degree, int residual, int half, float* out, const int32_t* n_valid,
+                         s3d_stream_t stream);
+int s3d_cc_features_backward(const float* x, uint32_t N, const s3d_cc_group* groups, uint32_t n_groups, const uint32_t* resolution,
+                             int residual, int half, const float* grad, const s3d_cc_group_grad* grads, float* found_inf,
+                             const int32_t* n_valid, s3d_stream_t stream);
+int s3d_cc_color_backward(const float* x, const float* dirs, uint32_t N, const s3d_cc_group* groups, uint32_t n_groups,
+                          const uint32_t* resolution, uint32_t degree, int residual, int half, const float* grad,
+                          const s3d_cc_group_grad* grads, float* found_inf, const int32_t* n_valid, s3d_stream_t stream);
+
 /* Build extensions for the TensoRF step (chains of tiny launches otherwise):
  * s3d_aabb_normalize: out[n][a] = 2 (x[n][a] - aabb[a]) / (aabb[3 + a] - aabb[a]) - 1 (tensoRF/network.py:155-157, the reference's
  *   operation order; aabb = 6 DEVICE floats);

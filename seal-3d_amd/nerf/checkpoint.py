@@ -32,6 +32,10 @@ def save_checkpoint(trainer, workspace, name="ngp", full=False, best=False, remo
         state["mean_density"] = model.mean_density
     if hasattr(model, "upsample_model") and hasattr(model, "resolution"):
         state["resolution"] = list(model.resolution)  # TensoRF: factor resolution at save time (tensoRF/utils.py:236)
+    if getattr(model, "rank_residual", False):  # CCNeRF: the model's structure (tensoRF/utils.py:251-256)
+        _refuse_composed(model, "save")
+        for key in _CC_RANKS:
+            state[key] = [int(r) for r in getattr(model, key)[0]]
     if full:
         state["optimizer"] = trainer.optimizer.state_dict()
         if lr_scheduler is not None:
@@ -86,7 +90,10 @@ def load_checkpoint(trainer, checkpoint, model_only=False, lr_scheduler=None, em
         model.load_state_dict(ckpt)
         _after_weights_changed(trainer)
         return [], []
-    if "resolution" in ckpt and hasattr(model, "upsample_model") and list(ckpt["resolution"]) != list(model.resolution):
+    if getattr(model, "rank_residual", False) and all(k in ckpt for k in _CC_RANKS):
+        _refuse_composed(model, "load")
+        model = _match_cc_structure(trainer, ckpt)
+    elif "resolution" in ckpt and hasattr(model, "upsample_model") and list(ckpt["resolution"]) != list(model.resolution):
         # TensoRF: bring the factors to the checkpoint's resolution before loading them, then re-create the optimizer
         # over the new Parameters (tensoRF/utils.py:347-352)
         model.upsample_model(ckpt["resolution"])
@@ -112,6 +119,39 @@ def load_checkpoint(trainer, checkpoint, model_only=False, lr_scheduler=None, em
     if trainer.scaler is not None and "scaler" in ckpt and ckpt["scaler"]:
         trainer.scaler.load_state_dict(ckpt["scaler"])
     return list(missing), list(unexpected)
+
+
+_CC_RANKS = ("rank_vec_density", "rank_mat_density", "rank_vec", "rank_mat")
+
+
+def _refuse_composed(model, what):
+    """the checkpoint format carries ONE object's rank lists (the reference's does too): a composed scene — several objects with
+    their `T_i` / `R_i` / `aabb_i` buffers — would be written with the host object's structure and come back with the other
+    objects' tensors as unexpected keys.  Save the objects' own checkpoints and compose them again after loading."""
+    if len(model.K) > 1:
+        raise ValueError(f"checkpoint: cannot {what} a composed CCNeRF scene ({len(model.K) - 1} composed objects): the format "
+                         "holds one object's rank lists; keep the objects' own checkpoints and call compose() after loading them")
+
+
+def _match_cc_structure(trainer, ckpt):
+    """CCNeRF: a checkpoint fits only a model of its own structure — the rank lists decide how many parameters there are, and a
+    finalized or compressed model has other lists than the one it was trained as.  A model of another structure is re-created
+    from the checkpoint's lists at the checkpoint's resolution, and the optimizer over its parameters (tensoRF/utils.py:327-356
+    of the reference)."""
+    model = trainer.model
+    same = (all([int(r) for r in ckpt[k]] == [int(r) for r in getattr(model, k)[0]] for k in _CC_RANKS) and len(model.K) == 1
+            and list(ckpt["resolution"]) == list(model.resolution))
+    if same:
+        return model
+    device = next(model.parameters()).device
+    extra = dict(bg_resolution=model.bg_resolution, bg_rank=model.bg_rank) if model.bg_radius > 0 else {}
+    new = type(model)(resolution=[int(r) for r in ckpt["resolution"]], degree=model.degree, bound=model.bound, cuda_ray=model.cuda_ray,
+                      density_scale=model.density_scale, min_near=model.min_near, density_thresh=model.density_thresh,
+                      bg_radius=model.bg_radius, **{k: [int(r) for r in ckpt[k]] for k in _CC_RANKS}, **extra).to(device)
+    new.train(model.training)
+    trainer.model = new
+    trainer.rebuild_optimizer()
+    return new
 
 
 def _after_weights_changed(trainer):

@@ -265,6 +265,20 @@ class NeRFRenderer(nn.Module):
                 rgbs = self.map_colors(mxyzs, mdirs, rgbs, mmask)
             if self.density_scale != 1:  # (x1 is the identity: skip the pass over [M])
                 sigmas = self.density_scale * sigmas
+            if sigmas.dim() == 2:
+                # CCNeRF's rank-residual training (tensoRF/network_cc.py): sigmas [K, M], rgbs [K, M, 3], the output of every
+                # prefix of groups.  One composite per level on the same samples, the background mixed per level; the fused
+                # composite-and-loss launches are not used here (nerf/trainer.py averages the criterion over the levels)
+                images, depths = [], []
+                for k in range(sigmas.shape[0]):
+                    weights_sum, depth, image = raymarching.composite_rays_train(sigmas[k], rgbs[k], deltas, rays, T_thresh)
+                    images.append((image + (1 - weights_sum).unsqueeze(-1) * bg_color).view(*prefix, 3))
+                    depths.append(depth.view(*prefix))
+                results["levels"] = sigmas.shape[0]  # (what nerf/trainer.py: render_loss recognises this rendering by)
+                results["weights_sum"] = weights_sum  # (the last level's)
+                results["depth"] = torch.stack(depths, dim=0)  # [K, *prefix]
+                results["image"] = torch.stack(images, dim=0)  # [K, *prefix, 3]
+                return results
             fused = kwargs.get("fused_loss")  # (nerf/trainer.py: the criterion and its gradient inside the compositing launch)
             # a background model's per-ray colours [N, 3] take the same launch in its per-ray form, which also hands out their
             # gradient (raymarching.composite_rays_train_loss_bg); so do the per-pixel random backgrounds of RGBA frames
@@ -336,6 +350,8 @@ class NeRFRenderer(nn.Module):
                 # device-side count the rows behind the last alive ray are skipped altogether (row_limit -> n_valid)
                 with s3d_hip.live_rows(deltas), s3d_hip.row_limit(rows, xyzs.shape[0]) if sync_free else _null_context():
                     sigmas, rgbs = self(mxyzs, mdirs)
+                if rgbs.dim() == 3:  # (CCNeRF's eval output [1, M, 3], tensoRF/network_cc.py: the same rows)
+                    rgbs = rgbs.reshape(-1, 3)
                 if self.density_scale != 1:
                     sigmas = self.density_scale * sigmas
                 rgbs = self.map_colors(mxyzs, mdirs, rgbs, mmask)

@@ -87,12 +87,13 @@ def rgba_targets(images, random_bg=True, generator=None, seed=None, ctl=None):
     return rgb * a + bg * (1 - a), bg
 
 
-def update_error_map(out, gt_rgb, error_map, gt_depth=None, depth_weight=1.0):
+def update_error_map(out, gt_rgb, error_map, gt_depth=None, depth_weight=1.0, per_ray_error=None):
     """nerf/utils.py:506-528: fold the step's per-ray error into the error map as 0.1 old + 0.9 err.  `error_map` =
     (map [n, 128*128], index [B], inds_coarse [B, N]); err = mean_c((pred - gt)^2) (+ depth_weight * the batch's mean L1 depth
     error, added to every ray as `loss += criterion_depth(...)` does).  A renderer output that defers its background (the GPU's
     native route) is folded in by one launch of s3d_error_map_update, which composites the background itself; otherwise the
-    reference's gather / scatter sequence runs."""
+    reference's gather / scatter sequence runs.  `per_ray_error`: the error itself, where the caller has formed it (the mean over
+    the levels of a rank-residual rendering)."""
     emap, index, inds = error_map
     index = torch.as_tensor(index, dtype=torch.int64, device=emap.device).reshape(-1)
     inds = inds.to(emap.device).reshape(index.numel(), -1)
@@ -117,7 +118,10 @@ def update_error_map(out, gt_rgb, error_map, gt_depth=None, depth_weight=1.0):
         bg = bg.view(pred.shape) if torch.is_tensor(bg) else (bg if not isinstance(bg, (tuple, list)) else torch.tensor(bg, device=pred.device))
         pred = pred + (1 - out["weights_sum"]).unsqueeze(-1) * bg
     with torch.no_grad():
-        error = F.mse_loss(pred.detach().float(), gt_rgb.detach().float().view(pred.shape), reduction="none").mean(-1).view(B, N)
+        if per_ray_error is not None:
+            error = per_ray_error.float().view(B, N)
+        else:
+            error = F.mse_loss(pred.detach().float(), gt_rgb.detach().float().view(pred.shape), reduction="none").mean(-1).view(B, N)
         if gt_depth is not None:
             error = error + depth_weight * F.l1_loss(depth.view(gt_depth.shape), gt_depth.float())
         em = emap[index]  # [B, 128*128] (advanced indexing: a copy)
@@ -130,6 +134,15 @@ def render_loss(out, gt_rgb, expected_grad=None, gt_depth=None, depth_weight=1.0
     """MSE between the rendered batch and the targets (+ Seal-3D's L1 depth term when `gt_depth` is given); uses the fused
     kernel when the renderer deferred the background (`expected_grad`: see _BgMse.forward).  `error_map`: (map, index,
     inds_coarse) of an error-map batch — the step's per-ray errors are folded into the map (update_error_map)."""
+    if "levels" in out:
+        # CCNeRF's rank-residual training (nerf/renderer.py marks it): image [K, ..., 3], one rendering per prefix of groups.  The per-ray criterion
+        # [K, ...] is averaged over the levels before the error-map update and the final mean (nerf/utils.py:502-530)
+        if gt_depth is not None:
+            raise NotImplementedError("render_loss: a depth target with a rank-residual (CCNeRF) rendering")
+        per_ray = F.mse_loss(out["image"], gt_rgb.unsqueeze(0).expand_as(out["image"]), reduction="none").mean(-1).mean(0)
+        if error_map is not None:
+            update_error_map(out, gt_rgb, error_map, per_ray_error=per_ray.detach())
+        return per_ray.mean()
     if error_map is not None:
         update_error_map(out, gt_rgb, error_map, gt_depth, depth_weight)
     if "loss" in out:  # the renderer's compositing launch formed the criterion itself (Trainer._fused_loss -> render(fused_loss=...))

@@ -50,6 +50,7 @@ EXPORTS = [
     "s3d_vm_backward_stage_bytes", "s3d_vm_transpose_factors",
     "s3d_vm_features_backward", "s3d_vm_color_forward", "s3d_vm_color_backward",
     "s3d_cp_transpose_lines", "s3d_cp_features_forward", "s3d_cp_color_forward", "s3d_cp_features_backward", "s3d_cp_color_backward",
+    "s3d_cc_features_forward", "s3d_cc_color_forward", "s3d_cc_features_backward", "s3d_cc_color_backward",
     "s3d_composite_rays_train_loss_bg", "s3d_bg_targets_rays",
     "s3d_background_forward", "s3d_background_backward_workspace_size", "s3d_background_backward",
     "s3d_vm_background_forward", "s3d_vm_background_backward_workspace_size", "s3d_vm_background_backward",
@@ -1908,6 +1909,136 @@ class CpBackend:
                                            _u(n_bounds), (C.c_void_p * 3)(*[t.data_ptr() for t in g_lines]), _p(g_basis), _p(found_inf),
                                            CpBackend._shadows(shadows), _nv(n_valid), _stream()), "cp_color_backward")
         return g_lines, g_basis
+
+
+class _CcGroup(C.Structure):
+    _fields_ = [("line", C.c_void_p * 3), ("plane", C.c_void_p * 3), ("s_vec", C.c_void_p), ("s_mat", C.c_void_p),
+                ("rank_vec", C.c_uint32), ("rank_mat", C.c_uint32)]
+
+
+class _CcGroupGrad(C.Structure):
+    _fields_ = [("line", C.c_void_p * 3), ("plane", C.c_void_p * 3), ("s_vec", C.c_void_p), ("s_mat", C.c_void_p)]
+
+
+class CcBackend:
+    """csrc/tensorf_cc.hip — CCNeRF features (tensoRF/network_cc.py:128-250, :287-291 of the reference).  A group is the tuple
+    (lines, planes, s_vec, s_mat): three lines [1,R,D_i,1] + s_vec [rows, R] and / or three planes [1,R,H_i,W_i] + s_mat [rows, R];
+    an absent component is (None, None).  rows = 1 (degree 0: the density head) or 3 * degree^2 (colour, with directions)."""
+    MAX_GROUPS, TABLE, MAX_DEGREE = 8, 7168, 4
+
+    @staticmethod
+    def refusal(groups, degree):
+        """None, or why the kernels do not cover these groups (the network then takes the grid_sample route)"""
+        if degree > CcBackend.MAX_DEGREE:
+            return f"degree {degree} above {CcBackend.MAX_DEGREE}"
+        if not 1 <= len(groups) <= CcBackend.MAX_GROUPS:
+            return f"{len(groups)} groups (1 .. {CcBackend.MAX_GROUPS})"
+        rows = 3 * degree * degree if degree else 1
+        if all(s_vec is None and s_mat is None for _, _, s_vec, s_mat in groups):
+            return "no component in any group"
+        for lines, planes, s_vec, s_mat in groups:
+            rank = (0 if s_vec is None else s_vec.shape[1]) + (0 if s_mat is None else s_mat.shape[1])
+            if rank * rows > CcBackend.TABLE:
+                return f"a group of rank {rank} with {rows} rows above the {CcBackend.TABLE}-float table"
+            for t in list(lines or ()) + list(planes or ()) + [s for s in (s_vec, s_mat) if s is not None]:
+                if not t.is_cuda or t.dtype != torch.float32:
+                    return "factors must be fp32 GPU tensors"
+        return None
+
+    @staticmethod
+    def _groups(groups, resolution, degree, what):
+        why = CcBackend.refusal(groups, degree)
+        if why is not None:
+            raise RuntimeError(f"{what}: {why}")
+        rows = 3 * degree * degree if degree else 1
+        res = [int(r) for r in resolution]
+        arr = (_CcGroup * len(groups))()
+        for rec, (lines, planes, s_vec, s_mat) in zip(arr, groups):
+            if (lines is None) != (s_vec is None) or (planes is None) != (s_mat is None):
+                raise RuntimeError(f"{what}: a component is its three factors and its S")
+            if s_vec is not None:
+                rec.rank_vec = R = int(s_vec.shape[1])
+                for i, t in enumerate(lines):
+                    if tuple(t.shape) != (1, R, res[2 - i], 1) or not t.is_contiguous():
+                        raise RuntimeError(f"{what}: line {i} must be contiguous [1,{R},{res[2 - i]},1], got {tuple(t.shape)}")
+                    rec.line[i] = t.data_ptr()
+                if tuple(s_vec.shape) != (rows, R) or not s_vec.is_contiguous():
+                    raise RuntimeError(f"{what}: s_vec must be contiguous [{rows},{R}]")
+                rec.s_vec = s_vec.data_ptr()
+            if s_mat is not None:
+                rec.rank_mat = R = int(s_mat.shape[1])
+                for i, (m0, m1) in enumerate(((0, 1), (0, 2), (1, 2))):
+                    t = planes[i]
+                    if tuple(t.shape) != (1, R, res[m1], res[m0]) or not t.is_contiguous():
+                        raise RuntimeError(f"{what}: plane {i} must be contiguous [1,{R},{res[m1]},{res[m0]}], got {tuple(t.shape)}")
+                    rec.plane[i] = t.data_ptr()
+                if tuple(s_mat.shape) != (rows, R) or not s_mat.is_contiguous():
+                    raise RuntimeError(f"{what}: s_mat must be contiguous [{rows},{R}]")
+                rec.s_mat = s_mat.data_ptr()
+        return arr, (C.c_uint32 * 3)(*res)
+
+    @staticmethod
+    def _points(x, dirs, degree, what):
+        _need(x, torch.float32, "x")
+        if not x.is_contiguous() or x.dim() != 2 or x.shape[1] != 3:
+            raise RuntimeError(f"{what}: x must be contiguous [N,3]")
+        if (dirs is None) != (degree == 0):
+            raise RuntimeError(f"{what}: directions go with a degree of 1 .. {CcBackend.MAX_DEGREE}, none with degree 0")
+        if dirs is not None:
+            _need(dirs, torch.float32, "dirs")
+            if not dirs.is_contiguous() or dirs.shape != x.shape:
+                raise RuntimeError(f"{what}: dirs must be contiguous [N,3]")
+        return x.shape[0]
+
+    @staticmethod
+    def forward(x, dirs, groups, resolution, degree, residual, half, out, n_valid=None):
+        """out fp32 [K_out, N] (degree 0, dirs None) or [K_out, N, 3]; K_out = len(groups) if residual else 1"""
+        N = CcBackend._points(x, dirs, degree, "cc forward")
+        arr, res = CcBackend._groups(groups, resolution, degree, "cc forward")
+        _need(out, torch.float32, "out")
+        if not out.is_contiguous() or out.numel() != (len(groups) if residual else 1) * N * (3 if degree else 1):
+            raise RuntimeError("cc forward: out must be contiguous [K_out, N] / [K_out, N, 3]")
+        if degree == 0:
+            _check(lib().s3d_cc_features_forward(_p(x), _u(N), arr, _u(len(groups)), res, C.c_int(int(bool(residual))),
+                                                 C.c_int(int(bool(half))), _p(out), _nv(n_valid), _stream()), "cc_features_forward")
+        else:
+            _check(lib().s3d_cc_color_forward(_p(x), _p(dirs), _u(N), arr, _u(len(groups)), res, _u(degree), C.c_int(int(bool(residual))),
+                                              C.c_int(int(bool(half))), _p(out), _nv(n_valid), _stream()), "cc_color_forward")
+
+    @staticmethod
+    def backward(x, dirs, groups, resolution, degree, residual, half, grad, found_inf=None, n_valid=None):
+        """parameter gradients of forward from grad fp32 [K_out, N] / [K_out, N, 3]: a list shaped like `groups`"""
+        N = CcBackend._points(x, dirs, degree, "cc backward")
+        arr, res = CcBackend._groups(groups, resolution, degree, "cc backward")
+        _need(grad, torch.float32, "grad")
+        if not grad.is_contiguous() or grad.numel() != (len(groups) if residual else 1) * N * (3 if degree else 1):
+            raise RuntimeError("cc backward: grad must be contiguous [K_out, N] / [K_out, N, 3]")
+        if found_inf is not None:
+            _need(found_inf, torch.float32, "found_inf")
+        flat = [t for lines, planes, s_vec, s_mat in groups
+                for t in list(lines or ()) + list(planes or ()) + [s for s in (s_vec, s_mat) if s is not None]]
+        zeros, _ = _zeros_like_many(flat)
+        garr, out, it = (_CcGroupGrad * len(groups))(), [], iter(zeros)
+        for rec, (lines, planes, s_vec, s_mat) in zip(garr, groups):
+            gl = [next(it) for _ in lines] if lines is not None else None
+            gp = [next(it) for _ in planes] if planes is not None else None
+            gsv = next(it) if s_vec is not None else None
+            gsm = next(it) if s_mat is not None else None
+            for i in range(3):
+                rec.line[i] = gl[i].data_ptr() if gl is not None else None
+                rec.plane[i] = gp[i].data_ptr() if gp is not None else None
+            rec.s_vec = gsv.data_ptr() if gsv is not None else None
+            rec.s_mat = gsm.data_ptr() if gsm is not None else None
+            out.append((gl, gp, gsv, gsm))
+        if degree == 0:
+            _check(lib().s3d_cc_features_backward(_p(x), _u(N), arr, _u(len(groups)), res, C.c_int(int(bool(residual))),
+                                                  C.c_int(int(bool(half))), _p(grad), garr, _p(found_inf), _nv(n_valid), _stream()),
+                   "cc_features_backward")
+        else:
+            _check(lib().s3d_cc_color_backward(_p(x), _p(dirs), _u(N), arr, _u(len(groups)), res, _u(degree),
+                                               C.c_int(int(bool(residual))), C.c_int(int(bool(half))), _p(grad), garr, _p(found_inf),
+                                               _nv(n_valid), _stream()), "cc_color_backward")
+        return out
 
 
 class MeshBackend:

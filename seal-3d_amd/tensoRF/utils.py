@@ -82,6 +82,10 @@ class GraphedTrainer(TensoRFSteps, _GraphedTrainer):
     """the same step replayed from a HIP graph (nerf/trainer.py: GraphedTrainer); re-captured after every upsampling"""
 
     def __init__(self, model, num_rays, lr0=2e-2, lr1=1e-3, l1_reg_weight=1e-4, upsample_model_steps=(), upsample_resolutions=(), **kw):
+        if getattr(model, "rank_residual", False):
+            raise NotImplementedError("GraphedTrainer: the CCNeRF backbone's rank-residual step (one composite per level and the "
+                                      "criterion averaged over the levels, without the captured step's fused composite-and-loss "
+                                      "launch) is not captured; use tensoRF.utils.Trainer")
         self._init_tensorf(lr0, lr1, l1_reg_weight, upsample_model_steps, upsample_resolutions)
         # the static sample budget: since round 6 every kernel of this backbone's sample path takes the device-side row count
         # (s3d_hip.row_limit -> n_valid), so the padding costs nothing and the budget keeps the NGP trainer's 30 % of headroom over
