@@ -946,6 +946,53 @@ int s3d_mc_count(const float* u, uint32_t nx, uint32_t ny, uint32_t nz, float is
 int s3d_mc_emit(const float* u, uint32_t nx, uint32_t ny, uint32_t nz, float iso, const void* workspace, const float* bounds,
                 float* vertices, uint32_t V, int32_t* triangles, uint32_t T, s3d_stream_t stream);
 
+/* ------------------------------------------------------------------ D-NeRF glue (csrc/dnerf.hip; DESIGN.md "D-NeRF")
+ * The deformation backbone (dnerf/network.py:123-165 of the reference): deform = MLP_5x128([freq_10(x) | freq_6(t)])[:, :3],
+ * x' = x + deform, h = MLP_2x64([grid(x') | freq_10(x) | freq_6(t)]).  Two fp16 rows per sample, padded to what s3d_ffmlp_* take:
+ *   din [B, 80]  : columns 0..62 freq_10(x) in s3d_freq_encode_forward's column order, 63..75 freq_6(t), 76..79 zero
+ *   sin [B, 112] : columns 0..2L-1 the grid features (level l in 2l, 2l+1), 32..94 freq_10(x), 95..107 freq_6(t), 108..111 zero
+ * n_valid: the padded-batch convention above (rows at or behind round_up(*n_valid, 128) are neither read nor written).
+ *
+ * s3d_dnerf_encode_forward: din and columns 32..111 of sin from one launch.  x fp32 [B,3] (raw: the frequency encoder ignores
+ * `bound`); t a device pointer read at t[b * t_stride], t_stride 0 (one time for all rows) or 1.  Values: the fp32 values of
+ * s3d_freq_encode_forward rounded to binary16 once (the contract of s3d_freq_encode_pack_forward), i.e. bit for bit half() of that
+ * kernel's output.  Columns 0..31 of sin are not touched.  No backward: neither x (marcher output) nor t takes a gradient.
+ *
+ * s3d_dnerf_warp_grid_forward, one launch: xw [B,3] fp32 = x + float(dout[:, 0:3]) (dout: the deformation network's fp16 [B,16]
+ * output; one fp32 add), deform [B,3] fp32 = float(dout[:, 0:3]) (optional), the hash / tiled grid encoding (D = 3, C = 2, L <= 16;
+ * every table dtype, gridtype, align_corners and interpolation s3d_grid_encode_forward takes) of xw written as fp16 into columns
+ * 0..2L-1 of sin (an fp32 table's sums are rounded to binary16 once, an fp16 table's are stored as they are), dy_dx [B,L,3,2] in
+ * the table's dtype (optional, the layout s3d_grid_encode_backward reads).  Corner rows, weights and sums are
+ * s3d_grid_encode_forward's expressions: features and dy_dx equal that call's on xw bit for bit.  bound as there (> 0: raw
+ * coordinates, normalised in the kernel; here WITH dy_dx, which stays the Jacobian w.r.t. the normalised coordinate).
+ * reg_sum (optional): one fp32 device word = sum of |deform| over the live rows (all B without n_valid, else the rows the
+ * convention above keeps: *n_valid rounded up to 128) and the three columns, summed in a fixed order (lanes by a shuffle tree,
+ * waves and workgroups in index order through `workspace`, s3d_dnerf_warp_grid_workspace_size(B) bytes, 16-byte aligned) without
+ * float atomics: two runs give the same bits.
+ * DIVERGENCE from the reference's regulariser (dnerf/utils.py:117-119 averages |deform| over every row the marcher returned,
+ * the zero-padded rows of a budgeted buffer at x = 0 included): only the live rows enter; equal whenever the marcher trims its
+ * buffers, which it does to the same multiple of 128.
+ *
+ * s3d_dnerf_split_grad: columns 0..2L-1 of the density network's input gradient (fp16 [B,112]) as the level-major [L][B][2]
+ * tensor in the table's dtype that s3d_grid_encode_backward takes as `grad` (an exact transposition; fp16 -> fp32 is exact).
+ *
+ * s3d_dnerf_warp_backward: grad_dout fp16 [B,16], columns 0..2 = half(fmaf(coef, sign(deform), float(grad_xw) * grad_scale)),
+ * columns 3..15 zero.  grad_xw [B,3] in `dtype`: s3d_grid_encode_backward's grad_inputs; grad_scale: 1 / (2 bound) when the
+ * lookup normalised in the kernel (a power of two: exact), else 1.  coef: device float, the upstream gradient of reg_sum (NULL:
+ * no regulariser); sign(0) = 0 as torch's abs backward gives. */
+int s3d_dnerf_encode_forward(const float* x, const float* t, uint32_t t_stride, uint32_t B, uint16_t* din, uint16_t* sin,
+                             const int32_t* n_valid, s3d_stream_t stream);
+size_t s3d_dnerf_warp_grid_workspace_size(uint32_t B);
+int s3d_dnerf_warp_grid_forward(const float* x, const uint16_t* dout, const void* embeddings, const int32_t* offsets,
+                                uint32_t B, uint32_t L, float S, uint32_t H, uint32_t gridtype, int align_corners,
+                                uint32_t interp, int dtype, float bound, uint16_t* sin, float* xw, float* deform, void* dy_dx,
+                                float* reg_sum, void* workspace, size_t workspace_bytes, const int32_t* n_valid,
+                                s3d_stream_t stream);
+int s3d_dnerf_split_grad(const uint16_t* grad_sin, uint32_t B, uint32_t L, int dtype, void* grad_levels,
+                         const int32_t* n_valid, s3d_stream_t stream);
+int s3d_dnerf_warp_backward(const void* grad_xw, int dtype, float grad_scale, const float* deform, const float* coef,
+                            uint32_t B, uint16_t* grad_dout, const int32_t* n_valid, s3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,8 @@ def save_checkpoint(trainer, workspace, name="ngp", full=False, best=False, remo
     if model.cuda_ray:
         state["mean_count"] = model.mean_count
         state["mean_density"] = model.mean_density
+    if hasattr(model, "time_size"):
+        state["time_size"] = int(model.time_size)  # D-NeRF: the time axis of density_grid / density_bitfield / times
     if hasattr(model, "upsample_model") and hasattr(model, "resolution"):
         state["resolution"] = list(model.resolution)  # TensoRF: factor resolution at save time (tensoRF/utils.py:236)
     if getattr(model, "rank_residual", False):  # CCNeRF: the model's structure (tensoRF/utils.py:251-256)
@@ -86,6 +88,7 @@ def load_checkpoint(trainer, checkpoint, model_only=False, lr_scheduler=None, em
     model = trainer.model
     device = next(model.parameters()).device
     ckpt = torch.load(checkpoint, map_location=device, weights_only=False)
+    _check_time_size(model, ckpt)
     if "model" not in ckpt:
         model.load_state_dict(ckpt)
         _after_weights_changed(trainer)
@@ -119,6 +122,19 @@ def load_checkpoint(trainer, checkpoint, model_only=False, lr_scheduler=None, em
     if trainer.scaler is not None and "scaler" in ckpt and ckpt["scaler"]:
         trainer.scaler.load_state_dict(ckpt["scaler"])
     return list(missing), list(unexpected)
+
+
+def _check_time_size(model, ckpt):
+    """D-NeRF: the occupancy buffers carry a time axis of `time_size` slots; a file of another size does not fit the model"""
+    if not hasattr(model, "time_size"):
+        return
+    sd = ckpt.get("model", ckpt)
+    have = ckpt.get("time_size")
+    if have is None and torch.is_tensor(sd.get("times")):
+        have = sd["times"].shape[0]
+    if have is not None and int(have) != int(model.time_size):
+        raise ValueError(f"checkpoint: written with time_size={int(have)}, the model has time_size={int(model.time_size)}; "
+                         "create the model with the checkpoint's time_size")
 
 
 _CC_RANKS = ("rank_vec_density", "rank_mat_density", "rank_vec", "rank_mat")

@@ -56,6 +56,8 @@ EXPORTS = [
     "s3d_vm_background_forward", "s3d_vm_background_backward_workspace_size", "s3d_vm_background_backward",
     "s3d_sample_train_rays", "s3d_error_map_update", "s3d_sample_train_rays_rgba", "s3d_rgba_targets",
     "s3d_mc_workspace_bytes", "s3d_mc_count", "s3d_mc_emit",
+    "s3d_dnerf_encode_forward", "s3d_dnerf_warp_grid_workspace_size", "s3d_dnerf_warp_grid_forward", "s3d_dnerf_split_grad",
+    "s3d_dnerf_warp_backward",
 ]
 
 
@@ -86,7 +88,8 @@ def lib():
                      "s3d_grid_encode_backward_control_size", "s3d_l1_pair_workspace_size",
                      "s3d_sweep_update_workspace_size", "s3d_sweep_draw_native_workspace_size", "s3d_vm_backward_bins_workspace_size", "s3d_vm_backward_stage_bytes",
                      "s3d_weighted_abs_sum_workspace_size", "s3d_background_backward_workspace_size",
-                     "s3d_vm_background_backward_workspace_size", "s3d_mc_workspace_bytes"):
+                     "s3d_vm_background_backward_workspace_size", "s3d_mc_workspace_bytes",
+                     "s3d_dnerf_warp_grid_workspace_size"):
             getattr(l, name).restype = C.c_size_t
         l.s3d_vm_backward_max_bins.restype = C.c_uint32
         l.s3d_grid_level_scales.restype = None
@@ -2073,3 +2076,79 @@ class MeshBackend:
         _check(lib().s3d_mc_emit(_p(u), _u(nx), _u(ny), _u(nz), _f(iso), _p(ws), _p(bounds), _p(vertices), _u(V), _p(triangles), _u(T), _stream()),
                "mc_emit")
         return vertices, triangles
+
+
+class DnerfBackend:
+    """D-NeRF glue (csrc/dnerf.hip): the two fp16 input rows din [B, 80] / sin [B, 112] of the deformation and the density
+    network, the warp + grid lookup, and the two backward steps around the grid backward (include/seal3d_hip.h)."""
+
+    DIN, SIN, GRID_COLS = 80, 112, 32
+
+    @staticmethod
+    def _rows(din, sin, B):
+        for name, t, cols in (("din", din, DnerfBackend.DIN), ("sin", sin, DnerfBackend.SIN)):
+            if t is None:
+                continue
+            _need(t, torch.float16, name)
+            if tuple(t.shape) != (B, cols) or not t.is_contiguous():
+                raise RuntimeError(f"{name} must be a contiguous fp16 [{B}, {cols}] tensor, got {tuple(t.shape)}")
+
+    @staticmethod
+    def encode_forward(x, t, din, sin, n_valid=None):
+        """din and sin[:, 32:] from x fp32 [B, 3] and t fp32 (one element: one time for all rows; B elements: one per row)"""
+        _need(x, torch.float32, "x"); _need(t, torch.float32, "t")
+        B = x.shape[0]
+        if x.dim() != 2 or x.shape[1] != 3 or t.numel() not in (1, B):
+            raise RuntimeError("encode_forward: x [B, 3], t with 1 or B elements")
+        DnerfBackend._rows(din, sin, B)
+        # (t of one element is read with stride 0 whatever B is: a [1, 1] time serves a batch of one row as well)
+        _check(lib().s3d_dnerf_encode_forward(_p(x), _p(t), _u(0 if t.numel() == 1 else 1), _u(B), _p(din), _p(sin), _nv(n_valid),
+                                              _stream()), "dnerf_encode_forward")
+
+    @staticmethod
+    def warp_grid_forward(x, dout, embeddings, offsets, S, H, gridtype, align_corners, interp, bound, sin, xw, deform=None,
+                          dy_dx=None, reg_sum=None, n_valid=None):
+        _need(x, torch.float32, "x"); _need(dout, torch.float16, "dout"); _need(offsets, torch.int32, "offsets")
+        _need(xw, torch.float32, "xw")
+        B, L = x.shape[0], offsets.shape[0] - 1
+        if tuple(dout.shape) != (B, 16) or tuple(xw.shape) != (B, 3) or embeddings.dim() != 2 or embeddings.shape[1] != 2:
+            raise RuntimeError("warp_grid_forward: dout [B, 16], xw [B, 3], a table of two features per row")
+        DnerfBackend._rows(None, sin, B)
+        if deform is not None:
+            _need(deform, torch.float32, "deform")
+            if tuple(deform.shape) != (B, 3):
+                raise RuntimeError("warp_grid_forward: deform must be [B, 3]")
+        if dy_dx is not None and (dy_dx.dtype != embeddings.dtype or dy_dx.numel() != B * L * 6):
+            raise RuntimeError("warp_grid_forward: dy_dx must hold [B, L, 3, 2] values of the table's dtype")
+        ws, nb = None, 0
+        if reg_sum is not None:
+            _need(reg_sum, torch.float32, "reg_sum")
+            nb = int(lib().s3d_dnerf_warp_grid_workspace_size(_u(B)))
+            ws = _ws.get(nb, x.device)
+        _check(lib().s3d_dnerf_warp_grid_forward(_p(x), _p(dout), _p(embeddings), _p(offsets), _u(B), _u(L), _f(S), _u(H), _u(gridtype),
+                                                 C.c_int(int(align_corners)), _u(interp), C.c_int(_dt(embeddings)), _f(bound), _p(sin),
+                                                 _p(xw), _p(deform), _p(dy_dx), _p(reg_sum), _p(ws), C.c_size_t(nb), _nv(n_valid),
+                                                 _stream()), "dnerf_warp_grid_forward")
+
+    @staticmethod
+    def split_grad(grad_sin, grad_levels, n_valid=None):
+        """grad_levels [L, B, 2] (fp16 or fp32) = the grid columns of grad_sin fp16 [B, 112], level-major"""
+        B = grad_sin.shape[0]
+        DnerfBackend._rows(None, grad_sin, B)
+        if grad_levels.dim() != 3 or grad_levels.shape[1] != B or grad_levels.shape[2] != 2 or grad_levels.shape[0] > 16:
+            raise RuntimeError("split_grad: grad_levels must be [L <= 16, B, 2]")
+        _check(lib().s3d_dnerf_split_grad(_p(grad_sin), _u(B), _u(grad_levels.shape[0]), C.c_int(_dt(grad_levels)), _p(grad_levels),
+                                          _nv(n_valid), _stream()), "dnerf_split_grad")
+
+    @staticmethod
+    def warp_backward(grad_xw, grad_scale, deform, coef, grad_dout, n_valid=None):
+        _need(grad_dout, torch.float16, "grad_dout")
+        B = grad_dout.shape[0]
+        if tuple(grad_dout.shape) != (B, 16) or tuple(grad_xw.shape) != (B, 3):
+            raise RuntimeError("warp_backward: grad_xw [B, 3], grad_dout [B, 16]")
+        if coef is not None:
+            _need(coef, torch.float32, "coef"); _need(deform, torch.float32, "deform")
+            if tuple(deform.shape) != (B, 3):
+                raise RuntimeError("warp_backward: deform must be [B, 3]")
+        _check(lib().s3d_dnerf_warp_backward(_p(grad_xw), C.c_int(_dt(grad_xw)), _f(grad_scale), _p(deform if coef is not None else None),
+                                             _p(coef), _u(B), _p(grad_dout), _nv(n_valid), _stream()), "dnerf_warp_backward")
