@@ -993,6 +993,59 @@ int s3d_dnerf_split_grad(const uint16_t* grad_sin, uint32_t B, uint32_t L, int d
 int s3d_dnerf_warp_backward(const void* grad_xw, int dtype, float grad_scale, const float* deform, const float* coef,
                             uint32_t B, uint16_t* grad_dout, const int32_t* n_valid, s3d_stream_t stream);
 
+/* ------------------------------------------------------------------ sampling without the occupancy grid (csrc/hiersample.hip;
+ * DESIGN.md "The sampling path without the grid")
+ * `NeRFRenderer.run` of the reference (nerf/renderer.py:125-253) and `sample_pdf` (:12-46).  S = num_steps >= 3, U = upsample_steps,
+ * K = S + U <= s3d_hier_max_samples() (2,048): above it every entry point returns S3D_ERR_UNSUPPORTED and the caller keeps its own
+ * route.  All tensors fp32 and row-major unless noted; rays_o, rays_d [N,3]; aabb[6] device memory; one wave per ray, no workspace.
+ * The merged row exists in depth order only as (z_sorted, order); sigma_cat, rgbs, weights, mask and the gradients are in the
+ * CONCATENATED order [coarse (S) | fine (U)] in which the networks see the samples: sorted slot p belongs to column order[p].
+ * order == NULL is the identity and is accepted only with U == 0.  z, new_z and the points take no gradient (:182 detaches them).
+ *
+ * s3d_hier_coarse_samples — :141-159.  nears, fars [N] by the expressions of s3d_near_far_from_aabb; z [N,S] = near + (far - near) *
+ * lin_i with lin = torch.linspace(0, 1, S) formed as torch forms it (step = 1 / (S - 1); fma(step, i, 0) for i < S / 2, else
+ * fma(-step, S - 1 - i, 1): torch's kernels contract these two), + (noise - 0.5) * sample_dist where noise [N,S] (the host's
+ * torch.rand values) is given; xyz [N,S,3] = min(max(o + d z, aabb_lo), aabb_hi).  Every other operation is rounded on its own, as
+ * the torch op sequence rounds it: z, nears, fars and xyz equal the torch ops on the device bit for bit.  sample_dist, here and
+ * below, is (far - near) * fl(1 / S): how torch's device kernel divides by a host scalar.
+ *
+ * s3d_hier_upsample — :174-186 and sample_pdf :12-46, U >= 1.  Per ray: delta_i = z_{i+1} - z_i (the last (far - near) / S),
+ * alpha_i = 1 - exp(-delta_i density_scale sigma_i), T_i = prod_{k<i} (1 - alpha_k + 1e-15), w_i = alpha_i T_i, bins z_mid_i =
+ * z_i + delta_i / 2 (S - 1 of them), pdf = (w[1..S-2] + 1e-5) / sum, cdf = [0 | running sum of pdf]; for each u: the first cdf entry
+ * above u (searchsorted right=True), its neighbour below, denom < 1e-5 -> 1, linear interpolation between the two bins.  u [N,U]
+ * (training: the host's values) or NULL: torch.linspace(0.5 / U, 1 - 0.5 / U, U).  Outputs new_z [N,U], new_xyz [N,U,3] (clamped
+ * like xyz), z_sorted [N,K] = sort(cat(z, new_z)) and order [N,K] int32 with cat(z, new_z)[order] == z_sorted exactly; equal depths
+ * in column order.  sigma [N,S] is read, not differentiated (:174 runs under no_grad).
+ *
+ * s3d_hier_weights — :205-215.  weights [N,K] = alpha T of the merged row (delta from z_sorted, the last (far - near) / S; sigma of
+ * sorted slot p = sigma_cat[order[p]]) and mask [N,K] (one byte per element: weights > 1e-4), both in concatenated order.
+ *
+ * s3d_hier_composite_forward — :222-229.  weights_sum [N] = sum w, depth [N] = sum w clamp((z - near) / (far - near), 0, 1),
+ * image [N,3] = sum w rgb (rgbs [N,K,3]; the background is the caller's).  A ray that misses the box has near = far = FLT_MAX and
+ * the reference's depth is 0 / 0 = NaN there: the clamp keeps a NaN (torch.clamp does, fminf / fmaxf would not).
+ *
+ * s3d_hier_composite_backward — the backward of s3d_hier_weights + s3d_hier_composite_forward w.r.t. sigma_cat and rgbs.  With
+ * s_p = 1 - alpha_p + 1e-15 and G_p = grad_image . rgb_p + grad_weights_sum + grad_depth znorm_p (sorted slots):
+ *   grad_sigma_p = delta_p density_scale exp(-delta_p density_scale sigma_p) (G_p T_p - (sum_{q>p} G_q w_q) / s_p)
+ *   grad_rgb_p   = w_p grad_image
+ * written at column order[p].  grad_image [N,3], grad_weights_sum [N], grad_depth [N]: each may be NULL for zero (a NULL
+ * grad_depth also keeps the NaN of a missing ray's depth out of the gradients, as autograd does when depth is not used). */
+int s3d_hier_max_samples(void);
+int s3d_hier_coarse_samples(const float* rays_o, const float* rays_d, const float* aabb, uint32_t N, float min_near, uint32_t S,
+                            const float* noise, float* nears, float* fars, float* z, float* xyz, s3d_stream_t stream);
+int s3d_hier_upsample(const float* z, const float* sigma, const float* nears, const float* fars, float density_scale,
+                      const float* u, const float* rays_o, const float* rays_d, const float* aabb, uint32_t N, uint32_t S,
+                      uint32_t U, float* new_z, float* new_xyz, float* z_sorted, int32_t* order, s3d_stream_t stream);
+int s3d_hier_weights(const float* z_sorted, const int32_t* order, const float* sigma_cat, const float* nears, const float* fars,
+                     float density_scale, uint32_t N, uint32_t S, uint32_t U, float* weights, uint8_t* mask, s3d_stream_t stream);
+int s3d_hier_composite_forward(const float* weights, const float* rgbs, const float* z_sorted, const int32_t* order,
+                               const float* nears, const float* fars, uint32_t N, uint32_t S, uint32_t U, float* weights_sum,
+                               float* depth, float* image, s3d_stream_t stream);
+int s3d_hier_composite_backward(const float* grad_image, const float* grad_weights_sum, const float* grad_depth,
+                                const float* sigma_cat, const float* rgbs, const float* z_sorted, const int32_t* order,
+                                const float* nears, const float* fars, float density_scale, uint32_t N, uint32_t S, uint32_t U,
+                                float* grad_sigma_cat, float* grad_rgbs, s3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -90,6 +90,32 @@ inline uint32_t stream_grid(uint64_t work, uint32_t block) {
 
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(hi, fmaxf(lo, x)); }
 
+// raymarching.cu:near_far_from_aabb — slab test against the box, near clamped to min_near; a miss gives FLT_MAX twice
+__device__ __forceinline__ void near_far_of(const float* __restrict__ rays_o, const float* __restrict__ rays_d, uint32_t n,
+                                            const float (&a)[6], float min_near, float& near_out, float& far_out) {
+    const float ox = rays_o[n * 3], oy = rays_o[n * 3 + 1], oz = rays_o[n * 3 + 2];
+    const float rdx = 1 / rays_d[n * 3], rdy = 1 / rays_d[n * 3 + 1], rdz = 1 / rays_d[n * 3 + 2];
+    float near = (a[0] - ox) * rdx, far = (a[3] - ox) * rdx;
+    if (near > far) { float t = near; near = far; far = t; }
+    float near_y = (a[1] - oy) * rdy, far_y = (a[4] - oy) * rdy;
+    if (near_y > far_y) { float t = near_y; near_y = far_y; far_y = t; }
+    bool miss = (near > far_y || near_y > far);
+    if (!miss) {
+        if (near_y > near) near = near_y;
+        if (far_y < far) far = far_y;
+        float near_z = (a[2] - oz) * rdz, far_z = (a[5] - oz) * rdz;
+        if (near_z > far_z) { float t = near_z; near_z = far_z; far_z = t; }
+        miss = (near > far_z || near_z > far);
+        if (!miss) {
+            if (near_z > near) near = near_z;
+            if (far_z < far) far = far_z;
+            if (near < min_near) near = min_near;
+        }
+    }
+    near_out = miss ? 3.402823466e+38f : near;
+    far_out = miss ? 3.402823466e+38f : far;
+}
+
 // Padded sample batches (`n_valid` of seal3d_hip.h): the ray marcher leaves the number of samples it produced in device
 // memory, the buffers behind it have a static extent B.  Rows [round_up(*n_valid, 128), B) are absent for every kernel
 // that takes the pointer — not read, not written — so the work follows the samples while launch geometry and strides

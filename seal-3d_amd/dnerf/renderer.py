@@ -96,7 +96,7 @@ class NeRFRenderer(_NgpRenderer):
         color = self.color
 
         def color_keeping_deform(x, d, mask=None, **dens):
-            kept["deform"] = dens.get("deform")  # (the base method hands over every density output, merged and depth-sorted)
+            kept["deform"] = dens.get("deform")  # (the base method hands over every density output of the merged row: depth-sorted on its torch route, [coarse | fine] on its native one)
             return color(x, d, mask=mask, **dens)
         self.color = color_keeping_deform  # (an instance attribute in front of the class's method, for the base method's call)
         try:

@@ -80,6 +80,36 @@ class _SweepState:
         return (type(None), ())
 
 
+class _HierComposite(torch.autograd.Function):
+    """weights_sum, depth and image of `NeRFRenderer._run_native` (s3d_hier_composite_forward on the weights that
+    s3d_hier_weights made) with the hand-derived backward to sigma and rgbs (s3d_hier_composite_backward); rows in the
+    concatenated order, `order` None for the identity"""
+
+    @staticmethod
+    def forward(ctx, sigma, rgbs, weights, z_sorted, order, nears, fars, density_scale, num_steps):
+        N = sigma.shape[0]
+        weights_sum, depth, image = sigma.new_empty(N), sigma.new_empty(N), sigma.new_empty(N, 3)
+        s3d_hip.HierBackend.composite_forward(weights, rgbs, z_sorted, order, nears, fars, num_steps, weights_sum, depth, image)
+        ctx.save_for_backward(sigma, rgbs, z_sorted, order, nears, fars)
+        ctx.density_scale, ctx.num_steps = density_scale, num_steps
+        # an output the loss does not use sends None, not zeros: the depth of a ray that misses the box is NaN, and 0 * NaN
+        # would reach every gradient of that ray — autograd over the torch route never visits an unused depth either
+        ctx.set_materialize_grads(False)
+        return weights_sum, depth, image
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_weights_sum, grad_depth, grad_image):
+        sigma, rgbs, z_sorted, order, nears, fars = ctx.saved_tensors
+        grad_sigma, grad_rgbs = torch.empty_like(sigma), torch.empty_like(rgbs)
+
+        def dense(g):
+            return None if g is None else g.float().contiguous()
+        s3d_hip.HierBackend.composite_backward(dense(grad_image), dense(grad_weights_sum), dense(grad_depth), sigma, rgbs, z_sorted,
+                                               order, nears, fars, ctx.density_scale, ctx.num_steps, grad_sigma, grad_rgbs)
+        return grad_sigma, grad_rgbs, None, None, None, None, None, None, None
+
+
 class NeRFRenderer(nn.Module):
     # mean_density / mean_count: plain host numbers, except between a native occupancy update and the first read after it —
     # then the update's record is still on its way from the device and the read waits for its event (finish_extra_state)
@@ -603,12 +633,73 @@ class NeRFRenderer(nn.Module):
             self.mean_count = int(count_sum / total_step)
         self.local_step = 0
 
+    # `native_sampling = False` on a model (or the class) keeps `run` on the torch op sequence for GPU tensors too: the A/B
+    # handle of tests and tools/bench_hier_sampling.py.  `last_sampling_route` names the route the last `run` took.
+    native_sampling = True
+    last_sampling_route = None
+
     def run(self, rays_o, rays_d, num_steps=128, upsample_steps=128, bg_color=None, perturb=False, **kwargs):
         """The sampling path without the occupancy grid (`cuda_ray` off; nerf/renderer.py:125-253): `num_steps` stratified
         samples between the ray's near and far, `upsample_steps` more drawn from the coarse weights (sample_pdf), alpha
-        compositing with torch ops, colours evaluated only where the weight exceeds 1e-4.  BASELINE configs[0] renders its
-        64x64 plumbing frame through this path (`num_steps=512`, main_SealNeRF.py:47).  The only native op is
-        near_far_from_aabb (the reference's `run` calls the extension for it too, :141)."""
+        compositing, colours evaluated only where the weight exceeds 1e-4.  BASELINE configs[0] renders its 64x64 plumbing
+        frame through this path (`num_steps=512`, main_SealNeRF.py:47).  GPU tensors take the HIP kernels of
+        csrc/hiersample.hip (`_run_native`) whenever they cover the shape (num_steps >= 3, num_steps + upsample_steps up to
+        HierBackend.max_samples()); CPU tensors, larger rows and `native_sampling = False` take the torch op sequence."""
+        native = (self.native_sampling and rays_o.is_cuda and rays_o.dtype == torch.float32 and rays_d.dtype == torch.float32
+                  and s3d_hip.HierBackend.supports(num_steps, upsample_steps))
+        self.last_sampling_route = "native" if native else "torch"
+        route = self._run_native if native else self._run_torch
+        return route(rays_o, rays_d, num_steps=num_steps, upsample_steps=upsample_steps, bg_color=bg_color, perturb=perturb, **kwargs)
+
+    def _run_native(self, rays_o, rays_d, num_steps=128, upsample_steps=128, bg_color=None, perturb=False, **kwargs):
+        """`run` on the kernels of csrc/hiersample.hip: the samples of a ray stay in the concatenated [coarse | fine] order in
+        which the networks produce them; only their depths are sorted, as (z_sorted, order) — no sort, gather, cumprod or
+        searchsorted launch and no reordering copy of `xyzs` or of a density output.  Same random draws in the same order as
+        `_run_torch` (the jitter on the device, the pdf's uniforms on the host)."""
+        H = s3d_hip.HierBackend
+        prefix = rays_o.shape[:-1]
+        rays_o = rays_o.contiguous().view(-1, 3)
+        rays_d = rays_d.contiguous().view(-1, 3)
+        N, device, S, U = rays_o.shape[0], rays_o.device, num_steps, upsample_steps
+        K = S + U
+        aabb = (self.aabb_train if self.training else self.aabb_infer).float().contiguous()
+
+        def new(*shape, dtype=torch.float32):
+            return torch.empty(shape, dtype=dtype, device=device)
+
+        noise = torch.rand((N, S), device=device) if perturb else None
+        nears, fars, z_vals, xyzs = new(N), new(N), new(N, S), new(N, S, 3)
+        H.coarse_samples(rays_o, rays_d, aabb, self.min_near, S, nears, fars, z_vals, xyzs, noise)
+        dens = {k: v.view(N, S, -1) for k, v in self.density(xyzs.view(-1, 3)).items()}
+        order = None
+        if U > 0:
+            u = None if not self.training else torch.rand([N, U]).to(device)
+            new_z, new_xyzs, z_sorted, order = new(N, U), new(N, U, 3), new(N, K), new(N, K, dtype=torch.int32)
+            H.upsample(z_vals, dens["sigma"].detach().reshape(N, S).float().contiguous(), nears, fars, self.density_scale, u,
+                       rays_o, rays_d, aabb, U, new_z, new_xyzs, z_sorted, order)
+            new_dens = {k: v.view(N, U, -1) for k, v in self.density(new_xyzs.view(-1, 3)).items()}
+            z_vals = z_sorted
+            xyzs = torch.cat([xyzs, new_xyzs], dim=1)
+            dens = {k: torch.cat([dens[k], new_dens[k]], dim=1) for k in dens}
+        sigma = dens["sigma"].reshape(N, K).float().contiguous()
+        weights, mask = new(N, K), new(N, K, dtype=torch.bool)
+        H.weights(z_vals, order, sigma.detach(), nears, fars, self.density_scale, S, weights, mask)
+        dirs = rays_d.view(-1, 1, 3).expand_as(xyzs)
+        dens = {k: v.reshape(-1, v.shape[-1]) for k, v in dens.items()}
+        rgbs = self.color(xyzs.reshape(-1, 3), dirs.reshape(-1, 3), mask=mask.reshape(-1), **dens).view(N, -1, 3)
+        weights_sum, depth, image = _HierComposite.apply(sigma, rgbs.float().contiguous(), weights, z_vals, order, nears, fars,
+                                                         float(self.density_scale), S)
+        if self.bg_radius > 0:
+            sph = raymarching.sph_from_ray(rays_o, rays_d, self.bg_radius)
+            bg_color = self.background(sph, rays_d.reshape(-1, 3))
+        elif bg_color is None:
+            bg_color = 1
+        image = image + (1 - weights_sum).unsqueeze(-1) * bg_color
+        return {"depth": depth.view(*prefix), "image": image.view(*prefix, 3), "weights_sum": weights_sum}
+
+    def _run_torch(self, rays_o, rays_d, num_steps=128, upsample_steps=128, bg_color=None, perturb=False, **kwargs):
+        """`run` as the reference's torch op sequence (nerf/renderer.py:125-253); the only native op is near_far_from_aabb (the
+        reference's `run` calls the extension for it too, :141).  CPU tensors always come here."""
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3)
         rays_d = rays_d.contiguous().view(-1, 3)

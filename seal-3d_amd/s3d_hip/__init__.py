@@ -58,6 +58,8 @@ EXPORTS = [
     "s3d_mc_workspace_bytes", "s3d_mc_count", "s3d_mc_emit",
     "s3d_dnerf_encode_forward", "s3d_dnerf_warp_grid_workspace_size", "s3d_dnerf_warp_grid_forward", "s3d_dnerf_split_grad",
     "s3d_dnerf_warp_backward",
+    "s3d_hier_max_samples", "s3d_hier_coarse_samples", "s3d_hier_upsample", "s3d_hier_weights", "s3d_hier_composite_forward",
+    "s3d_hier_composite_backward",
 ]
 
 
@@ -2152,3 +2154,104 @@ class DnerfBackend:
                 raise RuntimeError("warp_backward: deform must be [B, 3]")
         _check(lib().s3d_dnerf_warp_backward(_p(grad_xw), C.c_int(_dt(grad_xw)), _f(grad_scale), _p(deform if coef is not None else None),
                                              _p(coef), _u(B), _p(grad_dout), _nv(n_valid), _stream()), "dnerf_warp_backward")
+
+
+class HierBackend:
+    """The sampling path without the occupancy grid (csrc/hiersample.hip; include/seal3d_hip.h): stratified samples, inverse-CDF
+    upsampling with the depth merge, weights, compositing and its backward.  S = num_steps, U = upsample_steps, K = S + U; rows
+    of sigma, rgbs, weights, mask and the gradients are in the concatenated [coarse | fine] order, `order` maps depth-sorted
+    slots to those columns (None: the identity, only with U = 0).  Every tensor fp32 unless noted; outputs are the caller's."""
+
+    @staticmethod
+    def max_samples():
+        """the largest K = S + U the kernels take; above it every method raises and the renderer keeps its torch route"""
+        return int(lib().s3d_hier_max_samples())
+
+    @staticmethod
+    def supports(S, U):
+        return S >= 3 and U >= 0 and S + U <= HierBackend.max_samples()
+
+    @staticmethod
+    def _shape(who, S, U):
+        if S < 3 or U < 0:
+            raise RuntimeError(f"{who}: num_steps >= 3 and upsample_steps >= 0, got {S} and {U}")
+        if S + U > HierBackend.max_samples():
+            raise RuntimeError(f"{who}: num_steps + upsample_steps = {S + U} exceeds the cap of {HierBackend.max_samples()} samples per ray")
+
+    @staticmethod
+    def _rows(who, N, **tensors):
+        """name=(tensor, dtype, trailing shape): [N, *shape], contiguous (None is skipped)"""
+        for name, (t, dtype, shape) in tensors.items():
+            if t is None:
+                continue
+            _need(t, dtype, name)
+            if tuple(t.shape) != (N,) + tuple(shape) or not t.is_contiguous():
+                raise RuntimeError(f"{who}: {name} must be a contiguous [{N}, {', '.join(map(str, shape))}] tensor, got {tuple(t.shape)}")
+
+    @staticmethod
+    def coarse_samples(rays_o, rays_d, aabb, min_near, num_steps, nears, fars, z, xyz, noise=None):
+        f, S, N = torch.float32, int(num_steps), rays_o.shape[0]
+        HierBackend._shape("coarse_samples", S, 0)
+        HierBackend._rows("coarse_samples", N, rays_o=(rays_o, f, (3,)), rays_d=(rays_d, f, (3,)), nears=(nears, f, ()), fars=(fars, f, ()),
+                          z=(z, f, (S,)), xyz=(xyz, f, (S, 3)), noise=(noise, f, (S,)))
+        HierBackend._rows("coarse_samples", 6, aabb=(aabb, f, ()))
+        _check(lib().s3d_hier_coarse_samples(_p(rays_o), _p(rays_d), _p(aabb), _u(N), _f(min_near), _u(S), _p(noise), _p(nears),
+                                             _p(fars), _p(z), _p(xyz), _stream()), "hier_coarse_samples")
+
+    @staticmethod
+    def upsample(z, sigma, nears, fars, density_scale, u, rays_o, rays_d, aabb, upsample_steps, new_z, new_xyz, z_sorted, order):
+        """u: [N, U] uniforms, or None for the deterministic torch.linspace(0.5 / U, 1 - 0.5 / U, U)"""
+        f, N, S, U = torch.float32, z.shape[0], z.shape[1], int(upsample_steps)
+        HierBackend._shape("upsample", S, U)
+        if U < 1:
+            raise RuntimeError("upsample: upsample_steps must be at least 1 (none: skip the call)")
+        HierBackend._rows("upsample", N, z=(z, f, (S,)), sigma=(sigma, f, (S,)), nears=(nears, f, ()), fars=(fars, f, ()), u=(u, f, (U,)),
+                          rays_o=(rays_o, f, (3,)), rays_d=(rays_d, f, (3,)), new_z=(new_z, f, (U,)), new_xyz=(new_xyz, f, (U, 3)),
+                          z_sorted=(z_sorted, f, (S + U,)), order=(order, torch.int32, (S + U,)))
+        HierBackend._rows("upsample", 6, aabb=(aabb, f, ()))
+        _check(lib().s3d_hier_upsample(_p(z), _p(sigma), _p(nears), _p(fars), _f(density_scale), _p(u), _p(rays_o), _p(rays_d), _p(aabb),
+                                       _u(N), _u(S), _u(U), _p(new_z), _p(new_xyz), _p(z_sorted), _p(order), _stream()), "hier_upsample")
+
+    @staticmethod
+    def _merged(who, num_steps, z_sorted, order):
+        N, K, S = z_sorted.shape[0], z_sorted.shape[1], int(num_steps)
+        HierBackend._shape(who, S, K - S)
+        if order is None and K != S:
+            raise RuntimeError(f"{who}: order may be omitted (the identity) only without upsampling")
+        return N, K, S
+
+    @staticmethod
+    def weights(z_sorted, order, sigma_cat, nears, fars, density_scale, num_steps, weights, mask):
+        """mask: a torch.bool (or uint8) tensor [N, K]"""
+        f = torch.float32
+        N, K, S = HierBackend._merged("weights", num_steps, z_sorted, order)
+        HierBackend._rows("weights", N, z_sorted=(z_sorted, f, (K,)), order=(order, torch.int32, (K,)), sigma_cat=(sigma_cat, f, (K,)),
+                          nears=(nears, f, ()), fars=(fars, f, ()), weights=(weights, f, (K,)))
+        if mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (N, K):
+            raise RuntimeError(f"weights: mask must be a bool or uint8 [{N}, {K}] tensor")
+        _check(lib().s3d_hier_weights(_p(z_sorted), _p(order), _p(sigma_cat), _p(nears), _p(fars), _f(density_scale), _u(N), _u(S),
+                                      _u(K - S), _p(weights), _p(mask), _stream()), "hier_weights")
+
+    @staticmethod
+    def composite_forward(weights, rgbs, z_sorted, order, nears, fars, num_steps, weights_sum, depth, image):
+        f = torch.float32
+        N, K, S = HierBackend._merged("composite_forward", num_steps, z_sorted, order)
+        HierBackend._rows("composite_forward", N, weights=(weights, f, (K,)), rgbs=(rgbs, f, (K, 3)), z_sorted=(z_sorted, f, (K,)),
+                          order=(order, torch.int32, (K,)), nears=(nears, f, ()), fars=(fars, f, ()), weights_sum=(weights_sum, f, ()),
+                          depth=(depth, f, ()), image=(image, f, (3,)))
+        _check(lib().s3d_hier_composite_forward(_p(weights), _p(rgbs), _p(z_sorted), _p(order), _p(nears), _p(fars), _u(N), _u(S),
+                                                _u(K - S), _p(weights_sum), _p(depth), _p(image), _stream()), "hier_composite_forward")
+
+    @staticmethod
+    def composite_backward(grad_image, grad_weights_sum, grad_depth, sigma_cat, rgbs, z_sorted, order, nears, fars, density_scale,
+                           num_steps, grad_sigma_cat, grad_rgbs):
+        """grad_image [N, 3], grad_weights_sum [N], grad_depth [N]: each may be None for zero"""
+        f = torch.float32
+        N, K, S = HierBackend._merged("composite_backward", num_steps, z_sorted, order)
+        HierBackend._rows("composite_backward", N, grad_image=(grad_image, f, (3,)), grad_weights_sum=(grad_weights_sum, f, ()),
+                          grad_depth=(grad_depth, f, ()), sigma_cat=(sigma_cat, f, (K,)), rgbs=(rgbs, f, (K, 3)),
+                          z_sorted=(z_sorted, f, (K,)), order=(order, torch.int32, (K,)), nears=(nears, f, ()), fars=(fars, f, ()),
+                          grad_sigma_cat=(grad_sigma_cat, f, (K,)), grad_rgbs=(grad_rgbs, f, (K, 3)))
+        _check(lib().s3d_hier_composite_backward(_p(grad_image), _p(grad_weights_sum), _p(grad_depth), _p(sigma_cat), _p(rgbs),
+                                                 _p(z_sorted), _p(order), _p(nears), _p(fars), _f(density_scale), _u(N), _u(S), _u(K - S),
+                                                 _p(grad_sigma_cat), _p(grad_rgbs), _stream()), "hier_composite_backward")
