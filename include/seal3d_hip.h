@@ -1046,6 +1046,49 @@ int s3d_hier_composite_backward(const float* grad_image, const float* grad_weigh
                                 const float* nears, const float* fars, float density_scale, uint32_t N, uint32_t S, uint32_t U,
                                 float* grad_sigma_cat, float* grad_rgbs, s3d_stream_t stream);
 
+/* ------------------------------------------------------------------ SDF (csrc/sdf.hip; DESIGN.md "SDF")
+ * The data path of the signed-distance backbone (sdf/provider.py and loss.py:7-16 of the reference).  All tensors fp32, row-major
+ * and on the device unless noted; triangles [F,3,3] = F x {A, B, C} x {x, y, z}.
+ *
+ * s3d_mesh_sdf — sdf [N], winding [N] (optional), nearest_face [N] int32 (optional) of points [N,3] against F triangles, brute
+ * force (N F pair tests, one lane per point, the triangles staged through LDS in tiles of s3d_mesh_sdf_tile() = 256).
+ *   distance: min over the faces of the exact point-triangle distance = min(the three edge segments — whose end points are the
+ *     three vertices — and, where the foot of the perpendicular lies inside the face, the distance to its plane).  An edge with
+ *     |e|^2 <= 1e-30 is its start point, a face with |n|^2 <= 1e-30 (n = (B - A) x (C - A)) has no plane: a zero-area triangle is
+ *     its segment or its point.  nearest_face: the face of the minimum, the lowest index among equals.
+ *   winding:  w = (1 / 4 pi) sum_f Omega_f, Omega_f = 2 atan2(a.(b x c), |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|) with a, b, c the
+ *     vertices minus the point; Omega_f = 0 for a face without area and where a.(b x c) == 0 (the point in the face's plane: also on
+ *     an edge or a vertex, where atan2 would have no defined argument).
+ *   sign:     sdf = -dist where w > 0.5, +dist elsewhere: negative inside a mesh whose triangles face outward (the sign of the
+ *     reference's -pysdf(points)).
+ * No input yields NaN or Inf from finite coordinates.  N == 0: S3D_OK, nothing launched.  F == 0: S3D_ERR_INVALID.
+ *
+ * s3d_sdf_sample_points — points [N,3] of one dataset item (SDFDataset.__getitem__), N % 8 == 0, N <= 2^28:
+ *   rows [0, N/2)     a point on the surface
+ *   rows [N/2, 7N/8)  a point on the surface + noise_std * (standard normal per axis)
+ *   rows [7N/8, N)    uniform in [-1, 1)^3
+ * Word j of row n is hash_u32(key, step, 8 n + j) (csrc/s3d_common.hpp); U(w) = (w >> 8) / 2^24 in [0, 1).  Surface rows: the face is
+ * the first f with cdf[f] > U(word 0) (cdf [F] normalised, non-decreasing, cdf[F-1] = 1: faces in proportion to their area), the point
+ * (1 - s) A + s (1 - u2) B + s u2 C with s = sqrt(U(word 1)), u2 = U(word 2).  Normals by Box-Muller: r = sqrt(-2 ln(((w >> 8) + 1) /
+ * 2^24)), angle 2 pi U(next word): x, y from words 3, 4 (cosine, sine), z from words 5, 6 (cosine).  Uniform rows: 2 U(word j) - 1
+ * for j = 0, 1, 2 (exact in fp32).  face [N] int32 (optional): the drawn face, -1 for the uniform rows.  An item is a pure
+ * function of (key, step) and the mesh.
+ *
+ * s3d_sdf_mape_forward_backward — loss[0] = mean_b(|p_b - t_b| / (|t_b| + 1e-2)), p = clamp(pred, -clip, clip) (clip <= 0: none),
+ * and grad = grad_scale * sign(p - t) / ((|t| + 1e-2) * B) in fp32 (sign(0) = 0; 0 where |pred| > clip), in one launch.  pred and
+ * grad: S3D_F32 -> [B,1] fp32; S3D_F16 -> the [B,16] fp16 rows of the MLP's padded output, column 0 the distance, and grad's columns
+ * 1..15 written as zero (grad 16-byte aligned).  target [B].  The sum runs in a fixed order (a lane's rows, lanes by a shuffle tree,
+ * waves, then workgroups in index order through `workspace`, s3d_sdf_mape_workspace_size(B) bytes, 16-byte aligned) without float
+ * atomics: the same inputs give the same bits.  B == 0: S3D_ERR_INVALID. */
+int s3d_mesh_sdf_tile(void);
+int s3d_mesh_sdf(const float* points, uint32_t N, const float* triangles, uint32_t F, float* sdf, float* winding,
+                 int32_t* nearest_face, s3d_stream_t stream);
+int s3d_sdf_sample_points(const float* triangles, const float* cdf, uint32_t F, uint32_t N, uint32_t key, uint32_t step,
+                          float noise_std, float* points, int32_t* face, s3d_stream_t stream);
+size_t s3d_sdf_mape_workspace_size(uint32_t B);
+int s3d_sdf_mape_forward_backward(const void* pred, int dtype, const float* target, uint32_t B, float clip, float grad_scale,
+                                  float* loss, void* grad, void* workspace, size_t workspace_bytes, s3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

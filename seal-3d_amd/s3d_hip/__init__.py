@@ -60,6 +60,7 @@ EXPORTS = [
     "s3d_dnerf_warp_backward",
     "s3d_hier_max_samples", "s3d_hier_coarse_samples", "s3d_hier_upsample", "s3d_hier_weights", "s3d_hier_composite_forward",
     "s3d_hier_composite_backward",
+    "s3d_mesh_sdf_tile", "s3d_mesh_sdf", "s3d_sdf_sample_points", "s3d_sdf_mape_workspace_size", "s3d_sdf_mape_forward_backward",
 ]
 
 
@@ -91,7 +92,7 @@ def lib():
                      "s3d_sweep_update_workspace_size", "s3d_sweep_draw_native_workspace_size", "s3d_vm_backward_bins_workspace_size", "s3d_vm_backward_stage_bytes",
                      "s3d_weighted_abs_sum_workspace_size", "s3d_background_backward_workspace_size",
                      "s3d_vm_background_backward_workspace_size", "s3d_mc_workspace_bytes",
-                     "s3d_dnerf_warp_grid_workspace_size"):
+                     "s3d_dnerf_warp_grid_workspace_size", "s3d_sdf_mape_workspace_size"):
             getattr(l, name).restype = C.c_size_t
         l.s3d_vm_backward_max_bins.restype = C.c_uint32
         l.s3d_grid_level_scales.restype = None
@@ -2255,3 +2256,68 @@ class HierBackend:
         _check(lib().s3d_hier_composite_backward(_p(grad_image), _p(grad_weights_sum), _p(grad_depth), _p(sigma_cat), _p(rgbs),
                                                  _p(z_sorted), _p(order), _p(nears), _p(fars), _f(density_scale), _u(N), _u(S), _u(K - S),
                                                  _p(grad_sigma_cat), _p(grad_rgbs), _stream()), "hier_composite_backward")
+
+
+class SdfBackend:
+    """The SDF backbone's data path (csrc/sdf.hip; include/seal3d_hip.h "SDF"): signed distance and winding number of points against a
+    triangle mesh, one dataset item's points, and the MAPE criterion with its gradient.  Every tensor fp32 unless noted; outputs
+    are allocated here and returned."""
+
+    @staticmethod
+    def tile():
+        """triangles per LDS tile of mesh_sdf (tests place F at its edges)"""
+        return int(lib().s3d_mesh_sdf_tile())
+
+    @staticmethod
+    def _triangles(who, triangles):
+        _need(triangles, torch.float32, "triangles")
+        if triangles.dim() != 3 or tuple(triangles.shape[1:]) != (3, 3):
+            raise RuntimeError(f"{who}: triangles must be [F, 3, 3], got {tuple(triangles.shape)}")
+        return triangles.shape[0]
+
+    @staticmethod
+    def mesh_sdf(points, triangles, want_winding=False, want_face=False):
+        """points [N, 3], triangles [F, 3, 3] -> sdf [N] (negative inside), then winding [N] and nearest_face [N] int32 as asked"""
+        _need(points, torch.float32, "points")
+        F = SdfBackend._triangles("mesh_sdf", triangles)
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise RuntimeError(f"mesh_sdf: points must be [N, 3], got {tuple(points.shape)}")
+        N, dev = points.shape[0], points.device
+        sdf = torch.empty(N, dtype=torch.float32, device=dev)
+        winding = torch.empty(N, dtype=torch.float32, device=dev) if want_winding else None
+        face = torch.empty(N, dtype=torch.int32, device=dev) if want_face else None
+        _check(lib().s3d_mesh_sdf(_p(points), _u(N), _p(triangles), _u(F), _p(sdf), _p(winding), _p(face), _stream()), "mesh_sdf")
+        out = (sdf,) + ((winding,) if want_winding else ()) + ((face,) if want_face else ())
+        return out[0] if len(out) == 1 else out
+
+    @staticmethod
+    def sample_points(triangles, cdf, N, key, step, noise_std=0.01, want_face=False):
+        """one dataset item's points [N, 3] (surface | perturbed surface | uniform), a pure function of (key, step)"""
+        F = SdfBackend._triangles("sample_points", triangles)
+        _need(cdf, torch.float32, "cdf")
+        N = int(N)
+        if cdf.numel() != F or N < 0 or N % 8:
+            raise RuntimeError(f"sample_points: cdf holds one value per triangle, num_samples must be divisible by 8, got {N}")
+        points = torch.empty(N, 3, dtype=torch.float32, device=triangles.device)
+        face = torch.empty(N, dtype=torch.int32, device=triangles.device) if want_face else None
+        _check(lib().s3d_sdf_sample_points(_p(triangles), _p(cdf), _u(F), _u(N), _u(int(key) & 0xFFFFFFFF), _u(int(step) & 0xFFFFFFFF),
+                                           _f(noise_std), _p(points), _p(face), _stream()), "sdf_sample_points")
+        return (points, face) if want_face else points
+
+    @staticmethod
+    def mape_forward_backward(pred, target, clip=None, grad_scale=1.0):
+        """pred fp16 [B, 16] (the MLP's padded rows, column 0 the distance) or fp32 [B, 1]; target [B] or [B, 1] -> (loss fp32
+        scalar, grad laid out as pred)"""
+        _need(target, torch.float32, "target")
+        B = pred.shape[0]
+        if pred.dim() != 2 or pred.shape[1] != (16 if pred.dtype == torch.float16 else 1) or target.numel() != B:
+            raise RuntimeError("mape_forward_backward: pred is fp16 [B, 16] or fp32 [B, 1], target holds B values")
+        dt = _dt(pred)
+        nb = int(lib().s3d_sdf_mape_workspace_size(_u(B)))
+        ws = _ws.get(nb, pred.device)
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+        grad = torch.empty_like(pred)
+        _check(lib().s3d_sdf_mape_forward_backward(_p(pred), C.c_int(dt), _p(target), _u(B), _f(clip if clip else 0.0), _f(grad_scale),
+                                                   _p(loss), _p(grad), _p(ws), C.c_size_t(ws.numel()), _stream()),
+               "sdf_mape_forward_backward")
+        return loss, grad
