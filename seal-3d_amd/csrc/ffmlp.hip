@@ -1540,8 +1540,10 @@ int launch_backward_fused_k(const BwdArgs& a, const BwdOpts& o) {
     for (uint32_t m = 0; m < (uint32_t)NH; m++)
         plan.layer[1 + m] = WgradLayer{nullptr, nullptr, 0u, 0u, (uint32_t)W, (uint32_t)W, (uint32_t)(W * in_dim + m * W * W)};
     plan.layer[NH + 1] = WgradLayer{nullptr, nullptr, 0u, 0u, 16u, (uint32_t)W, (uint32_t)(W * in_dim + NH * W * W)};
+    // (the first matrix is [W, in_dim]: at W = 32 an input of 48 / 64 columns makes it the largest of the plan)
+    const uint32_t widest = (uint32_t)W > in_dim ? (uint32_t)W : in_dim;
     if (a.accumulate != 2u)  // (2: the caller finishes several networks with one s3d_ffmlp_wgrad_reduce_pair)
-        hipLaunchKernelGGL(k_ffmlp_wgrad_reduce, dim3(div_up<uint32_t>(W * W * kReduceSplit, 256), plan.n), dim3(256), 0, a.st, plan, nblk,
+        hipLaunchKernelGGL(k_ffmlp_wgrad_reduce, dim3(div_up<uint32_t>(W * widest * kReduceSplit, 256), plan.n), dim3(256), 0, a.st, plan, nblk,
                            (const float*)a.partial, a.grad_weights, a.accumulate, o.found_inf, kWgradPad);
     return check_launch("ffmlp_backward (fused)");
 }
