@@ -879,6 +879,26 @@ int s3d_step_epilogue(float* scale, int32_t* growth_tracker, float* found_inf, f
                       int32_t growth_interval, float* adam_step, const float* loss, int32_t* counter, float* loss_ring,
                       int32_t* counter_ring, int32_t* cursor, int32_t ring, int32_t loss_slots, s3d_stream_t stream);
 
+/* ------------------------------------------------------------------ parameter EMA (csrc/ema.hip)
+ * The reference's trainers keep torch_ema's ExponentialMovingAverage of the parameters (nerf/utils.py:733,882; main_nerf.py:147
+ * `ema_decay=0.95`).  tensors: HOST array of {param, shadow, n}: fp32, contiguous, DEVICE, 4-byte aligned (a view that starts
+ * inside an allocation is fine), n == 0 allowed; any number of tensors (one streaming launch per 64 non-empty ones).
+ * s3d_ema_update_multi: per element, three fp32 roundings and no contraction (bit-identical to torch_ema's tmp = s - p;
+ * tmp.mul_(c); s.sub_(tmp)):  t = s - p;  t = t * c;  s = s - t,  with c = (float)(1.0 - d) and, in double,
+ * d = min(decay, (1 + n) / (10 + n)) where n = *num_updates + 1 (use_num_updates != 0), or d = decay (use_num_updates == 0).
+ * num_updates: DEVICE int64, read by the update and advanced by exactly one by a one-thread launch behind it (also with no
+ * tensors at all); may be NULL when use_num_updates == 0 (nothing is counted then).  No host read: legal under stream capture,
+ * and a replay uses the count of its own time.  decay must lie in [0, 1].
+ * s3d_ema_exchange_multi: param[i] <-> shadow[i] for every element, in place; two calls are the identity. */
+typedef struct s3d_ema_tensor {
+    float* param; /* read by the update, written by the exchange */
+    float* shadow;
+    size_t n;
+} s3d_ema_tensor;
+int s3d_ema_update_multi(const s3d_ema_tensor* tensors /* host array */, int32_t n_tensors, double decay, int use_num_updates,
+                         int64_t* num_updates, s3d_stream_t stream);
+int s3d_ema_exchange_multi(const s3d_ema_tensor* tensors /* host array */, int32_t n_tensors, s3d_stream_t stream);
+
 /* ------------------------------------------------------------------ training-ray sampling (build extension)
  * nerf/utils.py:92-114 `get_rays(..., N, error_map)` on the device, for one training batch in one launch.  index [B] (device
  * int64): the image of each batch row.  error_map [n_img, 128*128] (fp32, 16-byte aligned): weighted draw of N <= 16,384 cells

@@ -47,7 +47,7 @@ class Trainer(_Trainer):
     def render_image(self, rays_o, rays_d, time, bg_color=1):
         """the eval / test rendering at `time`"""
         self.model.eval()
-        with torch.autocast("cuda", dtype=torch.float16, enabled=self.fp16):
+        with self._averaged(), torch.autocast("cuda", dtype=torch.float16, enabled=self.fp16):
             return self.model.render(rays_o, rays_d, time, bg_color=bg_color, perturb=False, **self.render_kwargs)
 
     eval_step = test_step = render_image

@@ -16,6 +16,8 @@ import os
 
 import torch
 
+from .ema import weights_changed
+
 
 def checkpoint_path(workspace, name, epoch):
     return os.path.join(workspace, "checkpoints", f"{name}_ep{epoch:04d}.pth")
@@ -64,15 +66,20 @@ def save_checkpoint(trainer, workspace, name="ngp", full=False, best=False, remo
     if stats["best_result"] is not None and stats["results"][-1] >= stats["best_result"]:
         return None
     stats["best_result"] = stats["results"][-1]
+    path = os.path.join(ckpt_dir, f"{name}.pth")
     if ema is not None:
         ema.store()
         ema.copy_to()
-    state["model"] = dict(model.state_dict())
-    state["model"].pop("density_grid", None)
-    if ema is not None:
-        ema.restore()
-    path = os.path.join(ckpt_dir, f"{name}.pth")
-    torch.save(state, path)
+    try:
+        state["model"] = dict(model.state_dict())
+        state["model"].pop("density_grid", None)
+        # written BEFORE the restore: a state-dict's tensors are the parameters' own storage, so a file written behind it (as
+        # the reference does, nerf/utils.py:1064-1073) would hold the restored values, not the averaged ones
+        torch.save(state, path)
+    finally:
+        if ema is not None:
+            ema.restore()
+            ema.collected_params = None
     return path
 
 
@@ -91,7 +98,8 @@ def load_checkpoint(trainer, checkpoint, model_only=False, lr_scheduler=None, em
     _check_time_size(model, ckpt)
     if "model" not in ckpt:
         model.load_state_dict(ckpt)
-        _after_weights_changed(trainer)
+        weights_changed(trainer.optimizer)
+        _reseed(ema, model)
         return [], []
     if getattr(model, "rank_residual", False) and all(k in ckpt for k in _CC_RANKS):
         _refuse_composed(model, "load")
@@ -102,9 +110,11 @@ def load_checkpoint(trainer, checkpoint, model_only=False, lr_scheduler=None, em
         model.upsample_model(ckpt["resolution"])
         trainer.rebuild_optimizer()
     missing, unexpected = model.load_state_dict(ckpt["model"], strict=False)
-    _after_weights_changed(trainer)
+    weights_changed(trainer.optimizer)
     if ema is not None and "ema" in ckpt:
         ema.load_state_dict(ckpt["ema"])
+    else:
+        _reseed(ema, model)
     if model.cuda_ray:
         if "mean_count" in ckpt:
             model.mean_count = ckpt["mean_count"]
@@ -170,10 +180,9 @@ def _match_cc_structure(trainer, ckpt):
     return new
 
 
-def _after_weights_changed(trainer):
-    """fp16 copies of the tables / MLP weights (eval cache, optimizer hand-over) follow the new fp32 values"""
-    from gridencoder.grid import bump_weights_epoch
-    bump_weights_epoch()
-    resync = getattr(trainer.optimizer, "resync_half", None)
-    if resync is not None:
-        resync()
+def _reseed(ema, model):
+    """A file without an `ema` entry (model-only, `best`, written without an EMA) loaded into a trainer that keeps one: the
+    average starts over from the loaded weights, update count 0.  (The reference leaves the shadows at the values they had —
+    after construction the random initial weights — and then evaluates those; DESIGN.md lists the divergence.)"""
+    if ema is not None and hasattr(ema, "reseed"):
+        ema.reseed(model.parameters())

@@ -164,8 +164,13 @@ def render_loss(out, gt_rgb, expected_grad=None, gt_depth=None, depth_weight=1.0
 
 class Trainer:
     def __init__(self, model, lr=1e-2, fp16=True, update_extra_interval=16, dist=None, max_steps=1024, dt_gamma=0,
-                 T_thresh=1e-4, capturable=False, native_optim=None, optimizer=None, scaler=None, lr_scheduler=None):
+                 T_thresh=1e-4, capturable=False, native_optim=None, optimizer=None, scaler=None, lr_scheduler=None, ema_decay=None):
         self.model = model
+        # `ema_decay` (the reference's NGP / D-NeRF / Seal entry points pass 0.95, nerf/utils.py:356-357): an exponential moving
+        # average of ALL parameters (nerf/ema.py), updated behind every optimizer step; evaluation and the `best` checkpoint use
+        # the averaged weights.  None: no object, no launch
+        self.ema_decay = ema_decay
+        self.ema = None
         # `lr_scheduler(optimizer)` -> a torch scheduler, stepped after every optimizer step (nerf/utils.py:411-414 with
         # `scheduler_update_every_step=True`, main_SealNeRF.py:283-300: LambdaLR 0.1 ** min(iter / iters, 1)); a replayed step
         # follows it through the optimizer's device-side lr factor (nerf/optim.py: follow_lr_schedule)
@@ -185,6 +190,7 @@ class Trainer:
             self.optimizer, self.scaler = optimizer, scaler
             if lr_scheduler is not None:
                 self.lr_scheduler = lr_scheduler(self.optimizer)
+            self._rebuild_ema()
         else:
             self.scaler = None
             self.rebuild_optimizer()
@@ -202,6 +208,8 @@ class Trainer:
             if resync is not None:
                 resync()  # ... so the optimizer's fp16 copies are re-made from the adopted values
             bump_weights_epoch()
+            if self.ema is not None:
+                self.ema.reseed()  # ... and the average starts from them: every rank holds the same shadows from here on
 
     def _param_groups(self):
         """the optimizer's parameter groups (a backbone's trainer may use several learning rates: tensoRF/utils.py)"""
@@ -226,6 +234,23 @@ class Trainer:
                 self.scaler = torch.amp.GradScaler("cuda", enabled=fp16)
         if self._lr_scheduler_factory is not None:
             self.lr_scheduler = self._lr_scheduler_factory(self.optimizer)
+        self._rebuild_ema()
+
+    def _rebuild_ema(self):
+        """the average over the model's CURRENT parameters, started from their current values with the update count at 0 (a
+        changed parameter set — TensoRF upsampling, a CCNeRF structure change — starts it over: the old shadows fit nothing)"""
+        if self.ema_decay is None:
+            return
+        if self.ema is None:
+            from .ema import NativeEMA, weights_changed
+            self.ema = NativeEMA(self.model.parameters(), decay=self.ema_decay,
+                                 on_weights_changed=lambda: weights_changed(self.optimizer))
+        else:
+            self.ema.reseed(self.model.parameters())
+
+    def _averaged(self):
+        """context of evaluation: the model holds the averaged weights inside it (nerf/utils.py:774-785, 919-1011), its own after it"""
+        return self.ema.average_parameters() if self.ema is not None else contextlib.nullcontext()
 
     def _sched_step(self):
         if self.lr_scheduler is not None:
@@ -234,12 +259,13 @@ class Trainer:
     def save_checkpoint(self, workspace, name="ngp", full=False, best=False, remove_old=True, max_keep_ckpt=2):
         """reference on-disk format (nerf/utils.py:1015-1076); see nerf/checkpoint.py"""
         from .checkpoint import save_checkpoint
-        return save_checkpoint(self, workspace, name, full=full, best=best, remove_old=remove_old, max_keep_ckpt=max_keep_ckpt)
+        return save_checkpoint(self, workspace, name, full=full, best=best, remove_old=remove_old, max_keep_ckpt=max_keep_ckpt,
+                               ema=self.ema)
 
     def load_checkpoint(self, checkpoint, model_only=False):
         """reference on-disk format (nerf/utils.py:1078-1137); a file written by the reference's Trainer loads as is"""
         from .checkpoint import load_checkpoint
-        return load_checkpoint(self, checkpoint, model_only=model_only)
+        return load_checkpoint(self, checkpoint, model_only=model_only, ema=self.ema)
 
     def _maybe_update_extra_state(self):
         model = self.model
@@ -313,6 +339,14 @@ class Trainer:
                 self.dist.allreduce_grads(self.scaler)
             self.scaler.step(self.optimizer)
         self.scaler.update()
+        self._ema_update()
+
+    def _ema_update(self):
+        """behind the optimizer step and the scaler's update of EVERY step, skipped ones included (nerf/utils.py:733: the
+        reference calls `ema.update()` unconditionally).  Stream order puts it behind a table update that ran inside the grid
+        backward too."""
+        if self.ema is not None:
+            self.ema.update()
 
     def _expected_grad(self):
         """the upstream gradient `_backward` will hand to the loss (NativeGradScaler: its scale tensor), if known in advance"""
@@ -415,7 +449,7 @@ class Trainer:
     @torch.no_grad()
     def render_image(self, rays_o, rays_d, bg_color=1):
         self.model.eval()
-        with torch.autocast("cuda", dtype=torch.float16, enabled=self.fp16):
+        with self._averaged(), torch.autocast("cuda", dtype=torch.float16, enabled=self.fp16):
             return self.model.render(rays_o, rays_d, bg_color=bg_color, perturb=False, **self.render_kwargs)
 
 
@@ -537,6 +571,7 @@ class GraphedTrainer(Trainer):
             self._ring_args = None
         else:
             self.scaler.update()
+        self._ema_update()  # (part of the captured optimizer body: a step stays one replay — the second one of the two-graph split)
 
     def _capture(self):
         """One graph for the whole step — with data parallelism too when the process group's collectives can be captured

@@ -61,6 +61,7 @@ EXPORTS = [
     "s3d_hier_max_samples", "s3d_hier_coarse_samples", "s3d_hier_upsample", "s3d_hier_weights", "s3d_hier_composite_forward",
     "s3d_hier_composite_backward",
     "s3d_mesh_sdf_tile", "s3d_mesh_sdf", "s3d_sdf_sample_points", "s3d_sdf_mape_workspace_size", "s3d_sdf_mape_forward_backward",
+    "s3d_ema_update_multi", "s3d_ema_exchange_multi",
 ]
 
 
@@ -1168,6 +1169,48 @@ class OptimBackend:
         """file `loss` [] / `counter` [2] in slot *cursor of the rings, clear the counter, advance the cursor (seal3d_hip.h)"""
         _check(lib().s3d_step_ring_push(*_ring_push_args(loss, counter, loss_ring, counter_ring, cursor, "step_ring_push"), _stream()),
                "step_ring_push")
+
+
+class _EmaTensor(C.Structure):
+    """seal3d_hip.h: s3d_ema_tensor"""
+    _fields_ = [("param", C.c_void_p), ("shadow", C.c_void_p), ("n", C.c_size_t)]
+
+
+class EmaBackend:
+    """csrc/ema.hip — the parameters' exponential moving average (torch_ema's update) and the by-value swap"""
+
+    @staticmethod
+    def _tensors(pairs, who):
+        """the s3d_ema_tensor array of `pairs` = [(param, shadow), ...]: fp32, contiguous, on the GPU, of equal size"""
+        arr = (_EmaTensor * max(len(pairs), 1))()
+        for a, (param, shadow) in zip(arr, pairs):
+            _need(param, torch.float32, f"{who}: param"); _need(shadow, torch.float32, f"{who}: shadow")
+            if param.numel() != shadow.numel():
+                raise RuntimeError(f"{who}: param and shadow must be of equal size, got {param.numel()} and {shadow.numel()}")
+            if param.device != shadow.device:
+                raise RuntimeError(f"{who}: param and shadow must live on one device")
+            a.param, a.shadow, a.n = _p(param), _p(shadow), param.numel()
+        return arr
+
+    @staticmethod
+    def update_multi(pairs, decay, num_updates, use_num_updates=True):
+        """shadow -= (1 - d) * (shadow - param) for every (param, shadow) of `pairs`, torch_ema's three roundings, one launch;
+        `num_updates`: the device int64 [1] count (advanced by one; None only with use_num_updates=False) — seal3d_hip.h"""
+        if num_updates is not None:
+            _need(num_updates, torch.int64, "ema_update_multi: num_updates")
+            if num_updates.numel() != 1:
+                raise RuntimeError("ema_update_multi: num_updates is one int64")
+        elif use_num_updates:
+            raise RuntimeError("ema_update_multi: the warm-up schedule needs the device update count")
+        arr = EmaBackend._tensors(pairs, "ema_update_multi")
+        _check(lib().s3d_ema_update_multi(arr, C.c_int32(len(pairs)), C.c_double(float(decay)), C.c_int(int(bool(use_num_updates))),
+                                          _p(num_updates), _stream()), "ema_update_multi")
+
+    @staticmethod
+    def exchange_multi(pairs):
+        """param <-> shadow, elementwise and in place, for every (param, shadow) of `pairs` in one launch"""
+        arr = EmaBackend._tensors(pairs, "ema_exchange_multi")
+        _check(lib().s3d_ema_exchange_multi(arr, C.c_int32(len(pairs)), _stream()), "ema_exchange_multi")
 
 
 class NgpHeadBackend:

@@ -2,8 +2,10 @@
 evaluation, checkpoints in the project's format and `save_mesh` through the device marching cubes.
 
 The criterion is the reference's `mape_loss` (loss.py:7-16).  Where the model's fused route runs, loss and gradient come from one
-launch on the MLP's padded rows (s3d_sdf_mape_forward_backward); anywhere else the torch restatement below is used.  Tensorboard,
-`rich` and the EMA of `torch_ema` are left out, as in the other trainers here."""
+launch on the MLP's padded rows (s3d_sdf_mape_forward_backward); anywhere else the torch restatement below is used.  The parameter
+average of `torch_ema` (main_sdf.py:58 `ema_decay=0.95`) is nerf/ema.py's; tensorboard and `rich` are left out, as in the other
+trainers here."""
+import contextlib
 import os
 
 import torch
@@ -54,9 +56,11 @@ def default_optimizer(model, lr=1e-4):
 
 class Trainer:
     def __init__(self, name, model, criterion=mape_loss, optimizer=None, lr_scheduler=None, device=None, mute=False, fp16=False,
-                 eval_interval=1, max_keep_ckpt=2, workspace=None, use_checkpoint="latest", scheduler_update_every_step=False):
+                 eval_interval=1, max_keep_ckpt=2, workspace=None, use_checkpoint="latest", scheduler_update_every_step=False,
+                 ema_decay=None):
         """optimizer / lr_scheduler: factories `model -> optimizer`, `optimizer -> scheduler` as in the reference (None: main_sdf.py's
-        Adam, and its StepLR(10, 0.1))"""
+        Adam, and its StepLR(10, 0.1)).  ema_decay: keep nerf.ema.NativeEMA over the parameters, updated after every optimizer step;
+        evaluation and the `best` checkpoint use the averaged weights (sdf/utils.py:148-149, 349-350, 414-422, 503-511 of the reference)"""
         self.name, self.mute, self.fp16, self.workspace = name, mute, fp16, workspace
         self.eval_interval, self.max_keep_ckpt, self.scheduler_update_every_step = eval_interval, max_keep_ckpt, scheduler_update_every_step
         self.device = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -66,6 +70,10 @@ class Trainer:
         self.lr_scheduler = (lr_scheduler(self.optimizer) if lr_scheduler is not None
                              else torch.optim.lr_scheduler.StepLR(self.optimizer, step_size=10, gamma=0.1))
         self.scaler = torch.amp.GradScaler(self.device.type, enabled=self.fp16 and self.device.type == "cuda")
+        self.ema = None
+        if ema_decay is not None:
+            from nerf.ema import NativeEMA, weights_changed
+            self.ema = NativeEMA(self.model.parameters(), decay=ema_decay, on_weights_changed=lambda: weights_changed(self.optimizer))
         self.epoch = self.global_step = self.local_step = 0
         self.stats = {"loss": [], "valid_loss": [], "results": [], "checkpoints": [], "best_result": None}
         self.step_losses = []  # the last epoch's loss per step
@@ -132,6 +140,8 @@ class Trainer:
             self.scaler.scale(loss).backward()
             self.scaler.step(self.optimizer)
             self.scaler.update()
+            if self.ema is not None:
+                self.ema.update()
             if self.scheduler_update_every_step:
                 self.lr_scheduler.step()
             losses.append(loss.detach().float())  # (read once, after the epoch)
@@ -151,10 +161,11 @@ class Trainer:
         self.log(f"++> Evaluate at epoch {self.epoch} ...")
         self.model.eval()
         losses = []
-        for data in loader:
-            with self._autocast():
-                _, _, loss = self.eval_step(self.prepare_data(data))
-            losses.append(loss.detach().float())
+        with self.ema.average_parameters() if self.ema is not None else contextlib.nullcontext():
+            for data in loader:
+                with self._autocast():
+                    _, _, loss = self.eval_step(self.prepare_data(data))
+                losses.append(loss.detach().float())
         average = float(torch.stack(losses).mean()) if losses else float("nan")
         self.stats["valid_loss"].append(average)
         self.stats["results"].append(average)  # (no metrics: the best checkpoint is the one of the lowest loss)
@@ -199,9 +210,10 @@ class Trainer:
 
     def save_checkpoint(self, full=False, best=False):
         return ckpt.save_checkpoint(self, self.workspace, name=self.name, full=full, best=best, max_keep_ckpt=self.max_keep_ckpt,
-                                    lr_scheduler=self.lr_scheduler)
+                                    lr_scheduler=self.lr_scheduler, ema=self.ema)
 
     def load_checkpoint(self, checkpoint, model_only=False):
-        missing, unexpected = ckpt.load_checkpoint(self, checkpoint, model_only=model_only, lr_scheduler=self.lr_scheduler)
+        missing, unexpected = ckpt.load_checkpoint(self, checkpoint, model_only=model_only, lr_scheduler=self.lr_scheduler,
+                                                      ema=self.ema)
         self.log(f"[INFO] loaded {checkpoint}" + (f", missing {missing}" if missing else "") + (f", unexpected {unexpected}" if unexpected else ""))
         return missing, unexpected
