@@ -1109,6 +1109,48 @@ size_t s3d_sdf_mape_workspace_size(uint32_t B);
 int s3d_sdf_mape_forward_backward(const void* pred, int dtype, const float* target, uint32_t B, float clip, float grad_scale,
                                   float* loss, void* grad, void* workspace, size_t workspace_bytes, s3d_stream_t stream);
 
+/* ------------------------------------------------------------------ SDF: BVH query (csrc/sdf_bvh.hip, csrc/sdf_pair.hpp; DESIGN.md "SDF")
+ * The same query as s3d_mesh_sdf over a bounding-volume hierarchy that sdf/bvh.py: MeshBVH builds once per mesh on the host.  Every
+ * coordinate of points and triangles lies in [-4, 4] (the dataset normalises into [-1, 1]); the pruning slack is derived from that.
+ *
+ * The tree.  LEAF = s3d_mesh_bvh_leaf() = 4 faces per leaf.  The faces are sorted (stably) by the 30-bit Morton code of their
+ * centroid; perm [F] int32: perm[k] is the original index of sorted face k.  L, the number of leaves, is the smallest power of two
+ * with L LEAF >= F (F <= 2^26: at most 2^24 leaves, depth 24).  The 2L - 1 nodes are in heap order: the children of node i are
+ * 2i + 1 and 2i + 2, the leaves are the last L nodes, and node i at depth d (i = 2^d - 1 + k) covers the sorted faces
+ * [k S, (k + 1) S) below F with S = (L >> d) LEAF.  A kernel finds nodes and face ranges by this arithmetic alone and reads perm
+ * only at the faces of a leaf, below F.
+ *   nodes [2L-1, 16] fp32, 16-byte aligned; per node:
+ *     [0..2]   lo: the lower corner of the node's (fp32) vertices, one step of nextafter towards -inf;  [3] 0
+ *     [4..6]   hi: the upper corner, one step towards +inf;  [7] 0
+ *     [8..10]  c: the area-weighted centroid of the faces (the mean of the vertices where the faces have no area)
+ *     [11]     r: the largest |vertex - c| over the node's vertices (c as stored), rounded up
+ *     [12..14] Nsum = sum_f (B - A) x (C - A) / 2, summed in float64, then rounded;  [15] 0
+ *   A node without faces (padding behind F) has lo = +inf, hi = -inf, c = Nsum = 0 and r = -1.
+ *   staged [F, 20] fp32, 16-byte aligned: the sorted faces as s3d_mesh_bvh_stage writes them from triangles [F,3,3] (already in
+ *     sorted order) — A, B - A, C - A, the normal, the reciprocal squared lengths and dot products that s3d_mesh_sdf stages through
+ *     LDS, made by the same expressions, so a pair test reads the same bits on either route.  F == 0: S3D_OK, nothing launched.
+ *
+ * s3d_mesh_sdf_bvh — sdf [N], winding [N] (optional), nearest_face [N] int32 (optional); one launch, a lane per point and walk
+ * (64 points per workgroup: one wave walks for the distance, one for the winding number), no host read, no atomics: the same
+ * inputs give the same bits.
+ *   distance: the minimum over the visited faces of s3d_mesh_sdf's pair test.  A walk from the root, the child with the nearer box
+ *     first; a subtree is skipped only where the fp32 distance to its box exceeds sqrt(best) by more than a slack of 1e-4 (csrc/
+ *     sdf_pair.hpp derives it), so every face whose computed d^2 is <= the final minimum is visited.  nearest_face is the ORIGINAL
+ *     index (through perm), the lowest among equal d^2.  |sdf| and nearest_face equal s3d_mesh_sdf's bit for bit.
+ *   winding:  a second walk in depth-first order, left child first (a fixed summation order): a node without faces adds 0; a node
+ *     with |c - p|^2 > (beta r)^2 adds Nsum.(c - p) / |c - p|^3 (the dipole term of Barill et al., "Fast winding numbers"); a leaf
+ *     that is not far adds Omega_f of s3d_mesh_sdf per face; any other node is opened.  w = sum / 4 pi, sdf = -dist where w > 0.5.
+ *     w differs from s3d_mesh_sdf's by the far-field approximation: at beta = 3 by at most about 1.2e-2 up to 5,120 faces (profiles/
+ *     sdf_bvh.md), against the gap of 0.5 between a closed mesh's winding numbers and the sign rule's cut.
+ *   Both walks are stackless over the heap indices and stop after 2 (2L - 1) iterations; a point whose walk reaches that cap gets
+ *     sdf = NaN.  It is not reached on a tree of this contract (a walk visits a node at most once).
+ * N == 0: S3D_OK, nothing launched.  F == 0, F > 2^26, L not a power of two, L LEAF < F, beta <= 0 or not finite, NULL points /
+ * nodes / staged / perm / sdf: S3D_ERR_INVALID. */
+int s3d_mesh_bvh_leaf(void);
+int s3d_mesh_bvh_stage(const float* triangles, uint32_t F, float* staged, s3d_stream_t stream);
+int s3d_mesh_sdf_bvh(const float* points, uint32_t N, const float* nodes, const float* staged, const int32_t* perm, uint32_t F,
+                     uint32_t L, float beta, float* sdf, float* winding, int32_t* nearest_face, s3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,7 @@ EXPORTS = [
     "s3d_hier_composite_backward",
     "s3d_mesh_sdf_tile", "s3d_mesh_sdf", "s3d_sdf_sample_points", "s3d_sdf_mape_workspace_size", "s3d_sdf_mape_forward_backward",
     "s3d_ema_update_multi", "s3d_ema_exchange_multi",
+    "s3d_mesh_bvh_leaf", "s3d_mesh_bvh_stage", "s3d_mesh_sdf_bvh",
 ]
 
 
@@ -2330,6 +2331,36 @@ class SdfBackend:
         winding = torch.empty(N, dtype=torch.float32, device=dev) if want_winding else None
         face = torch.empty(N, dtype=torch.int32, device=dev) if want_face else None
         _check(lib().s3d_mesh_sdf(_p(points), _u(N), _p(triangles), _u(F), _p(sdf), _p(winding), _p(face), _stream()), "mesh_sdf")
+        out = (sdf,) + ((winding,) if want_winding else ()) + ((face,) if want_face else ())
+        return out[0] if len(out) == 1 else out
+
+    @staticmethod
+    def bvh_leaf():
+        """faces per leaf of the mesh BVH (sdf/bvh.py builds to it)"""
+        return int(lib().s3d_mesh_bvh_leaf())
+
+    @staticmethod
+    def bvh_stage(triangles):
+        """triangles [F, 3, 3] in the tree's sorted order -> staged [F, 20], the records a pair test of mesh_sdf_bvh reads"""
+        F = SdfBackend._triangles("bvh_stage", triangles)
+        staged = torch.empty(F, 20, dtype=torch.float32, device=triangles.device)
+        _check(lib().s3d_mesh_bvh_stage(_p(triangles), _u(F), _p(staged), _stream()), "mesh_bvh_stage")
+        return staged
+
+    @staticmethod
+    def mesh_sdf_bvh(points, bvh, beta=3.0, want_winding=False, want_face=False):
+        """points [N, 3], bvh a sdf.bvh.MeshBVH -> what mesh_sdf returns: the same distance and nearest face bit for bit, the winding
+        number through the tree's far-field terms (`beta`: a node farther than beta radii is taken as a dipole)"""
+        _need(points, torch.float32, "points")
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise RuntimeError(f"mesh_sdf_bvh: points must be [N, 3], got {tuple(points.shape)}")
+        N, dev = points.shape[0], points.device
+        nodes, staged, perm = bvh.device_arrays(dev)
+        sdf = torch.empty(N, dtype=torch.float32, device=dev)
+        winding = torch.empty(N, dtype=torch.float32, device=dev) if want_winding else None
+        face = torch.empty(N, dtype=torch.int32, device=dev) if want_face else None
+        _check(lib().s3d_mesh_sdf_bvh(_p(points), _u(N), _p(nodes), _p(staged), _p(perm), _u(bvh.F), _u(bvh.L), _f(beta), _p(sdf),
+                                      _p(winding), _p(face), _stream()), "mesh_sdf_bvh")
         out = (sdf,) + ((winding,) if want_winding else ()) + ((face,) if want_face else ())
         return out[0] if len(out) == 1 else out
 

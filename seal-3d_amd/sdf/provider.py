@@ -1,5 +1,6 @@
 """SDF dataset (sdf/provider.py of the reference) with the sampling and the distance query on the device: an item is two launches,
-s3d_sdf_sample_points (surface | perturbed surface | uniform rows) and s3d_mesh_sdf over the rows that are not on the surface.
+s3d_sdf_sample_points (surface | perturbed surface | uniform rows) and s3d_mesh_sdf — or, from BVH_AUTO_MIN_FACES faces on,
+s3d_mesh_sdf_bvh over a tree built once (sdf/bvh.py) — over the rows that are not on the surface.
 The reference draws with trimesh and queries pysdf on the CPU; here the mesh is loaded, normalised, checked and oriented once on
 the host, and an item is a pure function of (seed, item number)."""
 import os
@@ -10,6 +11,12 @@ import torch
 
 import s3d_hip
 from nerf.mesh import read_ply
+from sdf.bvh import MeshBVH
+
+# accel="auto" takes the BVH from this many faces on: the smallest size of the sweep in profiles/sdf_bvh.md (N = 2^17 points, UV
+# spheres and tori of 1,280 faces and upwards in steps of 4x) at which the BVH's median was below brute force's in the same run,
+# on both meshes and both point sets (3.1 against 4.4 ms on the sphere; at 1,280 faces 1.5 against 1.1 ms)
+BVH_AUTO_MIN_FACES = 5120
 
 
 def read_obj(path_or_lines):
@@ -79,7 +86,8 @@ def signed_volume(vertices, faces):
 
 
 class SDFDataset(torch.utils.data.Dataset):
-    def __init__(self, path_or_mesh, size=100, num_samples=2 ** 18, clip_sdf=None, seed=0, device=None, noise_std=0.01):
+    def __init__(self, path_or_mesh, size=100, num_samples=2 ** 18, clip_sdf=None, seed=0, device=None, noise_std=0.01,
+                 accel="auto"):
         super().__init__()
         vertices, faces = load_mesh(path_or_mesh)
         if len(faces) == 0:
@@ -106,6 +114,12 @@ class SDFDataset(torch.utils.data.Dataset):
         cdf[int(np.nonzero(area)[0][-1]):] = 1.0  # (the last face with an area closes the range, whatever the rounding)
         self.triangles = torch.from_numpy(tri.astype(np.float32)).contiguous().to(self.device)
         self.cdf = torch.from_numpy(cdf).to(self.device)
+        # the distance query: brute force over all faces, or the BVH (the same distance bit for bit, the sign through a hierarchical
+        # winding number with far-field terms); the tree is built here, once
+        if accel not in ("brute", "bvh", "auto"):
+            raise ValueError(f"SDFDataset: accel is 'brute', 'bvh' or 'auto', not `{accel}`")
+        self.accel = accel if accel != "auto" else ("bvh" if len(faces) >= BVH_AUTO_MIN_FACES else "brute")
+        self.bvh = MeshBVH(tri.astype(np.float32)) if self.accel == "bvh" else None
 
     def __len__(self):
         return self.size
@@ -115,7 +129,10 @@ class SDFDataset(torch.utils.data.Dataset):
         # (the reference draws afresh whenever an item is asked for: the trainer counts `epoch` up, so item i of another epoch differs)
         points = s3d_hip.SdfBackend.sample_points(self.triangles, self.cdf, N, self.seed, self.epoch * self.size + int(i), self.noise_std)
         sdfs = torch.zeros(N, 1, dtype=torch.float32, device=self.device)  # (rows [0, N / 2) lie on the surface)
-        sdfs[N // 2:, 0] = s3d_hip.SdfBackend.mesh_sdf(points[N // 2:], self.triangles)
+        if self.bvh is not None:
+            sdfs[N // 2:, 0] = s3d_hip.SdfBackend.mesh_sdf_bvh(points[N // 2:], self.bvh)
+        else:
+            sdfs[N // 2:, 0] = s3d_hip.SdfBackend.mesh_sdf(points[N // 2:], self.triangles)
         if self.clip_sdf is not None:
             sdfs = sdfs.clamp(-self.clip_sdf, self.clip_sdf)
         return {"sdfs": sdfs, "points": points}

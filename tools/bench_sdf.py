@@ -13,6 +13,11 @@ medians; prints one JSON line.
     fused route against torch route, alternating call by call on one model.
 
     python tools/bench_sdf.py [--reps 9]
+
+`--accel bvh` or `--accel both` prints the BVH sweep instead (profiles/sdf_bvh.md): s3d_mesh_sdf_bvh, alone or alternating call by
+call with s3d_mesh_sdf, at N = 2^17 uniform points and at an item's own rows [N/2, N), on UV spheres and tori of 1,280 faces and
+upwards in steps of 4x up to 327,680; the BVH on the same rows in Morton order; max |dw|, bit equality of distance and face;
+the host build; a whole 2^18-row item.  The default, `--accel brute`, is the line described above.
 """
 import argparse
 import contextlib
@@ -148,7 +153,7 @@ def sampler_and_item(reps):
     from sdf.provider import SDFDataset
     v, f = uv_sphere(20, 32, weld=True)
     with contextlib.redirect_stdout(sys.stderr):  # (the dataset reports the mesh it loaded: not part of the result line)
-        ds = SDFDataset((v, f), num_samples=2 ** 18)
+        ds = SDFDataset((v, f), num_samples=2 ** 18, accel="brute")
     return {"rows": 2 ** 18, "faces": len(ds.faces),
             "sampler": _timed(lambda: s3d_hip.SdfBackend.sample_points(ds.triangles, ds.cdf, 2 ** 18, 0, 1), reps),
             "item": _timed(lambda: ds[1], reps)}
@@ -160,7 +165,7 @@ def step(reps):
     from sdf.utils import Trainer
     v, f = uv_sphere(20, 32, weld=True)
     with contextlib.redirect_stdout(sys.stderr):  # (the dataset reports the mesh it loaded: not part of the result line)
-        ds = SDFDataset((v, f), num_samples=2 ** 18)
+        ds = SDFDataset((v, f), num_samples=2 ** 18, accel="brute")
     torch.manual_seed(0)
     net = SDFNetwork(encoding="hashgrid")
     tr = Trainer("bench", net, fp16=True, mute=True)
@@ -184,12 +189,90 @@ def step(reps):
     return {"points": 2 ** 18, "ms": res, "last_loss": {"fused": routes[True], "torch": routes[False]}}
 
 
+def torus(nu, nv, R=0.6, r=0.25):
+    """(vertices, faces) of a closed torus with 2 nu nv outward-facing triangles, none without area"""
+    th = np.linspace(0, 2 * np.pi, nu, endpoint=False)[:, None]
+    ph = np.linspace(0, 2 * np.pi, nv, endpoint=False)[None, :]
+    v = np.stack([(R + r * np.cos(ph)) * np.cos(th), (R + r * np.cos(ph)) * np.sin(th), r * np.sin(ph) * np.ones_like(th)], -1).reshape(-1, 3)
+    i, j = np.meshgrid(np.arange(nu), np.arange(nv), indexing="ij")
+    a, b, c, d = i * nv + j, i * nv + (j + 1) % nv, ((i + 1) % nu) * nv + j, ((i + 1) % nu) * nv + (j + 1) % nv
+    f = np.concatenate([np.stack([a, c, d], -1).reshape(-1, 3), np.stack([a, d, b], -1).reshape(-1, 3)])
+    return v, f
+
+
+def _morton_order(points):
+    """row order of points in [-1, 1]^3 along a 30-bit Morton curve (an experiment: the cost of the sort is not timed)"""
+    q = ((points.clamp(-1, 1) + 1) * 511.5).long().clamp(0, 1023)
+    code = torch.zeros(points.shape[0], dtype=torch.long, device=points.device)
+    for bit in range(10):
+        for axis in range(3):
+            code |= ((q[:, axis] >> bit) & 1) << (3 * bit + axis)
+    return torch.argsort(code)
+
+
+def bvh_sweep(reps, accel, max_faces=327680):
+    """brute force against the BVH in one process, alternating call by call: N = 2^17 uniform points and an item's own rows
+    [N/2, N) (perturbed surface + uniform), UV spheres and tori of 1,280 faces and upwards in steps of 4x; the BVH also on the
+    same rows in Morton order; the host build; a whole item of 2^18 rows"""
+    import time
+    import warnings
+    import s3d_hip
+    from sdf.provider import SDFDataset
+    S = s3d_hip.SdfBackend
+    uniform = (torch.rand(N_QUERY, 3, generator=torch.Generator().manual_seed(0)) * 2 - 1).cuda()
+    out = {"points": N_QUERY, "beta": 3.0, "leaf": S.bvh_leaf(), "meshes": {}}
+    for mesh_name, make in (("uv_sphere", uv_sphere), ("torus", torus)):
+        sizes, nu, nv = {}, 20, 32
+        while 2 * nu * nv <= max_faces:
+            v, f = make(nu, nv)
+            with contextlib.redirect_stdout(sys.stderr), warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                t0 = time.perf_counter()
+                ds = SDFDataset((v, f), num_samples=2 * N_QUERY, accel="bvh")
+                t_ds = time.perf_counter() - t0
+                t0 = time.perf_counter()
+                type(ds.bvh)(ds.bvh.triangles_sorted)
+                t_build = time.perf_counter() - t0
+            item_rows = S.sample_points(ds.triangles, ds.cdf, 2 * N_QUERY, 0, 1)[N_QUERY:].contiguous()
+            r = {"host_build_s": t_build, "dataset_init_s": t_ds, "leaves": ds.bvh.L}
+            for set_name, pts in (("uniform", uniform), ("item_rows", item_rows)):
+                ordered = pts[_morton_order(pts)].contiguous()
+                variants = {}
+                if accel in ("brute", "both"):
+                    variants["brute"] = lambda pts=pts: S.mesh_sdf(pts, ds.triangles)
+                if accel in ("bvh", "both"):
+                    variants["bvh"] = lambda pts=pts: S.mesh_sdf_bvh(pts, ds.bvh)
+                    variants["bvh_morton_ordered_rows"] = lambda ordered=ordered: S.mesh_sdf_bvh(ordered, ds.bvh)
+                res = _alternate(variants, reps)
+                if accel == "both":
+                    s0, w0, f0 = S.mesh_sdf(pts, ds.triangles, want_winding=True, want_face=True)
+                    s1, w1, f1 = S.mesh_sdf_bvh(pts, ds.bvh, want_winding=True, want_face=True)
+                    res["max_abs_dw"] = float((w0 - w1).abs().max())
+                    res["distance_bits_equal"] = bool(torch.equal(s0.abs().view(torch.int32), s1.abs().view(torch.int32)))
+                    res["faces_equal"] = bool(torch.equal(f0, f1))
+                    res["signs_differ"] = int(((s0 < 0) != (s1 < 0)).sum())
+                    res["nan"] = int(torch.isnan(s1).sum())
+                r[set_name] = res
+            if accel in ("bvh", "both"):
+                r["item_2^18_rows_bvh"] = _timed(lambda: ds[1], reps)
+            sizes[str(len(f))] = r
+            nu, nv = nu * 2, nv * 2
+        out["meshes"][mesh_name] = sizes
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--accel", choices=("brute", "bvh", "both"), default="brute",
+                    help="brute: the figures above (the default); bvh / both: the BVH sweep instead, alone or against brute force")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_sdf: needs a GPU (no CPU timing is meaningful here)")
+    if a.accel != "brute":
+        print(json.dumps({"metric": "SDF mesh distance query: brute force against the BVH", "device": torch.cuda.get_device_name(0),
+                          "sweep": bvh_sweep(a.reps, a.accel)}))
+        return
     res = {"metric": "SDF backbone: mesh distance query, sampler, dataset item, training step", "device": torch.cuda.get_device_name(0),
            "mesh_sdf": query(a.reps), "dataset": sampler_and_item(a.reps), "step": step(a.reps)}
     print(json.dumps(res))
