@@ -1066,7 +1066,7 @@ int s3d_hier_composite_backward(const float* grad_image, const float* grad_weigh
                                 const float* nears, const float* fars, float density_scale, uint32_t N, uint32_t S, uint32_t U,
                                 float* grad_sigma_cat, float* grad_rgbs, s3d_stream_t stream);
 
-/* ------------------------------------------------------------------ SDF (csrc/sdf.hip; DESIGN.md "SDF")
+/* ------------------------------------------------------------------ SDF (csrc/sdf.hip, csrc/sdf_pair.hpp; DESIGN.md "SDF")
  * The data path of the signed-distance backbone (sdf/provider.py and loss.py:7-16 of the reference).  All tensors fp32, row-major
  * and on the device unless noted; triangles [F,3,3] = F x {A, B, C} x {x, y, z}.
  *
@@ -1128,7 +1128,7 @@ int s3d_sdf_mape_forward_backward(const void* pred, int dtype, const float* targ
  *   A node without faces (padding behind F) has lo = +inf, hi = -inf, c = Nsum = 0 and r = -1.
  *   staged [F, 20] fp32, 16-byte aligned: the sorted faces as s3d_mesh_bvh_stage writes them from triangles [F,3,3] (already in
  *     sorted order) — A, B - A, C - A, the normal, the reciprocal squared lengths and dot products that s3d_mesh_sdf stages through
- *     LDS, made by the same expressions, so a pair test reads the same bits on either route.  F == 0: S3D_OK, nothing launched.
+ *     LDS, made by the same function, so a pair test reads the same bits on either route.  F == 0: S3D_OK, nothing launched.
  *
  * s3d_mesh_sdf_bvh — sdf [N], winding [N] (optional), nearest_face [N] int32 (optional); one launch, a lane per point and walk
  * (64 points per workgroup: one wave walks for the distance, one for the winding number), no host read, no atomics: the same

@@ -1,34 +1,17 @@
 // sdf.hip — the SDF backbone's data path (include/seal3d_hip.h "SDF"; DESIGN.md "SDF"): signed distance and winding number of
 // points against a triangle mesh (brute force, the triangles staged through LDS), one dataset item's points in one launch, and the
-// MAPE criterion with its gradient on the MLP's padded output.
+// MAPE criterion with its gradient on the MLP's padded output.  The pair test itself, with its tie and sign rules, is
+// csrc/sdf_pair.hpp, shared with the BVH query (csrc/sdf_bvh.hip): this file only tiles the faces and loops over them.
 #include "s3d_common.hpp"
+#include "sdf_pair.hpp"
 
 namespace s3d {
 namespace {
 
+using namespace sdfpair;
+
 constexpr uint32_t kSdfBlock = 256;  // lanes per workgroup = points per workgroup
 constexpr uint32_t kSdfTile = 256;   // triangles per LDS tile: one per lane to stage, 20 KiB, 8 workgroups per CU fit in 160 KiB
-constexpr float kTiny = 1e-30f;      // |edge|^2 or |normal|^2 below this: the edge is a point / the triangle has no area
-
-// one staged triangle: what every pair test reads and what depends on the triangle alone (5 x 16 bytes)
-struct __attribute__((aligned(16))) StagedTri {
-    float ax, ay, az, inv_nn;     // A; 1 / |n|^2, 0 for a triangle without area
-    float abx, aby, abz, inv_ab;  // B - A; 1 / |B - A|^2 (0: A == B)
-    float acx, acy, acz, inv_ac;  // C - A; 1 / |C - A|^2
-    float nx, ny, nz, inv_bc;     // n = (B - A) x (C - A); 1 / |C - B|^2
-    float d00, d01, d11, pad;     // ab.ab, ab.ac, ac.ac
-};
-
-__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
-    return ax * bx + ay * by + az * bz;
-}
-
-__device__ __forceinline__ float seg_dist2(float px, float py, float pz, float ex, float ey, float ez, float pe, float inv_ee) {
-    // squared distance of p (relative to the segment's start) to the segment along e; pe = p.e; inv_ee = 0 collapses it to the start
-    const float t = clampf(pe * inv_ee, 0.0f, 1.0f);
-    const float vx = px - t * ex, vy = py - t * ey, vz = pz - t * ez;
-    return dot3(vx, vy, vz, vx, vy, vz);
-}
 
 __global__ void __launch_bounds__(kSdfBlock) mesh_sdf_kernel(const float* __restrict__ points, uint32_t N, const float* __restrict__ triangles,
                                                             uint32_t F, float* __restrict__ sdf, float* __restrict__ winding,
@@ -42,65 +25,17 @@ __global__ void __launch_bounds__(kSdfBlock) mesh_sdf_kernel(const float* __rest
     uint32_t best_face = 0;
     for (uint32_t base = 0; base < F; base += kSdfTile) {
         const uint32_t count = F - base < kSdfTile ? F - base : kSdfTile;
-        if (threadIdx.x < count) {
-            const float* t = triangles + (size_t)(base + threadIdx.x) * 9;
-            StagedTri s;
-            s.ax = t[0]; s.ay = t[1]; s.az = t[2];
-            s.abx = t[3] - s.ax; s.aby = t[4] - s.ay; s.abz = t[5] - s.az;
-            s.acx = t[6] - s.ax; s.acy = t[7] - s.ay; s.acz = t[8] - s.az;
-            s.nx = s.aby * s.acz - s.abz * s.acy;
-            s.ny = s.abz * s.acx - s.abx * s.acz;
-            s.nz = s.abx * s.acy - s.aby * s.acx;
-            s.d00 = dot3(s.abx, s.aby, s.abz, s.abx, s.aby, s.abz);
-            s.d01 = dot3(s.abx, s.aby, s.abz, s.acx, s.acy, s.acz);
-            s.d11 = dot3(s.acx, s.acy, s.acz, s.acx, s.acy, s.acz);
-            const float bcx = s.acx - s.abx, bcy = s.acy - s.aby, bcz = s.acz - s.abz;
-            const float bb = dot3(bcx, bcy, bcz, bcx, bcy, bcz);
-            const float nn = dot3(s.nx, s.ny, s.nz, s.nx, s.ny, s.nz);
-            s.inv_ab = s.d00 > kTiny ? 1.0f / s.d00 : 0.0f;
-            s.inv_ac = s.d11 > kTiny ? 1.0f / s.d11 : 0.0f;
-            s.inv_bc = bb > kTiny ? 1.0f / bb : 0.0f;
-            s.inv_nn = nn > kTiny ? 1.0f / nn : 0.0f;
-            s.pad = 0.0f;
-            tile[threadIdx.x] = s;
-        }
+        if (threadIdx.x < count) tile[threadIdx.x] = stage_tri(triangles + (size_t)(base + threadIdx.x) * 9);
         __syncthreads();
         for (uint32_t j = 0; j < count; j++) {
-            const StagedTri& s = tile[j];  // the same address in every lane: a broadcast read
-            const float apx = px - s.ax, apy = py - s.ay, apz = pz - s.az;
-            const float d20 = dot3(apx, apy, apz, s.abx, s.aby, s.abz);
-            const float d21 = dot3(apx, apy, apz, s.acx, s.acy, s.acz);
-            // the three edges (their end points are the three vertices)
-            float d2 = seg_dist2(apx, apy, apz, s.abx, s.aby, s.abz, d20, s.inv_ab);
-            d2 = fminf(d2, seg_dist2(apx, apy, apz, s.acx, s.acy, s.acz, d21, s.inv_ac));
-            const float bpx = apx - s.abx, bpy = apy - s.aby, bpz = apz - s.abz;
-            const float bcx = s.acx - s.abx, bcy = s.acy - s.aby, bcz = s.acz - s.abz;
-            d2 = fminf(d2, seg_dist2(bpx, bpy, bpz, bcx, bcy, bcz, dot3(bpx, bpy, bpz, bcx, bcy, bcz), s.inv_bc));
-            // the face: the foot of the perpendicular lies inside iff its two barycentric numerators and their complement are >= 0
-            const float pn = dot3(apx, apy, apz, s.nx, s.ny, s.nz);
-            const float v = s.d11 * d20 - s.d01 * d21;
-            const float w = s.d00 * d21 - s.d01 * d20;
-            const float den = s.d00 * s.d11 - s.d01 * s.d01;
-            if (s.inv_nn > 0.0f && v >= 0.0f && w >= 0.0f && v + w <= den) d2 = fminf(d2, pn * pn * s.inv_nn);
-            if (d2 < best) { best = d2; best_face = base + j; }  // (strict: ties stay with the lowest face)
-            // solid angle (van Oosterom & Strackee): a, b, c = vertices - point; a.(b x c) = a.n = -pn
-            if (s.inv_nn > 0.0f && pn != 0.0f) {
-                const float ax = -apx, ay = -apy, az = -apz;
-                const float bx = ax + s.abx, by = ay + s.aby, bz = az + s.abz;
-                const float cx = ax + s.acx, cy = ay + s.acy, cz = az + s.acz;
-                const float la = sqrtf(dot3(ax, ay, az, ax, ay, az)), lb = sqrtf(dot3(bx, by, bz, bx, by, bz));
-                const float lc = sqrtf(dot3(cx, cy, cz, cx, cy, cz));
-                const float denom = la * lb * lc + dot3(ax, ay, az, bx, by, bz) * lc + dot3(bx, by, bz, cx, cy, cz) * la
-                                    + dot3(cx, cy, cz, ax, ay, az) * lb;
-                omega += 2.0f * atan2f(-pn, denom);
-            }
+            pair_accumulate(tile[j], base + j, px, py, pz, &best, &best_face, &omega);  // (one address in every lane: a broadcast read)
         }
         __syncthreads();
     }
     if (!live) return;
-    const float wn = omega * 0.07957747154594767f;  // 1 / (4 pi)
-    const float dist = sqrtf(best);
-    sdf[n] = wn > 0.5f ? -dist : dist;
+    float s, wn;
+    pair_finish(true, best, omega, &s, &wn);
+    sdf[n] = s;
     if (winding) winding[n] = wn;
     if (nearest_face) nearest_face[n] = (int32_t)best_face;
 }

@@ -44,7 +44,7 @@ __global__ void __launch_bounds__(2 * kBvhPoints) mesh_sdf_bvh_kernel(const floa
     __syncthreads();
     if (winds || n >= N) return;
     float s, w;
-    bvh_finish(ok && ok_of[lane] != 0u, best, omega_of[lane], &s, &w);
+    pair_finish(ok && ok_of[lane] != 0u, best, omega_of[lane], &s, &w);
     sdf[n] = s;
     if (winding) winding[n] = w;
     if (nearest_face) nearest_face[n] = (int32_t)best_face;

@@ -1,7 +1,9 @@
-// sdf_pair.hpp — the point-triangle pair test of csrc/sdf.hip and the two walks of the mesh BVH (include/seal3d_hip.h "SDF: BVH
-// query"; DESIGN.md "SDF"), in plain C++ that compiles for the device and for the host: csrc/sdf_bvh.hip runs each walk one lane
-// per point, tests/sdf_bvh_host.cpp runs the same text under the host sanitizers.  The staging and pair expressions are those of
-// mesh_sdf_kernel (csrc/sdf.hip), operation for operation; the library is built without contraction, so they give the same bits.
+// sdf_pair.hpp — the point-triangle pair test of the SDF backbone and the two walks of the mesh BVH (include/seal3d_hip.h "SDF",
+// "SDF: BVH query"; DESIGN.md "SDF"), in plain C++ that compiles for the device and for the host.  This is the only place that
+// knows the staging of a triangle, the distance and solid-angle expressions, the tie rule (pair_accumulate) and the sign rule
+// (pair_finish): mesh_sdf_kernel (csrc/sdf.hip) runs pair_accumulate over its LDS tiles, csrc/sdf_bvh.hip runs each walk one lane
+// per point, and tests/sdf_bvh_host.cpp runs both routes from the same text under the host sanitizers.  The library is built
+// without contraction, so one text gives one set of bits wherever it is compiled.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -80,40 +82,78 @@ S3D_HD StagedTri stage_tri(const float* t) {
     return s;
 }
 
-// squared distance of p to the staged triangle
-S3D_HD float pair_dist2(const StagedTri& s, float px, float py, float pz) {
-    const float apx = px - s.ax, apy = py - s.ay, apz = pz - s.az;
-    const float d20 = dot3(apx, apy, apz, s.abx, s.aby, s.abz);
-    const float d21 = dot3(apx, apy, apz, s.acx, s.acy, s.acz);
+// the point as one triangle sees it: what both halves of the pair test start from
+struct PairPoint {
+    float apx, apy, apz;  // p - A
+    float pn;             // (p - A).n
+};
+
+S3D_HD PairPoint pair_point(const StagedTri& s, float px, float py, float pz) {
+    PairPoint q;
+    q.apx = px - s.ax; q.apy = py - s.ay; q.apz = pz - s.az;
+    q.pn = dot3(q.apx, q.apy, q.apz, s.nx, s.ny, s.nz);
+    return q;
+}
+
+// squared distance of the point to the staged triangle
+S3D_HD float pair_dist2(const StagedTri& s, const PairPoint& q) {
+    const float d20 = dot3(q.apx, q.apy, q.apz, s.abx, s.aby, s.abz);
+    const float d21 = dot3(q.apx, q.apy, q.apz, s.acx, s.acy, s.acz);
     // the three edges (their end points are the three vertices)
-    float d2 = seg_dist2(apx, apy, apz, s.abx, s.aby, s.abz, d20, s.inv_ab);
-    d2 = fminf(d2, seg_dist2(apx, apy, apz, s.acx, s.acy, s.acz, d21, s.inv_ac));
-    const float bpx = apx - s.abx, bpy = apy - s.aby, bpz = apz - s.abz;
+    float d2 = seg_dist2(q.apx, q.apy, q.apz, s.abx, s.aby, s.abz, d20, s.inv_ab);
+    d2 = fminf(d2, seg_dist2(q.apx, q.apy, q.apz, s.acx, s.acy, s.acz, d21, s.inv_ac));
+    const float bpx = q.apx - s.abx, bpy = q.apy - s.aby, bpz = q.apz - s.abz;
     const float bcx = s.acx - s.abx, bcy = s.acy - s.aby, bcz = s.acz - s.abz;
     d2 = fminf(d2, seg_dist2(bpx, bpy, bpz, bcx, bcy, bcz, dot3(bpx, bpy, bpz, bcx, bcy, bcz), s.inv_bc));
     // the face: the foot of the perpendicular lies inside iff its two barycentric numerators and their complement are >= 0
-    const float pn = dot3(apx, apy, apz, s.nx, s.ny, s.nz);
     const float v = s.d11 * d20 - s.d01 * d21;
     const float w = s.d00 * d21 - s.d01 * d20;
     const float den = s.d00 * s.d11 - s.d01 * s.d01;
-    if (s.inv_nn > 0.0f && v >= 0.0f && w >= 0.0f && v + w <= den) d2 = fminf(d2, pn * pn * s.inv_nn);
+    if (s.inv_nn > 0.0f && v >= 0.0f && w >= 0.0f && v + w <= den) d2 = fminf(d2, q.pn * q.pn * s.inv_nn);
     return d2;
 }
 
-// solid angle of the staged triangle seen from p (van Oosterom & Strackee): a, b, c = vertices - point; a.(b x c) = a.n = -pn;
-// 0 for a triangle without area and for a point in its plane
-S3D_HD float pair_omega(const StagedTri& s, float px, float py, float pz) {
-    const float apx = px - s.ax, apy = py - s.ay, apz = pz - s.az;
-    const float pn = dot3(apx, apy, apz, s.nx, s.ny, s.nz);
-    if (!(s.inv_nn > 0.0f && pn != 0.0f)) return 0.0f;
-    const float ax = -apx, ay = -apy, az = -apz;
+// whether the point sees a solid angle at all: not for a triangle without area, not from inside its plane
+S3D_HD bool pair_subtends(const StagedTri& s, const PairPoint& q) { return s.inv_nn > 0.0f && q.pn != 0.0f; }
+
+// solid angle of the staged triangle seen from a point that pair_subtends (van Oosterom & Strackee): a, b, c = vertices - point;
+// a.(b x c) = a.n = -pn
+S3D_HD float pair_omega(const StagedTri& s, const PairPoint& q) {
+    const float ax = -q.apx, ay = -q.apy, az = -q.apz;
     const float bx = ax + s.abx, by = ay + s.aby, bz = az + s.abz;
     const float cx = ax + s.acx, cy = ay + s.acy, cz = az + s.acz;
     const float la = sqrtf(dot3(ax, ay, az, ax, ay, az)), lb = sqrtf(dot3(bx, by, bz, bx, by, bz));
     const float lc = sqrtf(dot3(cx, cy, cz, cx, cy, cz));
     const float denom = la * lb * lc + dot3(ax, ay, az, bx, by, bz) * lc + dot3(bx, by, bz, cx, cy, cz) * la
                         + dot3(cx, cy, cz, ax, ay, az) * lb;
-    return 2.0f * atan2f(-pn, denom);
+    return 2.0f * atan2f(-q.pn, denom);
+}
+
+// the two halves for a walk, which needs one of them per visit (0 where the point sees no solid angle)
+S3D_HD float pair_dist2(const StagedTri& s, float px, float py, float pz) { return pair_dist2(s, pair_point(s, px, py, pz)); }
+
+S3D_HD float pair_omega(const StagedTri& s, float px, float py, float pz) {
+    const PairPoint q = pair_point(s, px, py, pz);
+    return pair_subtends(s, q) ? pair_omega(s, q) : 0.0f;
+}
+
+// One step of the brute-force loop over the faces in their order: the running minimum is strict, so among equal d2 the lowest
+// face stays; the solid angles add up in face order.
+S3D_HD void pair_accumulate(const StagedTri& s, uint32_t face, float px, float py, float pz, float* best_d2, uint32_t* best_face,
+                            float* omega) {
+    const PairPoint q = pair_point(s, px, py, pz);
+    const float d2 = pair_dist2(s, q);
+    if (d2 < *best_d2) { *best_d2 = d2; *best_face = face; }
+    if (pair_subtends(s, q)) *omega += pair_omega(s, q);
+}
+
+// minimum and solid angle over all faces -> sdf (inside where the winding number exceeds 1/2; NaN: a walk reached its iteration
+// cap, which the brute-force loop cannot) and winding number
+S3D_HD void pair_finish(bool ok, float best_d2, float omega, float* sdf, float* winding) {
+    const float wn = omega * 0.07957747154594767f;  // 1 / (4 pi)
+    const float dist = sqrtf(best_d2);
+    *sdf = ok ? (wn > 0.5f ? -dist : dist) : NAN;
+    *winding = wn;
 }
 
 // squared distance of p to the node's box (+inf for a node without faces: its corners are inverted)
@@ -215,14 +255,6 @@ S3D_HD bool bvh_solid_angle(const BvhNode* nodes, const StagedTri* tris, uint32_
     return false;
 }
 
-// what the two walks give for one point -> sdf (NaN: an iteration cap was reached) and winding number
-S3D_HD void bvh_finish(bool ok, float best_d2, float omega, float* sdf, float* winding) {
-    const float wn = omega * 0.07957747154594767f;  // 1 / (4 pi)
-    const float dist = sqrtf(best_d2);
-    *sdf = ok ? (wn > 0.5f ? -dist : dist) : NAN;
-    *winding = wn;
-}
-
 // both walks for one point, one after the other (the kernel gives each walk a wave of its own)
 S3D_HD void bvh_query_point(const BvhNode* nodes, const StagedTri* tris, const int32_t* perm, uint32_t F, uint32_t L, float beta, float px,
                             float py, float pz, float* sdf, float* winding, int32_t* face) {
@@ -230,7 +262,7 @@ S3D_HD void bvh_query_point(const BvhNode* nodes, const StagedTri* tris, const i
     uint32_t best_face = 0;
     const bool ok_d = bvh_nearest(nodes, tris, perm, F, L, px, py, pz, &best, &best_face);
     const bool ok_w = bvh_solid_angle(nodes, tris, F, L, beta, px, py, pz, &omega);
-    bvh_finish(ok_d && ok_w, best, omega, sdf, winding);
+    pair_finish(ok_d && ok_w, best, omega, sdf, winding);
     *face = (int32_t)best_face;
 }
 

@@ -2320,19 +2320,25 @@ class SdfBackend:
         return triangles.shape[0]
 
     @staticmethod
-    def mesh_sdf(points, triangles, want_winding=False, want_face=False):
-        """points [N, 3], triangles [F, 3, 3] -> sdf [N] (negative inside), then winding [N] and nearest_face [N] int32 as asked"""
+    def _query(who, points, want_winding, want_face, launch):
+        """what mesh_sdf and mesh_sdf_bvh share: the points check, the outputs and their order; launch(N, sdf, winding, face)"""
         _need(points, torch.float32, "points")
-        F = SdfBackend._triangles("mesh_sdf", triangles)
         if points.dim() != 2 or points.shape[1] != 3:
-            raise RuntimeError(f"mesh_sdf: points must be [N, 3], got {tuple(points.shape)}")
+            raise RuntimeError(f"{who}: points must be [N, 3], got {tuple(points.shape)}")
         N, dev = points.shape[0], points.device
         sdf = torch.empty(N, dtype=torch.float32, device=dev)
         winding = torch.empty(N, dtype=torch.float32, device=dev) if want_winding else None
         face = torch.empty(N, dtype=torch.int32, device=dev) if want_face else None
-        _check(lib().s3d_mesh_sdf(_p(points), _u(N), _p(triangles), _u(F), _p(sdf), _p(winding), _p(face), _stream()), "mesh_sdf")
+        launch(N, sdf, winding, face)
         out = (sdf,) + ((winding,) if want_winding else ()) + ((face,) if want_face else ())
         return out[0] if len(out) == 1 else out
+
+    @staticmethod
+    def mesh_sdf(points, triangles, want_winding=False, want_face=False):
+        """points [N, 3], triangles [F, 3, 3] -> sdf [N] (negative inside), then winding [N] and nearest_face [N] int32 as asked"""
+        F = SdfBackend._triangles("mesh_sdf", triangles)
+        return SdfBackend._query("mesh_sdf", points, want_winding, want_face, lambda N, sdf, winding, face: _check(
+            lib().s3d_mesh_sdf(_p(points), _u(N), _p(triangles), _u(F), _p(sdf), _p(winding), _p(face), _stream()), "mesh_sdf"))
 
     @staticmethod
     def bvh_leaf():
@@ -2351,18 +2357,11 @@ class SdfBackend:
     def mesh_sdf_bvh(points, bvh, beta=3.0, want_winding=False, want_face=False):
         """points [N, 3], bvh a sdf.bvh.MeshBVH -> what mesh_sdf returns: the same distance and nearest face bit for bit, the winding
         number through the tree's far-field terms (`beta`: a node farther than beta radii is taken as a dipole)"""
-        _need(points, torch.float32, "points")
-        if points.dim() != 2 or points.shape[1] != 3:
-            raise RuntimeError(f"mesh_sdf_bvh: points must be [N, 3], got {tuple(points.shape)}")
-        N, dev = points.shape[0], points.device
-        nodes, staged, perm = bvh.device_arrays(dev)
-        sdf = torch.empty(N, dtype=torch.float32, device=dev)
-        winding = torch.empty(N, dtype=torch.float32, device=dev) if want_winding else None
-        face = torch.empty(N, dtype=torch.int32, device=dev) if want_face else None
-        _check(lib().s3d_mesh_sdf_bvh(_p(points), _u(N), _p(nodes), _p(staged), _p(perm), _u(bvh.F), _u(bvh.L), _f(beta), _p(sdf),
-                                      _p(winding), _p(face), _stream()), "mesh_sdf_bvh")
-        out = (sdf,) + ((winding,) if want_winding else ()) + ((face,) if want_face else ())
-        return out[0] if len(out) == 1 else out
+        def launch(N, sdf, winding, face):
+            nodes, staged, perm = bvh.device_arrays(points.device)
+            _check(lib().s3d_mesh_sdf_bvh(_p(points), _u(N), _p(nodes), _p(staged), _p(perm), _u(bvh.F), _u(bvh.L), _f(beta), _p(sdf),
+                                          _p(winding), _p(face), _stream()), "mesh_sdf_bvh")
+        return SdfBackend._query("mesh_sdf_bvh", points, want_winding, want_face, launch)
 
     @staticmethod
     def sample_points(triangles, cdf, N, key, step, noise_std=0.01, want_face=False):

@@ -1,9 +1,9 @@
-// The BVH walks of csrc/sdf_pair.hpp on the host: tests/test_sdf_bvh.py compiles this file with the address and undefined-behaviour
-// sanitizers and runs it on trees that sdf/bvh.py built, before any of that code runs on a GPU.
+// Both routes of csrc/sdf_pair.hpp on the host, the BVH walks and the brute-force loop that mesh_sdf_kernel runs: tests/test_sdf_bvh.py
+// compiles this file with the address and undefined-behaviour sanitizers and runs it on trees that sdf/bvh.py built.
 //   sdf_bvh_host IN OUT
 // IN:  uint32 N, F, L; float beta; points [N,3]; nodes [2L-1,16]; triangles [F,3,3] in sorted order; perm [F] int32
 // OUT: per point, the BVH's sdf, winding, face [N each], then the same three from a brute-force loop over the faces in their
-//      original order (the pair functions of the same header, strict minimum), then uint32: the points whose walk hit its cap
+//      original order (pair_accumulate and pair_finish of the same header), then uint32: the points whose walk hit its cap
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -49,13 +49,8 @@ int main(int argc, char** argv) {
         if (std::isnan(sdf[n])) capped++;
         float best = 3.402823466e+38f, omega = 0.0f;
         uint32_t best_face = 0;
-        for (uint32_t f = 0; f < F; f++) {
-            const float d2 = pair_dist2(original[f], px, py, pz);
-            if (d2 < best) { best = d2; best_face = f; }
-            omega += pair_omega(original[f], px, py, pz);
-        }
-        bw[n] = omega * 0.07957747154594767f;
-        bsdf[n] = bw[n] > 0.5f ? -sqrtf(best) : sqrtf(best);
+        for (uint32_t f = 0; f < F; f++) pair_accumulate(original[f], f, px, py, pz, &best, &best_face, &omega);
+        pair_finish(true, best, omega, &bsdf[n], &bw[n]);
         bface[n] = (int32_t)best_face;
     }
     FILE* out = fopen(argv[2], "wb");
