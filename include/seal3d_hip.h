@@ -1013,6 +1013,37 @@ int s3d_dnerf_split_grad(const uint16_t* grad_sin, uint32_t B, uint32_t L, int d
 int s3d_dnerf_warp_backward(const void* grad_xw, int dtype, float grad_scale, const float* deform, const float* coef,
                             uint32_t B, uint16_t* grad_dout, const int32_t* n_valid, s3d_stream_t stream);
 
+/* ------------------------------------------------------------------ D-NeRF, temporal basis: the density head
+ * (csrc/dnerf_basis.hip; DESIGN.md "D-NeRF, temporal basis")
+ * dnerf/network_basis.py:139-152 of the reference: sigma = trunc_exp(h[:, :32] @ sigma_basis), colour-net input =
+ * cat[SH_4(d), h[:, 32:]].  h fp16 [B,64]: the density network's output; sigma_basis fp16 [32] (one call has one time); dirs fp32
+ * [B,3].  One lane per row; h, sigma_basis, color_in, grad_color_in and grad_h 16-byte aligned.  n_valid: the padded-batch
+ * convention above (rows at or behind round_up(*n_valid, 128) are neither read, written nor summed).
+ *
+ * s3d_dnerf_basis_mid_forward:
+ *   acc = fmaf(float(h_k), float(sb_k), acc) for k = 0..31 ascending, acc = 0 at the start (fp32);
+ *   pre = float(half(acc))  — the output of the reference's fp16 matrix-vector product;  sigma[b] = expf(pre) (fp32).
+ *   color_in [B,48] fp16 (NULL: sigma alone, dirs may then be NULL): columns 0..15 the bits s3d_ngp_mid_forward writes for the
+ *   same dirs (half(SH_4(d))), columns 16..47 = h[:, 32:64], copied.
+ *
+ * s3d_dnerf_basis_mid_backward:
+ *   grad_h[:, 32:64] = grad_color_in[:, 16:48], copied;
+ *   g = grad_sigma[b] * expf(clamp(pre, -15, 15)) with pre recomputed by the forward's chain (activation.py:13-16), gh = half(g);
+ *   grad_h[:, k] = half(float(gh) * float(sb_k)) for k = 0..31 (the product of two halves is exact in fp32: one rounding);
+ *   grad_sigma_basis[k] (fp32 [32], may be NULL) = sum over the live rows of float(gh_b) * float(h_bk), in fp32.
+ *   grad_sigma == NULL: columns 0..31 of grad_h and grad_sigma_basis are zero.
+ *   The sum is deterministic — the same bits on every run for the same B and the same live rows, no floating-point atomics: the
+ *   launch has min(512, ceil(B / 256)) workgroups of 256 lanes; a lane adds its rows b, b + 256 G, ... in ascending order, a wave
+ *   adds its lanes by a fixed exchange tree, a workgroup its four waves in index order, and the last workgroup to arrive (a ticket) adds
+ *   the workgroups' partials of `workspace`: eight stripes (workgroup index mod 8) each in ascending order, then the stripes in
+ *   order.  workspace: s3d_dnerf_basis_mid_workspace_size(B) bytes, 16-byte aligned; its first 16 bytes are cleared by the call. */
+int s3d_dnerf_basis_mid_forward(const uint16_t* h, const float* dirs, const uint16_t* sigma_basis, uint32_t B, float* sigma,
+                                uint16_t* color_in, const int32_t* n_valid, s3d_stream_t stream);
+size_t s3d_dnerf_basis_mid_workspace_size(uint32_t B);
+int s3d_dnerf_basis_mid_backward(const uint16_t* grad_color_in, const float* grad_sigma, const uint16_t* h,
+                                 const uint16_t* sigma_basis, uint32_t B, uint16_t* grad_h, float* grad_sigma_basis,
+                                 void* workspace, size_t workspace_bytes, const int32_t* n_valid, s3d_stream_t stream);
+
 /* ------------------------------------------------------------------ sampling without the occupancy grid (csrc/hiersample.hip;
  * DESIGN.md "The sampling path without the grid")
  * `NeRFRenderer.run` of the reference (nerf/renderer.py:125-253) and `sample_pdf` (:12-46).  S = num_steps >= 3, U = upsample_steps,

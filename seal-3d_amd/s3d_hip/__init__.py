@@ -58,6 +58,7 @@ EXPORTS = [
     "s3d_mc_workspace_bytes", "s3d_mc_count", "s3d_mc_emit",
     "s3d_dnerf_encode_forward", "s3d_dnerf_warp_grid_workspace_size", "s3d_dnerf_warp_grid_forward", "s3d_dnerf_split_grad",
     "s3d_dnerf_warp_backward",
+    "s3d_dnerf_basis_mid_forward", "s3d_dnerf_basis_mid_workspace_size", "s3d_dnerf_basis_mid_backward",
     "s3d_hier_max_samples", "s3d_hier_coarse_samples", "s3d_hier_upsample", "s3d_hier_weights", "s3d_hier_composite_forward",
     "s3d_hier_composite_backward",
     "s3d_mesh_sdf_tile", "s3d_mesh_sdf", "s3d_sdf_sample_points", "s3d_sdf_mape_workspace_size", "s3d_sdf_mape_forward_backward",
@@ -94,7 +95,7 @@ def lib():
                      "s3d_sweep_update_workspace_size", "s3d_sweep_draw_native_workspace_size", "s3d_vm_backward_bins_workspace_size", "s3d_vm_backward_stage_bytes",
                      "s3d_weighted_abs_sum_workspace_size", "s3d_background_backward_workspace_size",
                      "s3d_vm_background_backward_workspace_size", "s3d_mc_workspace_bytes",
-                     "s3d_dnerf_warp_grid_workspace_size", "s3d_sdf_mape_workspace_size"):
+                     "s3d_dnerf_warp_grid_workspace_size", "s3d_dnerf_basis_mid_workspace_size", "s3d_sdf_mape_workspace_size"):
             getattr(l, name).restype = C.c_size_t
         l.s3d_vm_backward_max_bins.restype = C.c_uint32
         l.s3d_grid_level_scales.restype = None
@@ -2199,6 +2200,54 @@ class DnerfBackend:
                 raise RuntimeError("warp_backward: deform must be [B, 3]")
         _check(lib().s3d_dnerf_warp_backward(_p(grad_xw), C.c_int(_dt(grad_xw)), _f(grad_scale), _p(deform if coef is not None else None),
                                              _p(coef), _u(B), _p(grad_dout), _nv(n_valid), _stream()), "dnerf_warp_backward")
+
+
+class DnerfBasisBackend:
+    """The density head of the D-NeRF temporal-basis backbone (csrc/dnerf_basis.hip; include/seal3d_hip.h): sigma =
+    exp(half(h[:, :32] . sigma_basis)) and the colour net's input row [half(SH_4(d)) | h[:, 32:]], one kernel per direction."""
+
+    ROW, CIN, BASIS = 64, 48, 32
+
+    @staticmethod
+    def _check_rows(h, sigma_basis, who):
+        _need(h, torch.float16, "h"); _need(sigma_basis, torch.float16, "sigma_basis")
+        if h.dim() != 2 or h.shape[1] != DnerfBasisBackend.ROW or sigma_basis.numel() != DnerfBasisBackend.BASIS:
+            raise RuntimeError(f"{who}: h [B, 64] fp16, sigma_basis [32] fp16")
+        return h.shape[0]
+
+    @staticmethod
+    def mid_forward(h, dirs, sigma_basis, sigma, color_in=None, n_valid=None):
+        B = DnerfBasisBackend._check_rows(h, sigma_basis, "basis_mid_forward")
+        _need(sigma, torch.float32, "sigma")
+        if sigma.numel() != B:
+            raise RuntimeError("basis_mid_forward: sigma must be [B]")
+        if color_in is not None:
+            _need(color_in, torch.float16, "color_in"); _need(dirs, torch.float32, "dirs")
+            if tuple(color_in.shape) != (B, DnerfBasisBackend.CIN) or tuple(dirs.shape) != (B, 3):
+                raise RuntimeError("basis_mid_forward: dirs [B, 3], color_in [B, 48]")
+        _check(lib().s3d_dnerf_basis_mid_forward(_p(h), _p(dirs if color_in is not None else None), _p(sigma_basis), _u(B), _p(sigma),
+                                                 _p(color_in), _nv(n_valid), _stream()), "dnerf_basis_mid_forward")
+
+    @staticmethod
+    def mid_backward(grad_color_in, grad_sigma, h, sigma_basis, grad_h, grad_sigma_basis=None, n_valid=None):
+        B = DnerfBasisBackend._check_rows(h, sigma_basis, "basis_mid_backward")
+        _need(grad_color_in, torch.float16, "grad_color_in"); _need(grad_h, torch.float16, "grad_h")
+        if tuple(grad_color_in.shape) != (B, DnerfBasisBackend.CIN) or tuple(grad_h.shape) != (B, DnerfBasisBackend.ROW):
+            raise RuntimeError("basis_mid_backward: grad_color_in [B, 48], grad_h [B, 64]")
+        if grad_sigma is not None:
+            _need(grad_sigma, torch.float32, "grad_sigma")
+            if grad_sigma.numel() != B:
+                raise RuntimeError("basis_mid_backward: grad_sigma must be [B]")
+        ws, nb = None, 0
+        if grad_sigma_basis is not None:
+            _need(grad_sigma_basis, torch.float32, "grad_sigma_basis")
+            if grad_sigma_basis.numel() != DnerfBasisBackend.BASIS:
+                raise RuntimeError("basis_mid_backward: grad_sigma_basis must be [32]")
+            nb = int(lib().s3d_dnerf_basis_mid_workspace_size(_u(B)))
+            ws = _ws.get(nb, h.device)
+        _check(lib().s3d_dnerf_basis_mid_backward(_p(grad_color_in), _p(grad_sigma), _p(h), _p(sigma_basis), _u(B), _p(grad_h),
+                                                  _p(grad_sigma_basis), _p(ws), C.c_size_t(nb), _nv(n_valid), _stream()),
+               "dnerf_basis_mid_backward")
 
 
 class HierBackend:
