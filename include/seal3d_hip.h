@@ -1044,6 +1044,54 @@ int s3d_dnerf_basis_mid_backward(const uint16_t* grad_color_in, const float* gra
                                  const uint16_t* sigma_basis, uint32_t B, uint16_t* grad_h, float* grad_sigma_basis,
                                  void* workspace, size_t workspace_bytes, const int32_t* n_valid, s3d_stream_t stream);
 
+/* ------------------------------------------------------------------ D-NeRF, hyper: the 4-D grid lookup
+ * (csrc/dnerf_hyper.hip; DESIGN.md "D-NeRF, hyper")
+ * dnerf/network_hyper.py:126-140 of the reference: `x = cat([x, ambient.repeat(N, 1)]); x = encoder(x, bound)` with a 4-D tiled /
+ * hash grid.  One call has one time, so the fourth coordinate is ONE device word for every row.  C = 2, L <= 16; every table
+ * dtype, gridtype, align_corners and interpolation s3d_grid_encode_forward takes.  feat, x4, dy_da, grad_feat and grad_levels
+ * 16-byte aligned.  n_valid: the padded-batch convention above (rows at or behind round_up(*n_valid, 128) are neither read,
+ * written nor summed).
+ *
+ * s3d_dnerf_hyper_grid_forward, one launch.  x fp32 [B,3]; ambient: a DEVICE pointer to one fp32 word (no host read).  bound > 0:
+ * raw coordinates, normalised in the kernel as s3d_grid_encode_forward does ((v + bound) * fl(1 / (2 bound))), the ambient word
+ * as well; bound == 0: coordinates in [0,1].
+ *   feat [B, 2L] fp16, row-major: bit for bit the features of s3d_grid_encode_forward with D = 4 on [x | ambient] — an fp16
+ *     table's sums stored as they are, an fp32 table's sums (the fmaf chain over the 16 corners) rounded to binary16 ONCE.
+ *   x4 (optional) fp32 [B,4] = [x | ambient], as given (raw when bound > 0): the `inputs` of the table backward.
+ *   dy_da (optional) [B, L, 2] in the table's dtype: bit for bit that call's dy_dx[:, :, 3, :] (which it produces for
+ *     pre-normalised inputs only: on the normalised coordinates as formed here), the ambient column of the Jacobian w.r.t. the
+ *     NORMALISED coordinate, from the 16 corner rows the value fetched.  Rounding points as there: an fp32
+ *     table adds fmaf(fl(w * diff), pos_deriv, acc) per corner pair; an fp16 table rounds diff to half (one half subtraction),
+ *     fl(fl(w * diff) * pos_deriv) to half and adds in half.  pos_deriv of every dimension but 0 is the constant 0 under linear
+ *     interpolation (the reference's `pos_deriv[D] = {1.0f}`): dy_da is then zero, and a caller need not ask for it.
+ *   A row with any of the four normalised coordinates outside [0,1] gets zero features and zero dy_da.
+ *   On a tiled level whose index does not contain the ambient coordinate (the index drops trailing coordinates once its stride
+ *   exceeds the level's size) the kernel fetches eight rows and uses each twice: the same bits.
+ *
+ * s3d_dnerf_hyper_grid_backward, one launch.  grad_feat fp16 [B, 2L].
+ *   grad_levels [L][B][2] in `dtype` (the table's): grad_feat transposed, what s3d_grid_encode_backward takes as `grad` (exact;
+ *     fp16 -> fp32 is exact).
+ *   grad_ambient (fp32, one word; written when dy_da and grad_ambient are both given) = fl(S * grad_scale), S = sum over the live
+ *     rows of term_b, term_b = the fp32 chain acc = fmaf(float(g_bk), float(j_bk), acc) over the row's columns k = 0 .. 2L-1
+ *     ascending from 0 (g = grad_feat, j = dy_da).  grad_scale: 1 / (2 bound) when the lookup normalised in the kernel (a power of
+ *     two for the usual bounds: exact), else 1.
+ *     DIVERGENCE from the reference, whose kernel_input_backward rounds each row's dot to the table's dtype before torch sums the
+ *     [N, 1] column: the row terms stay fp32 here.
+ *   The sum is deterministic — the same bits on every run for the same B and the same live rows, no floating-point atomics: the
+ *   launch has G = min(512, ceil(B / 256)) workgroups of 256 lanes; a lane adds the terms of its rows b, b + 256 G, ... in ascending
+ *   order, a wave adds its lanes by a fixed exchange tree (offsets 32, 16, .., 1), a workgroup its four waves in index order, and
+ *   the last workgroup to arrive (a ticket) adds the workgroups' partials of `workspace`: lane i those of workgroups i, i + 256 in
+ *   that order, then the tree and the waves as before.  workspace: s3d_dnerf_hyper_backward_workspace_size(B) bytes, 16-byte
+ *   aligned; its first 16 bytes are cleared by the call. */
+int s3d_dnerf_hyper_grid_forward(const float* x, const float* ambient, const void* embeddings, const int32_t* offsets,
+                                 uint32_t B, uint32_t L, float S, uint32_t H, uint32_t gridtype, int align_corners,
+                                 uint32_t interp, int dtype, float bound, uint16_t* feat, float* x4, void* dy_da,
+                                 const int32_t* n_valid, s3d_stream_t stream);
+size_t s3d_dnerf_hyper_backward_workspace_size(uint32_t B);
+int s3d_dnerf_hyper_grid_backward(const uint16_t* grad_feat, const void* dy_da, uint32_t B, uint32_t L, int dtype,
+                                  float grad_scale, void* grad_levels, float* grad_ambient, void* workspace,
+                                  size_t workspace_bytes, const int32_t* n_valid, s3d_stream_t stream);
+
 /* ------------------------------------------------------------------ sampling without the occupancy grid (csrc/hiersample.hip;
  * DESIGN.md "The sampling path without the grid")
  * `NeRFRenderer.run` of the reference (nerf/renderer.py:125-253) and `sample_pdf` (:12-46).  S = num_steps >= 3, U = upsample_steps,

@@ -2,7 +2,7 @@
 
 
 def get_encoder(encoding, input_dim=3, multires=6, degree=4, num_levels=16, level_dim=2, base_resolution=16,
-                log2_hashmap_size=19, desired_resolution=2048, align_corners=False, **kwargs):
+                log2_hashmap_size=19, desired_resolution=2048, align_corners=False, interpolation="linear", **kwargs):
     if encoding == "None":
         return (lambda x, **kw: x), input_dim
     if encoding == "frequency":
@@ -16,7 +16,8 @@ def get_encoder(encoding, input_dim=3, multires=6, degree=4, num_levels=16, leve
         enc = GridEncoder(input_dim=input_dim, num_levels=num_levels, level_dim=level_dim,
                           base_resolution=base_resolution, log2_hashmap_size=log2_hashmap_size,
                           desired_resolution=desired_resolution,
-                          gridtype="hash" if encoding == "hashgrid" else "tiled", align_corners=align_corners)
+                          gridtype="hash" if encoding == "hashgrid" else "tiled", align_corners=align_corners,
+                          interpolation=interpolation)  # (`interpolation`: a build extension; the reference's factory never passes it)
     else:
         raise NotImplementedError(
             "Unknown encoding mode, choose from [None, frequency, sphere_harmonics, hashgrid, tiledgrid]")

@@ -59,6 +59,7 @@ EXPORTS = [
     "s3d_dnerf_encode_forward", "s3d_dnerf_warp_grid_workspace_size", "s3d_dnerf_warp_grid_forward", "s3d_dnerf_split_grad",
     "s3d_dnerf_warp_backward",
     "s3d_dnerf_basis_mid_forward", "s3d_dnerf_basis_mid_workspace_size", "s3d_dnerf_basis_mid_backward",
+    "s3d_dnerf_hyper_grid_forward", "s3d_dnerf_hyper_backward_workspace_size", "s3d_dnerf_hyper_grid_backward",
     "s3d_hier_max_samples", "s3d_hier_coarse_samples", "s3d_hier_upsample", "s3d_hier_weights", "s3d_hier_composite_forward",
     "s3d_hier_composite_backward",
     "s3d_mesh_sdf_tile", "s3d_mesh_sdf", "s3d_sdf_sample_points", "s3d_sdf_mape_workspace_size", "s3d_sdf_mape_forward_backward",
@@ -95,7 +96,8 @@ def lib():
                      "s3d_sweep_update_workspace_size", "s3d_sweep_draw_native_workspace_size", "s3d_vm_backward_bins_workspace_size", "s3d_vm_backward_stage_bytes",
                      "s3d_weighted_abs_sum_workspace_size", "s3d_background_backward_workspace_size",
                      "s3d_vm_background_backward_workspace_size", "s3d_mc_workspace_bytes",
-                     "s3d_dnerf_warp_grid_workspace_size", "s3d_dnerf_basis_mid_workspace_size", "s3d_sdf_mape_workspace_size"):
+                     "s3d_dnerf_warp_grid_workspace_size", "s3d_dnerf_basis_mid_workspace_size", "s3d_dnerf_hyper_backward_workspace_size",
+                     "s3d_sdf_mape_workspace_size"):
             getattr(l, name).restype = C.c_size_t
         l.s3d_vm_backward_max_bins.restype = C.c_uint32
         l.s3d_grid_level_scales.restype = None
@@ -2248,6 +2250,72 @@ class DnerfBasisBackend:
         _check(lib().s3d_dnerf_basis_mid_backward(_p(grad_color_in), _p(grad_sigma), _p(h), _p(sigma_basis), _u(B), _p(grad_h),
                                                   _p(grad_sigma_basis), _p(ws), C.c_size_t(nb), _nv(n_valid), _stream()),
                "dnerf_basis_mid_backward")
+
+
+class DnerfHyperBackend:
+    """The 4-D grid lookup of the D-NeRF hyper backbone (csrc/dnerf_hyper.hip; include/seal3d_hip.h): features, the 4-D input row
+    and the ambient column of the Jacobian from one launch; the transposition of the feature gradient and grad_ambient from one."""
+
+    MAX_LEVELS = 16
+
+    @staticmethod
+    def _table(embeddings, offsets, who):
+        _need(offsets, torch.int32, "offsets")
+        L = offsets.shape[0] - 1
+        if embeddings.dim() != 2 or embeddings.shape[1] != 2 or embeddings.dtype not in (torch.float16, torch.float32) \
+                or not 1 <= L <= DnerfHyperBackend.MAX_LEVELS:
+            raise RuntimeError(f"{who}: a table of two fp16 / fp32 features per row, 1 <= L <= 16")
+        return L
+
+    @staticmethod
+    def grid_forward(x, ambient, embeddings, offsets, S, H, gridtype, align_corners, interp, bound, feat, x4=None, dy_da=None,
+                     n_valid=None):
+        """feat fp16 [B, 2L] (+ x4 fp32 [B, 4] = [x | ambient], dy_da [B, L, 2] in the table's dtype) from x fp32 [B, 3] and the one
+        fp32 device word `ambient`"""
+        _need(x, torch.float32, "x"); _need(ambient, torch.float32, "ambient"); _need(feat, torch.float16, "feat")
+        L = DnerfHyperBackend._table(embeddings, offsets, "hyper grid_forward")
+        B = x.shape[0]
+        if x.dim() != 2 or x.shape[1] != 3 or ambient.numel() != 1 or tuple(feat.shape) != (B, 2 * L):
+            raise RuntimeError(f"hyper grid_forward: x [B, 3], ambient of one element, feat [B, {2 * L}]")
+        if x4 is not None:
+            _need(x4, torch.float32, "x4")
+            if tuple(x4.shape) != (B, 4):
+                raise RuntimeError("hyper grid_forward: x4 must be [B, 4]")
+        if dy_da is not None and (dy_da.dtype != embeddings.dtype or tuple(dy_da.shape) != (B, L, 2)):
+            raise RuntimeError("hyper grid_forward: dy_da must be [B, L, 2] in the table's dtype")
+        _check(lib().s3d_dnerf_hyper_grid_forward(_p(x), _p(ambient), _p(embeddings), _p(offsets), _u(B), _u(L), _f(S), _u(H),
+                                                  _u(gridtype), C.c_int(int(align_corners)), _u(interp), C.c_int(_dt(embeddings)),
+                                                  _f(bound), _p(feat), _p(x4), _p(dy_da), _nv(n_valid), _stream()),
+               "dnerf_hyper_grid_forward")
+
+    @staticmethod
+    def backward_workspace_size(B):
+        return int(lib().s3d_dnerf_hyper_backward_workspace_size(_u(B)))
+
+    @staticmethod
+    def grid_backward(grad_feat, dy_da, grad_scale, grad_levels, grad_ambient=None, n_valid=None):
+        """grad_levels [L, B, 2] (fp16 or fp32) = grad_feat fp16 [B, 2L] transposed; grad_ambient fp32 [1] = grad_scale * the
+        fixed-order sum of grad_feat . dy_da over the live rows (written when dy_da and grad_ambient are both given)"""
+        _need(grad_feat, torch.float16, "grad_feat")
+        if grad_levels.dim() != 3 or grad_levels.shape[2] != 2 or not 1 <= grad_levels.shape[0] <= DnerfHyperBackend.MAX_LEVELS \
+                or grad_levels.dtype not in (torch.float16, torch.float32):
+            raise RuntimeError("hyper grid_backward: grad_levels must be [L <= 16, B, 2], fp16 or fp32")
+        L, B = grad_levels.shape[0], grad_levels.shape[1]
+        if tuple(grad_feat.shape) != (B, 2 * L):
+            raise RuntimeError(f"hyper grid_backward: grad_feat must be [B, {2 * L}]")
+        if dy_da is not None and (dy_da.dtype != grad_levels.dtype or tuple(dy_da.shape) != (B, L, 2)):
+            raise RuntimeError("hyper grid_backward: dy_da must be [B, L, 2] in grad_levels' dtype")
+        ws, nb = None, 0
+        if grad_ambient is not None:
+            _need(grad_ambient, torch.float32, "grad_ambient")
+            if grad_ambient.numel() != 1:
+                raise RuntimeError("hyper grid_backward: grad_ambient must hold one element")
+            if dy_da is not None:
+                nb = DnerfHyperBackend.backward_workspace_size(B)
+                ws = _ws.get(nb, grad_feat.device)
+        _check(lib().s3d_dnerf_hyper_grid_backward(_p(grad_feat), _p(dy_da), _u(B), _u(L), C.c_int(_dt(grad_levels)), _f(grad_scale),
+                                                   _p(grad_levels), _p(grad_ambient), _p(ws), C.c_size_t(nb), _nv(n_valid), _stream()),
+               "dnerf_hyper_grid_backward")
 
 
 class HierBackend:
