@@ -946,6 +946,20 @@ int s3d_rgba_targets(const void* images, int images_dtype, uint32_t R, int rando
 int s3d_error_map_update(float* error_map, uint32_t n_img, const int64_t* index, const int64_t* inds_coarse, uint32_t B, uint32_t N,
                          const float* image, const float* weights_sum, const float* gt, const float* bg_rgb, const float* bg_rays,
                          const float* depth, const float* gt_depth, float depth_weight, s3d_stream_t stream);
+/* Build extension — Seal-3D's custom-pose batches (SealNeRF/provider.py:145-178): B orbit cameras looking at look_at from
+ * distance radius, and every ray of each camera's rH x rW frame, in one launch.  Pose b, nerf/provider.py:57-91 `rand_poses`
+ * in its expression order (fp32, no contraction): theta = u_t * fl(theta1 - theta0) + theta0, phi likewise; offset = radius *
+ * (sin theta sin phi, cos theta, sin theta cos phi); forward = -offset / (|offset| + 1e-10); right = normalize(forward x
+ * (0, -1, 0)); up = normalize(right x forward); poses_out [B,4,4] (optional) = columns right, up, forward, offset + look_at.
+ * rays_o, rays_d [B, rH*rW, 3] (16-byte aligned), pixels in row-major order: get_rays(pose, intrinsics, rH, rW, -1), formed by
+ * the code s3d_sample_train_rays forms a winner's ray with.  intrinsics: 4 HOST floats fx, fy, cx, cy of the rH x rW frame;
+ * look_at: 3 HOST floats or NULL (the origin).  Randomness: u_t = (float)(hash_u32(pcg_hash(seed ^ 0x1B873593), ctl[0], b) >> 8)
+ * * 2^-24, u_p the same with 0xCC9E2D51 (hash_u32, pcg_hash: s3d_rgba_targets); ctl [2] int32 on the device = {step, 0}: the
+ * last workgroup advances ctl[0], so a captured launch draws fresh poses on every replay.  Test entry: u_pose [B,2] in [0, 1)
+ * replaces the hash and leaves ctl alone.  B = 0 or an empty frame: nothing is launched. */
+int s3d_orbit_rays(uint32_t B, uint32_t rH, uint32_t rW, const float* intrinsics, const float* look_at, float radius,
+                   double theta0, double theta1, double phi0, double phi1, uint32_t seed, int32_t* ctl, const float* u_pose,
+                   float* poses_out, float* rays_o, float* rays_d, s3d_stream_t stream);
 
 /* Build extension — mesh export: marching cubes over a dense fp32 volume u [nx,ny,nz] (C order, z fastest); DESIGN.md §8.
  * A grid point is solid iff u > iso, with NaN read as 0 and +-inf as +-FLT_MAX (u is not modified).  Point p owns its +x, +y,

@@ -21,9 +21,17 @@
 //    sampler's other keys uses (pixels 0x5BD1E995, rows 0x632BE5AB, fine perturb 0xA511E9B3), so what they draw for a seed
 //    does not move.  The sampler's RGBA form is the same kernel body (template flag): one launch gathers four channels, blends,
 //    and writes gt and bg.
+//  * s3d_orbit_rays: Seal-3D's custom-pose batches (SealNeRF/provider.py:145-178) — B orbit cameras around look_at drawn as
+//    nerf/provider.py:57-91 `rand_poses` draws them (theta_key = pcg_hash(seed ^ 0x1B873593), phi_key = pcg_hash(seed ^
+//    0xCC9E2D51), u = (float)(hash_u32(key, step, b) >> 8) * 2^-24: two more constants of their own) and every ray of each
+//    pose's rH x rW frame, formed by the sampler's own ray function.  A pose's frame spans many workgroups: each recomputes
+//    the pose (one thread, handed round through LDS), and every lane stores 16 aligned bytes of the flat [B, rH rW, 3] stream.
 #include "s3d_common.hpp"
 
 #include <math.h>
+
+#include <algorithm>
+#include <cmath>
 
 namespace s3d {
 namespace {
@@ -143,18 +151,28 @@ struct SampleArgs {
     float fx, fy, cx, cy, sx, sy;
 };
 
-// the ray of pixel `pix` into row b's slot n (get_rays: pixel centre, normalised direction, cam2world rotation) + targets
+// world direction of the ray through pixel `pix` of a frame W wide (get_rays: pixel centre, normalised direction, cam2world
+// rotation; pose = rows of the 4 x 4 matrix) — the one copy the sampler and the orbit-frame kernel both form their rays with
+__device__ __forceinline__ void pixel_ray_dir(uint32_t pix, uint32_t W, float fx, float fy, float cx, float cy,
+                                              const float* __restrict__ pose, float d[3]) {
+    const float i = (float)(pix % W) + 0.5f, j = (float)(pix / W) + 0.5f;
+    const float x = (i - cx) / fx * 1.0f, y = (j - cy) / fy * 1.0f, z = 1.0f;
+    const float nrm = sqrtf(x * x + y * y + z * z);
+    const float dx = x / nrm, dy = y / nrm, dz = z / nrm;
+#pragma unroll
+    for (int k = 0; k < 3; k++) d[k] = dx * pose[k * 4] + dy * pose[k * 4 + 1] + dz * pose[k * 4 + 2];
+}
+
+// the ray of pixel `pix` into row b's slot n + targets
 template <bool kRgba>
 __device__ __forceinline__ void emit_ray(const SampleArgs& a, uint32_t b, uint32_t img, uint32_t n, uint32_t pix,
                                          const float* __restrict__ pose, uint32_t step) {
     const size_t o = (size_t)b * a.N + n;
-    const float i = (float)(pix % a.W) + 0.5f, j = (float)(pix / a.W) + 0.5f;
-    const float x = (i - a.cx) / a.fx * 1.0f, y = (j - a.cy) / a.fy * 1.0f, z = 1.0f;
-    const float nrm = sqrtf(x * x + y * y + z * z);
-    const float dx = x / nrm, dy = y / nrm, dz = z / nrm;
+    float d[3];
+    pixel_ray_dir(pix, a.W, a.fx, a.fy, a.cx, a.cy, pose, d);
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-        a.rays_d[o * 3 + k] = dx * pose[k * 4] + dy * pose[k * 4 + 1] + dz * pose[k * 4 + 2];
+        a.rays_d[o * 3 + k] = d[k];
         a.rays_o[o * 3 + k] = pose[k * 4 + 3];
     }
     a.inds[o] = (int64_t)pix;
@@ -345,6 +363,132 @@ k_error_map_update(float* __restrict__ error_map, const int64_t* __restrict__ in
     }
 }
 
+constexpr uint32_t kThetaKeySalt = 0x1B873593u, kPhiKeySalt = 0xCC9E2D51u;
+constexpr uint32_t kOrbitBlock = 256;
+// workgroups per pose at most; larger frames go round the item loop.  Every workgroup ends in advance_step's fence and
+// arrival (about 27 ns each, one after the other): 1,875 of them made an 800 x 800 frame 60 us, 256 make it 19 us, and
+// without the counter (explicit uniforms) the frame is written in 10 us either way (profiles/custom_pose.md)
+constexpr uint32_t kOrbitMaxChunks = 256;
+
+struct OrbitArgs {
+    const float* u_pose;  // [B, 2] or NULL (test entry: explicit uniforms of theta, phi)
+    int32_t* ctl;         // {step, arrivals} or NULL (explicit uniforms)
+    float* poses_out;     // [B, 4, 4] or NULL
+    float* rays_o;        // [B, HW, 3], 16-byte aligned
+    float* rays_d;
+    uint32_t W, HW, chunks, seed;
+    float fx, fy, cx, cy;
+    float radius, th_lo, th_span, ph_lo, ph_span, look[3];
+};
+
+__device__ __forceinline__ void normalize3(const float v[3], float out[3]) {
+    const float n = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]) + 1e-10f;
+#pragma unroll
+    for (int k = 0; k < 3; k++) out[k] = v[k] / n;
+}
+
+__device__ __forceinline__ void cross3(const float a[3], const float b[3], float out[3]) {
+    out[0] = a[1] * b[2] - a[2] * b[1];
+    out[1] = a[2] * b[0] - a[0] * b[2];
+    out[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// nerf/provider.py:57-91 `rand_poses` for one pair of uniforms, its expression order in fp32, + look_at on the centre: the
+// 16 values of the cam2world matrix (columns right, up, forward, centre)
+__device__ __forceinline__ void orbit_pose(const OrbitArgs& a, float u_theta, float u_phi, float* pose) {
+    const float theta = u_theta * a.th_span + a.th_lo, phi = u_phi * a.ph_span + a.ph_lo;
+    const float st = sinf(theta), ct = cosf(theta), sp = sinf(phi), cp = cosf(phi);
+    const float off[3] = {a.radius * st * sp, a.radius * ct, a.radius * st * cp};
+    const float up0[3] = {0.0f, -1.0f, 0.0f};
+    float fwd[3], right[3], up[3], tmp[3];
+    normalize3(off, fwd);
+#pragma unroll
+    for (int k = 0; k < 3; k++) fwd[k] = -fwd[k];
+    cross3(fwd, up0, tmp);
+    normalize3(tmp, right);
+    cross3(right, fwd, tmp);
+    normalize3(tmp, up);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        pose[k * 4] = right[k];
+        pose[k * 4 + 1] = up[k];
+        pose[k * 4 + 2] = fwd[k];
+        pose[k * 4 + 3] = off[k] + a.look[k];
+    }
+    pose[12] = 0.0f; pose[13] = 0.0f; pose[14] = 0.0f; pose[15] = 1.0f;
+}
+
+// s3d_orbit_rays: workgroup (b, chunk) = blockIdx.x.  The rays of pose b are one stream of 3 HW floats per output; a work item
+// is one 16-byte aligned group of four of them (parts of two neighbouring rays), so that a wave's store instruction covers
+// 1 KiB of consecutive addresses.  The first and the last item of a pose may reach into the neighbouring pose's floats (3 HW
+// need not be a multiple of 4): only there, each float inside the pose is stored on its own.
+__global__ void __launch_bounds__(kOrbitBlock) k_orbit_rays(OrbitArgs a) {
+    __shared__ float s_pose[16];
+    __shared__ uint32_t s_step;
+    const uint32_t t = threadIdx.x, b = blockIdx.x / a.chunks, chunk = blockIdx.x % a.chunks;
+    if (t == 0) {
+        const uint32_t step = a.ctl ? (uint32_t)a.ctl[0] : 0u;
+        s_step = step;
+        float ut, up;
+        if (a.u_pose) {
+            ut = a.u_pose[(size_t)b * 2];
+            up = a.u_pose[(size_t)b * 2 + 1];
+        } else {
+            ut = (float)(hash_u32(pcg_hash(a.seed ^ kThetaKeySalt), step, b) >> 8) * (1.0f / 16777216.0f);
+            up = (float)(hash_u32(pcg_hash(a.seed ^ kPhiKeySalt), step, b) >> 8) * (1.0f / 16777216.0f);
+        }
+        orbit_pose(a, ut, up, s_pose);
+        if (chunk == 0 && a.poses_out) {
+#pragma unroll
+            for (int k = 0; k < 16; k++) a.poses_out[(size_t)b * 16 + k] = s_pose[k];
+        }
+    }
+    __syncthreads();
+    float pose[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) pose[k] = s_pose[k];
+    const float o[3] = {pose[3], pose[7], pose[11]};
+    const uint64_t F = 3ull * a.HW, lo = (uint64_t)b * F, hi = lo + F;
+    const uint64_t q1 = (hi + 3u) >> 2;  // items [lo / 4, q1) hold a float of this pose
+    for (uint64_t q = (lo >> 2) + (uint64_t)chunk * kOrbitBlock + t; q < q1; q += (uint64_t)a.chunks * kOrbitBlock) {
+        const uint64_t g0 = q << 2;
+        const uint32_t f0 = (uint32_t)((g0 > lo ? g0 : lo) - lo);  // the item's first float inside the pose
+        const uint32_t r0 = f0 / 3u;
+        float d0[3], d1[3];  // the item's floats belong to rays r0 and r0 + 1 (the latter may lie past the frame: never stored)
+        pixel_ray_dir(r0, a.W, a.fx, a.fy, a.cx, a.cy, pose, d0);
+        pixel_ray_dir(r0 + 1u, a.W, a.fx, a.fy, a.cx, a.cy, pose, d1);
+        float vd[4], vo[4];
+        bool in[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+            const uint64_t g = g0 + j;
+            in[j] = g >= lo && g < hi;
+            const uint32_t f = in[j] ? (uint32_t)(g - lo) : f0;
+            const uint32_t r = f / 3u, c = f - 3u * r;
+            const float a0 = r == r0 ? d0[0] : d1[0], a1 = r == r0 ? d0[1] : d1[1], a2 = r == r0 ? d0[2] : d1[2];
+            vd[j] = c == 0u ? a0 : (c == 1u ? a1 : a2);
+            vo[j] = c == 0u ? o[0] : (c == 1u ? o[1] : o[2]);
+        }
+        if (in[0] && in[3]) {
+            *reinterpret_cast<float4*>(a.rays_d + g0) = make_float4(vd[0], vd[1], vd[2], vd[3]);
+            *reinterpret_cast<float4*>(a.rays_o + g0) = make_float4(vo[0], vo[1], vo[2], vo[3]);
+        } else {
+#pragma unroll
+            for (uint32_t j = 0; j < 4; j++) {
+                if (in[j]) {
+                    a.rays_d[g0 + j] = vd[j];
+                    a.rays_o[g0 + j] = vo[j];
+                }
+            }
+        }
+    }
+    // the last workgroup to finish advances the step number (every workgroup read it above)
+    if (a.ctl) {
+        __syncthreads();
+        if (t == 0) advance_step(a.ctl, s_step);
+    }
+}
+
 }  // namespace
 }  // namespace s3d
 
@@ -445,4 +589,31 @@ S3D_EXPORT int s3d_error_map_update(float* error_map, uint32_t n_img, const int6
     hipLaunchKernelGGL(k_error_map_update, dim3(1), dim3(kUpdateBlock), 0, as_stream(stream), error_map, index, inds_coarse, B, N,
                        n_img, image, weights_sum, gt, b0, b1, b2, bg_rays, depth, gt_depth, depth_weight);
     return check_launch("k_error_map_update");
+}
+
+S3D_EXPORT int s3d_orbit_rays(uint32_t B, uint32_t rH, uint32_t rW, const float* intrinsics, const float* look_at, float radius,
+                              double theta0, double theta1, double phi0, double phi1, uint32_t seed, int32_t* ctl,
+                              const float* u_pose, float* poses_out, float* rays_o, float* rays_d, s3d_stream_t stream) {
+    if (B == 0 || rH == 0 || rW == 0) return S3D_OK;
+    S3D_REQUIRE(intrinsics && rays_o && rays_d, "s3d_orbit_rays: null argument");
+    S3D_REQUIRE(ctl || u_pose, "s3d_orbit_rays: needs ctl or the explicit uniforms u_pose");
+    S3D_REQUIRE(((reinterpret_cast<uintptr_t>(rays_o) | reinterpret_cast<uintptr_t>(rays_d)) & 15u) == 0,
+                "s3d_orbit_rays: rays_o and rays_d must be 16-byte aligned");
+    S3D_REQUIRE(std::isfinite(radius) && std::isfinite(theta0) && std::isfinite(theta1) && std::isfinite(phi0) && std::isfinite(phi1),
+                "s3d_orbit_rays: radius and the angle ranges must be finite");
+    S3D_REQUIRE((uint64_t)rH * rW * 3 < (1ull << 32), "s3d_orbit_rays: frame too large");
+    OrbitArgs a;
+    a.u_pose = u_pose; a.ctl = u_pose ? nullptr : ctl;  // (explicit uniforms leave ctl alone)
+    a.poses_out = poses_out; a.rays_o = rays_o; a.rays_d = rays_d;
+    a.W = rW; a.HW = rH * rW; a.seed = seed;
+    a.fx = intrinsics[0]; a.fy = intrinsics[1]; a.cx = intrinsics[2]; a.cy = intrinsics[3];
+    a.radius = radius;
+    a.th_lo = (float)theta0; a.th_span = (float)(theta1 - theta0);  // (torch: the Python difference, rounded once)
+    a.ph_lo = (float)phi0; a.ph_span = (float)(phi1 - phi0);
+    for (int k = 0; k < 3; k++) a.look[k] = look_at ? look_at[k] : 0.0f;
+    // a pose's 3 HW floats touch at most 3 HW / 4 + 2 aligned groups of four
+    a.chunks = (uint32_t)std::min<uint64_t>(div_up<uint64_t>(3ull * a.HW / 4 + 2, kOrbitBlock), kOrbitMaxChunks);
+    S3D_REQUIRE((uint64_t)B * a.chunks < (1ull << 31), "s3d_orbit_rays: too many poses for one launch");
+    hipLaunchKernelGGL(k_orbit_rays, dim3(B * a.chunks), dim3(kOrbitBlock), 0, as_stream(stream), a);
+    return check_launch("k_orbit_rays");
 }

@@ -44,7 +44,8 @@ class DeviceSampling:
         torch.multinomial without replacement, winners in ascending cell order); otherwise pixels are uniform.  RGBA frames
         (nerf/utils.py:465-474) are blended in the same launch: `images` is the target on a per-pixel random background, which
         is returned as `bg_color` [B,N,3] (the dataset's `random_bg=False`, for a model with bg_radius > 0: blended onto 1, no
-        `bg_color`).  The background's draws are keyed by `seed`: ranks of a data-parallel run use different seeds."""
+        `bg_color`).  The background's draws are keyed by `seed`: ranks of a data-parallel run use different seeds (so do the
+        poses of sealnerf.provider.SealRandomDataset.sample, which replaces this method with one s3d_orbit_rays launch)."""
         import s3d_hip
         if not self.poses.is_cuda:
             raise RuntimeError("sample() runs on the GPU: the dataset's poses must live there (use collate() on the CPU)")

@@ -47,6 +47,27 @@ def orbit_poses(n, seed=0, radius=LEGO_RADIUS, theta_range=(math.pi / 6, math.pi
     return poses.to(device)
 
 
+def rand_poses(size, device, radius=1, theta_range=(math.pi / 3, 2 * math.pi / 3), phi_range=(0, 2 * math.pi), look_at=None,
+               generator=None):
+    """`size` random orbit cameras (nerf/provider.py:57-91, its expression order in fp32): cam2world [size, 4, 4] at distance
+    `radius` (a number or a 0-d tensor) looking at `look_at` ([3]; None: the origin — then, under the same torch.manual_seed,
+    the reference's poses bit for bit).  `look_at` translates the camera and leaves the rotation as it is: the extension that
+    SealNeRF/provider.py:158-159 calls for.  theta is drawn first, then phi, from `generator` (None: torch's global one)."""
+    thetas = torch.rand(size, device=device, generator=generator) * (theta_range[1] - theta_range[0]) + theta_range[0]
+    phis = torch.rand(size, device=device, generator=generator) * (phi_range[1] - phi_range[0]) + phi_range[0]
+    offsets = torch.stack([radius * torch.sin(thetas) * torch.sin(phis),
+                           radius * torch.cos(thetas),
+                           radius * torch.sin(thetas) * torch.cos(phis)], dim=-1)
+    forward = -_normalize(offsets)
+    up = torch.tensor([0.0, -1.0, 0.0], device=device).unsqueeze(0).repeat(size, 1)
+    right = _normalize(torch.cross(forward, up, dim=-1))
+    up = _normalize(torch.cross(right, forward, dim=-1))
+    poses = torch.eye(4, dtype=torch.float, device=device).unsqueeze(0).repeat(size, 1, 1)
+    poses[:, :3, :3] = torch.stack((right, up, forward), dim=-1)
+    poses[:, :3, 3] = offsets if look_at is None else offsets + torch.as_tensor(look_at, dtype=torch.float, device=device)
+    return poses
+
+
 def get_rays(poses, intrinsics, H, W, N=-1, error_map=None, generator=None):
     """Pixel-centre rays (nerf/utils.py:54-139 without patches).
     poses [B,4,4] cam2world; returns dict(rays_o [B,n,3], rays_d [B,n,3], inds [B,n]).

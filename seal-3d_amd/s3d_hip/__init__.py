@@ -12,6 +12,7 @@ There is NO CPU fallback: if the library is missing or a tensor is not on the
 GPU the call fails loudly.
 """
 import ctypes as C
+import math
 import os
 import subprocess
 import weakref
@@ -54,7 +55,7 @@ EXPORTS = [
     "s3d_composite_rays_train_loss_bg", "s3d_bg_targets_rays",
     "s3d_background_forward", "s3d_background_backward_workspace_size", "s3d_background_backward",
     "s3d_vm_background_forward", "s3d_vm_background_backward_workspace_size", "s3d_vm_background_backward",
-    "s3d_sample_train_rays", "s3d_error_map_update", "s3d_sample_train_rays_rgba", "s3d_rgba_targets",
+    "s3d_sample_train_rays", "s3d_error_map_update", "s3d_sample_train_rays_rgba", "s3d_rgba_targets", "s3d_orbit_rays",
     "s3d_mc_workspace_bytes", "s3d_mc_count", "s3d_mc_emit",
     "s3d_dnerf_encode_forward", "s3d_dnerf_warp_grid_workspace_size", "s3d_dnerf_warp_grid_forward", "s3d_dnerf_split_grad",
     "s3d_dnerf_warp_backward",
@@ -1391,8 +1392,8 @@ class NgpHeadBackend:
 
 
 class RaySampleBackend:
-    """csrc/raysample.hip — training rays drawn on the device (nerf/utils.py:92-114 with or without an error map) and the
-    error map's EMA update (nerf/utils.py:506-528)"""
+    """csrc/raysample.hip — training rays drawn on the device (nerf/utils.py:92-114 with or without an error map), the
+    error map's EMA update (nerf/utils.py:506-528) and the frames of generated orbit poses (SealNeRF/provider.py:145-178)"""
 
     @staticmethod
     def sample_train_rays(error_map, index, N, H, W, poses, intrinsics, rays_o, rays_d, inds, inds_coarse=None, images=None,
@@ -1464,6 +1465,30 @@ class RaySampleBackend:
         _check(lib().s3d_rgba_targets(_p(images), C.c_int(F16 if images.dtype == torch.float16 else F32), _u(R),
                                       C.c_int(1 if random_bg else 0), _u(int(seed) & 0xFFFFFFFF), _p(ctl), _p(u_bg), _p(gt), _p(bg),
                                       _stream()), "s3d_rgba_targets")
+
+    @staticmethod
+    def orbit_rays(B, rH, rW, intrinsics, rays_o, rays_d, poses_out=None, look_at=None, radius=1.0, theta_range=(math.pi / 3, 2 * math.pi / 3),
+                   phi_range=(0.0, 2 * math.pi), seed=0, ctl=None, u_pose=None):
+        """seal3d_hip.h: s3d_orbit_rays.  B orbit poses around `look_at` (3 host numbers; None: the origin) at distance `radius`
+        and the rays of each pose's rH x rW frame: rays_o, rays_d [B, rH*rW, 3], poses_out [B, 4, 4] (optional), all fp32 and
+        preallocated.  `intrinsics`: fx, fy, cx, cy of the rH x rW frame.  The draw is keyed by (`seed`, ctl[0]); u_pose [B, 2]:
+        explicit uniforms of theta and phi (test entry, ctl is left alone)"""
+        B, rH, rW = int(B), int(rH), int(rW)
+        for t, n, w in ((rays_o, "rays_o", rH * rW * 3), (rays_d, "rays_d", rH * rW * 3), (poses_out, "poses_out", 16), (u_pose, "u_pose", 2)):
+            if t is not None:
+                _need(t, torch.float32, n)
+                if t.numel() != B * w:
+                    raise RuntimeError(f"orbit_rays: {n} must hold {B} x {w} values")
+        if ctl is not None:
+            _need(ctl, torch.int32, "ctl")
+            if ctl.numel() < 2:
+                raise RuntimeError("orbit_rays: ctl holds {step, 0}")
+        intr = (C.c_float * 4)(*[float(v) for v in intrinsics])
+        look = None if look_at is None else (C.c_float * 3)(*[float(v) for v in look_at])
+        _check(lib().s3d_orbit_rays(_u(B), _u(rH), _u(rW), intr, look, C.c_float(float(radius)), C.c_double(float(theta_range[0])),
+                                    C.c_double(float(theta_range[1])), C.c_double(float(phi_range[0])), C.c_double(float(phi_range[1])),
+                                    _u(int(seed) & 0xFFFFFFFF), _p(ctl), _p(u_pose), _p(poses_out), _p(rays_o), _p(rays_d), _stream()),
+               "s3d_orbit_rays")
 
     @staticmethod
     def error_map_update(error_map, index, inds_coarse, image, gt, weights_sum=None, bg=None, depth=None, gt_depth=None,

@@ -598,14 +598,38 @@ class GraphedSealTrainer(SealSteps, GraphedTrainer):
     def train_step(self, rays_o, rays_d, gt_rgb=None, gt_depth=None, bg_color=1, index=None, inds_coarse=None):
         self.end_pretraining()
         if gt_rgb is None:
-            mode = self.online_proxy_mode
-            ok = (self.graph_proxy and self.fp16 and rays_o.is_cuda and rays_o.numel() == self.s_ro.numel()
-                  and (mode == "train" or (mode is None and self.teacher.training))  # (the one-march branch has static extents)
-                  and self.teacher.honours_row_limit_under_autocast(rays_o.numel() // 3 * self.render_kwargs["max_steps"]))
-            if ok:
+            if rays_o.is_cuda and rays_o.numel() == self.s_ro.numel() and self._proxy_graphable():
                 torch._foreach_copy_([self.s_ro, self.s_rd], [rays_o.reshape(-1, 3), rays_d.reshape(-1, 3)])
                 self._proxy_replay()
                 gt_rgb, gt_depth = self.s_gt, self.s_depth
             else:
                 gt_rgb, gt_depth = self.proxy_truth(rays_o, rays_d)
         return GraphedTrainer.train_step(self, rays_o, rays_d, (gt_rgb, gt_depth), bg_color, index=index, inds_coarse=inds_coarse)
+
+    def _proxy_graphable(self):
+        """the conditions under which train_step's proxy render of a num_rays batch is replayed from its graph"""
+        mode = self.online_proxy_mode
+        return (self.graph_proxy and self.fp16 and self.s_ro.is_cuda
+                and (mode == "train" or (mode is None and self.teacher.training))
+                and self.teacher.honours_row_limit_under_autocast(self.s_ro.shape[0] * self.render_kwargs["max_steps"]))
+
+    def train_step_random(self, dataset, index=(0,)):
+        """one custom-pose fine-tuning step (`--custom_pose`, main_SealNeRF.py:316-340) on a sealnerf.provider.SealRandomDataset:
+        the dataset's sampler launch draws a pose and writes its frame's rays straight into s_ro / s_rd, the teacher's proxy
+        graph renders the targets from them into s_gt / s_depth, and the student's step is replayed — three device-side pieces
+        with no host data, read-back or copy in between.  Where train_step would render the proxy eagerly (`_proxy_graphable`),
+        so does this, into the same static buffers.  The step's poses stay in `self.s_poses`."""
+        n = self.s_ro.shape[0]
+        if len(index) * dataset.rays_per_batch != n:
+            raise ValueError(f"train_step_random: the dataset's frames have {dataset.rays_per_batch} rays per pose "
+                             f"({len(index)} pose(s) a step), this trainer was built for num_rays = {n}")
+        if getattr(self, "s_poses", None) is None or self.s_poses.shape[0] != len(index):
+            self.s_poses = torch.zeros(len(index), 4, 4, device=self.s_ro.device)
+        self.end_pretraining()
+        dataset.sample(index, out={"rays_o": self.s_ro.view(len(index), -1, 3), "rays_d": self.s_rd.view(len(index), -1, 3),
+                                   "poses": self.s_poses})
+        if self._proxy_graphable():
+            self._proxy_replay()
+        else:
+            self.proxy_truth(self.s_ro, self.s_rd, self.s_gt, self.s_depth)
+        return self.train_step(self.s_ro, self.s_rd, self.s_gt, self.s_depth)
