@@ -960,6 +960,41 @@ int s3d_error_map_update(float* error_map, uint32_t n_img, const int64_t* index,
 int s3d_orbit_rays(uint32_t B, uint32_t rH, uint32_t rW, const float* intrinsics, const float* look_at, float radius,
                    double theta0, double theta1, double phi0, double phi1, uint32_t seed, int32_t* ctl, const float* u_pose,
                    float* poses_out, float* rays_o, float* rays_d, s3d_stream_t stream);
+/* Build extension — interactive preview (nerf/utils.py:754-820 `test_gui`, SealNeRF/gui.py `NeRFGUI.prepare_buffer`,
+ * `test_step`, `get_mask_pos`); DESIGN.md §5 "Interactive preview".
+ * s3d_frame_rays: rays_o, rays_d [rH*rW, 3] (16-byte aligned) of the ONE camera `pose` (16 HOST floats, a row-major 4 x 4
+ * cam2world matrix; they travel in the launch's argument block) = get_rays(pose, intrinsics, rH, rW, -1), pixels in row-major
+ * order, formed by the code s3d_sample_train_rays forms a winner's ray with.  intrinsics: 4 HOST floats fx, fy, cx, cy of the
+ * rH x rW frame.  An empty frame: nothing is launched. */
+int s3d_frame_rays(const float* pose, const float* intrinsics, uint32_t rH, uint32_t rW, float* rays_o, float* rays_d,
+                   s3d_stream_t stream);
+/* s3d_preview_resolve: everything between the renderer's output image [rH,rW,3], depth [rH,rW] (fp32) and the displayed
+ * frame, one pass over the H x W destination (rH <= H, rW <= W).  Destination pixel (y, x) reads source pixel
+ * (min((int)floorf(y * fl((float)rH / H)), rH - 1), the same for x): F.interpolate(mode='nearest').  frame_depth [H,W] =
+ * nan_to_num(depth) (NaN -> 0, +-inf -> +-FLT_MAX); frame_image [H,W,3] = the colours, through linear_to_srgb (x < 0.0031308 ?
+ * 12.92 x : 1.055 x^0.41666 - 0.055) when to_srgb; where that is a plain copy of image (rH == H, rW == W, no conversion)
+ * frame_image may be NULL and is then not written.  pos [H,W,3] (optional; needs rays_o, rays_d [H*W,3] and rH == H, rW == W)
+ * = rays_o + fl(frame_depth * rays_d).  buffer [H,W,3] (optional), the display buffer, is updated in place with the prepared
+ * frame: the colours, or with depth_mode frame_depth / (max(frame_depth) + 1e-6) on all three channels (the maximum over the
+ * destination frame: a first launch, into workspace — 4 bytes); where any of the K masks [K,H,W] uint8 is non-zero, fl(color *
+ * fl(alpha)) + fl(prepared * fl(1 - alpha)) (color: 3 HOST floats; 1 - alpha formed in double); then with spp > 0 frames in the
+ * buffer already, buffer = (fl(buffer * spp) + prepared) / (spp + 1), each operation rounded to fp32; spp == 0 stores.  All of
+ * frame_image, frame_depth, pos, buffer 16-byte aligned, masks 4-byte.  Every operation but the power is individually rounded:
+ * the results are the torch / numpy sequence's bits. */
+int s3d_preview_resolve(const float* image, const float* depth, uint32_t rH, uint32_t rW, uint32_t H, uint32_t W, int to_srgb,
+                        const float* rays_o, const float* rays_d, float* frame_image, float* frame_depth, float* pos,
+                        float* buffer, int depth_mode, const uint8_t* masks, uint32_t K, const float* color, double alpha,
+                        uint32_t spp, uint32_t* workspace, s3d_stream_t stream);
+/* Mask positions (get_mask_pos): for each of K masks [K,H,W] uint8 the rows of pos [H*W,3] where the mask is non-zero, in
+ * row-major pixel order — numpy's pos[mask > 0] — concatenated over the masks.  s3d_mask_positions_count fills the workspace
+ * (s3d_mask_positions_workspace_bytes; 0 for invalid sizes) and writes offsets [K+1] int64 on the device: rows before mask k,
+ * offsets[K] the total.  s3d_mask_positions_emit, given the same masks and workspace, writes out [rows,3] with rows =
+ * offsets[K].  No atomics: the order is fixed.  K * H * W < 2^32. */
+size_t s3d_mask_positions_workspace_bytes(uint32_t K, uint32_t H, uint32_t W);
+int s3d_mask_positions_count(const uint8_t* masks, uint32_t K, uint32_t H, uint32_t W, void* workspace, int64_t* offsets,
+                             s3d_stream_t stream);
+int s3d_mask_positions_emit(const uint8_t* masks, uint32_t K, uint32_t H, uint32_t W, const void* workspace, const float* pos,
+                            float* out, uint32_t rows, s3d_stream_t stream);
 
 /* Build extension — mesh export: marching cubes over a dense fp32 volume u [nx,ny,nz] (C order, z fastest); DESIGN.md §8.
  * A grid point is solid iff u > iso, with NaN read as 0 and +-inf as +-FLT_MAX (u is not modified).  Point p owns its +x, +y,

@@ -26,6 +26,9 @@
 //    0xCC9E2D51), u = (float)(hash_u32(key, step, b) >> 8) * 2^-24: two more constants of their own) and every ray of each
 //    pose's rH x rW frame, formed by the sampler's own ray function.  A pose's frame spans many workgroups: each recomputes
 //    the pose (one thread, handed round through LDS), and every lane stores 16 aligned bytes of the flat [B, rH rW, 3] stream.
+//  * s3d_frame_rays: the rays of ONE given camera for a whole rH x rW frame (get_rays(pose, intrinsics, rH, rW, -1), the
+//    first step of a preview frame: nerf/utils.py:754-763).  The pose travels in the launch's argument block; each lane stores
+//    16 aligned bytes of the flat [rH rW, 3] stream, the ray formed by pixel_ray_dir like every other ray of this file.
 #include "s3d_common.hpp"
 
 #include <math.h>
@@ -489,6 +492,43 @@ __global__ void __launch_bounds__(kOrbitBlock) k_orbit_rays(OrbitArgs a) {
     }
 }
 
+struct FrameArgs {
+    float pose[12];  // the cam2world matrix's first three rows
+    float* rays_o;   // [HW, 3], 16-byte aligned
+    float* rays_d;
+    uint32_t W, HW;
+    float fx, fy, cx, cy;
+};
+
+// s3d_frame_rays: a work item is one 16-byte aligned group of four floats of the 3 HW floats of either output (parts of two
+// neighbouring rays); only the frame's last item can be partial
+__global__ void __launch_bounds__(kOrbitBlock) k_frame_rays(FrameArgs a) {
+    const uint32_t F = 3u * a.HW, items = (F + 3u) >> 2;
+    for (uint32_t q = blockIdx.x * kOrbitBlock + threadIdx.x; q < items; q += gridDim.x * kOrbitBlock) {
+        const uint32_t g0 = q << 2, r0 = g0 / 3u;
+        float d0[3], d1[3];  // the item's floats belong to rays r0 and r0 + 1 (the latter may lie past the frame: never stored)
+        pixel_ray_dir(r0, a.W, a.fx, a.fy, a.cx, a.cy, a.pose, d0);
+        pixel_ray_dir(r0 + 1u, a.W, a.fx, a.fy, a.cx, a.cy, a.pose, d1);
+        float vd[4], vo[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+            const uint32_t f = g0 + j, r = f / 3u, c = f - 3u * r;
+            const float a0 = r == r0 ? d0[0] : d1[0], a1 = r == r0 ? d0[1] : d1[1], a2 = r == r0 ? d0[2] : d1[2];
+            vd[j] = c == 0u ? a0 : (c == 1u ? a1 : a2);
+            vo[j] = c == 0u ? a.pose[3] : (c == 1u ? a.pose[7] : a.pose[11]);
+        }
+        if (g0 + 4u <= F) {
+            *reinterpret_cast<float4*>(a.rays_d + g0) = make_float4(vd[0], vd[1], vd[2], vd[3]);
+            *reinterpret_cast<float4*>(a.rays_o + g0) = make_float4(vo[0], vo[1], vo[2], vo[3]);
+        } else {
+            for (uint32_t j = 0; g0 + j < F; j++) {
+                a.rays_d[g0 + j] = vd[j];
+                a.rays_o[g0 + j] = vo[j];
+            }
+        }
+    }
+}
+
 }  // namespace
 }  // namespace s3d
 
@@ -616,4 +656,20 @@ S3D_EXPORT int s3d_orbit_rays(uint32_t B, uint32_t rH, uint32_t rW, const float*
     S3D_REQUIRE((uint64_t)B * a.chunks < (1ull << 31), "s3d_orbit_rays: too many poses for one launch");
     hipLaunchKernelGGL(k_orbit_rays, dim3(B * a.chunks), dim3(kOrbitBlock), 0, as_stream(stream), a);
     return check_launch("k_orbit_rays");
+}
+
+S3D_EXPORT int s3d_frame_rays(const float* pose, const float* intrinsics, uint32_t rH, uint32_t rW, float* rays_o, float* rays_d,
+                              s3d_stream_t stream) {
+    if (rH == 0 || rW == 0) return S3D_OK;
+    S3D_REQUIRE(pose && intrinsics && rays_o && rays_d, "s3d_frame_rays: null argument");
+    S3D_REQUIRE(((reinterpret_cast<uintptr_t>(rays_o) | reinterpret_cast<uintptr_t>(rays_d)) & 15u) == 0,
+                "s3d_frame_rays: rays_o and rays_d must be 16-byte aligned");
+    S3D_REQUIRE((uint64_t)rH * rW * 3 + 4 < (1ull << 32), "s3d_frame_rays: frame too large");
+    FrameArgs a;
+    for (int k = 0; k < 12; k++) a.pose[k] = pose[k];
+    a.rays_o = rays_o; a.rays_d = rays_d;
+    a.W = rW; a.HW = rH * rW;
+    a.fx = intrinsics[0]; a.fy = intrinsics[1]; a.cx = intrinsics[2]; a.cy = intrinsics[3];
+    hipLaunchKernelGGL(k_frame_rays, dim3(stream_grid((3ull * a.HW + 3) / 4, kOrbitBlock)), dim3(kOrbitBlock), 0, as_stream(stream), a);
+    return check_launch("k_frame_rays");
 }

@@ -52,6 +52,21 @@ class Trainer(_Trainer):
 
     eval_step = test_step = render_image
 
+    def _preview_render(self, rays_o, rays_d, bg_color, perturb, time=0):
+        self.model.eval()
+        with self._averaged(), torch.autocast("cuda", dtype=torch.float16, enabled=self.fp16):
+            return self.model.render(rays_o, rays_d, time, staged=True, bg_color=bg_color, perturb=perturb, **self.render_kwargs)
+
+    @torch.no_grad()
+    def test_gui(self, pose, intrinsics, W, H, time=0, bg_color=None, spp=1, downscale=1, color_space="srgb", native=None,
+                 display=None):
+        """dnerf/utils.py:169-219: the preview frame of nerf.trainer.Trainer.test_gui at `time` in [0, 1].  As in the reference
+        `perturb=spp` is passed ALWAYS, so a D-NeRF preview jitters its first sample at spp 1 as well (the static trainers do
+        not), and there is no `return_pos`."""
+        from nerf.preview import preview_frame
+        return preview_frame(self, pose, intrinsics, W, H, bg_color=bg_color, spp=spp, downscale=downscale, color_space=color_space,
+                             native=native, display=display, perturb=spp, time=time)
+
 
 class GraphedTrainer(_GraphedTrainer):
     def __init__(self, model, *args, **kw):

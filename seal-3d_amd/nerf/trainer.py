@@ -452,6 +452,59 @@ class Trainer:
         with self._averaged(), torch.autocast("cuda", dtype=torch.float16, enabled=self.fp16):
             return self.model.render(rays_o, rays_d, bg_color=bg_color, perturb=False, **self.render_kwargs)
 
+    # ------------------------------------------------------------------ interactive preview (nerf/preview.py)
+    def _preview_render(self, rays_o, rays_d, bg_color, perturb):
+        """the render of a preview frame: eval mode, averaged weights, autocast (nerf/utils.py:772-785)"""
+        self.model.eval()
+        with self._averaged(), torch.autocast("cuda", dtype=torch.float16, enabled=self.fp16):
+            return self.model.render(rays_o, rays_d, staged=True, bg_color=bg_color, perturb=perturb, **self.render_kwargs)
+
+    @torch.no_grad()
+    def test_gui(self, pose, intrinsics, W, H, bg_color=None, spp=1, downscale=1, return_pos=False, color_space="srgb", native=None,
+                 display=None):
+        """nerf/utils.py:754-820: one preview frame from a free camera.  `pose`: 4 x 4 cam2world (numpy), `intrinsics`: fx, fy,
+        cx, cy of the W x H frame.  The frame is rendered at int(H * downscale) x int(W * downscale) with the intrinsics scaled,
+        `perturb = False if spp == 1 else spp`, and brought back to H x W by nearest-neighbour upsampling; `color_space="linear"`
+        converts the colours to sRGB.  Returns device tensors {"image" [H, W, 3], "depth" [H, W]} and, with `return_pos`
+        (downscale 1 only: ValueError otherwise), "pos" [H, W, 3] = rays_o + depth * rays_d.
+        On the GPU the frame's rays and the whole tail are one launch each (s3d_frame_rays, s3d_preview_resolve); on CPU tensors,
+        or with `native=False`, the reference's torch op sequence runs.  `display`: the display state of a
+        nerf.preview.PreviewSession, whose buffer the tail then updates as well.  The model is only read: a captured training
+        step replays unchanged afterwards."""
+        from .preview import preview_frame
+        return preview_frame(self, pose, intrinsics, W, H, bg_color=bg_color, spp=spp, downscale=downscale, return_pos=return_pos,
+                             color_space=color_space, native=native, display=display)
+
+    def _gui_batch(self, dataset, i):
+        """batch i of train_gui: drawn on the device where the dataset lives there (`sample`), else by `collate`"""
+        index = [i % len(dataset)]
+        dev = getattr(dataset, "device", None)
+        if hasattr(dataset, "sample") and dev is not None and torch.device(dev).type == "cuda":
+            return dataset.sample(index)
+        return dataset.collate(index)
+
+    def _gui_train_step(self, data):
+        gt, bg = data["images"], data.get("bg_color", 1)
+        if gt.shape[-1] == 4:
+            gt, bg = rgba_targets(gt)
+        return self.train_step(data["rays_o"].reshape(-1, 3), data["rays_d"].reshape(-1, 3), gt.reshape(-1, 3),
+                               bg_color=bg.reshape(-1, 3) if torch.is_tensor(bg) else bg, index=data.get("index"),
+                               inds_coarse=data.get("inds_coarse"))
+
+    def train_gui(self, dataset, step=16):
+        """nerf/utils.py:690-749: `step` training steps between two preview frames, on batches of `dataset` (its `sample` on
+        the device, else `collate`), cycling through its images.  Nothing is read back before the one read of the summed loss.
+        The parameter average keeps this trainer's cadence (every step).  Returns {"loss": the mean, "lr": the first group's}."""
+        total = None
+        for k in range(step):
+            loss = self._gui_train_step(self._gui_batch(dataset, self._gui_cursor + k)).detach().float().reshape(())
+            total = loss.clone() if total is None else total + loss
+        self._gui_cursor += step
+        return {"loss": float(total) / step if step else 0.0, "lr": self.optimizer.param_groups[0]["lr"]}
+
+    _gui_cursor = 0
+
+
 
 # Stream capture restricts HIP calls of the CAPTURING thread only: with a process group alive, torch's RCCL watchdog thread
 # polls its work events (hipEventQuery) at any time, and under the default "global" mode such a poll during one of the

@@ -66,6 +66,7 @@ EXPORTS = [
     "s3d_mesh_sdf_tile", "s3d_mesh_sdf", "s3d_sdf_sample_points", "s3d_sdf_mape_workspace_size", "s3d_sdf_mape_forward_backward",
     "s3d_ema_update_multi", "s3d_ema_exchange_multi",
     "s3d_mesh_bvh_leaf", "s3d_mesh_bvh_stage", "s3d_mesh_sdf_bvh",
+    "s3d_frame_rays", "s3d_preview_resolve", "s3d_mask_positions_workspace_bytes", "s3d_mask_positions_count", "s3d_mask_positions_emit",
 ]
 
 
@@ -98,7 +99,7 @@ def lib():
                      "s3d_weighted_abs_sum_workspace_size", "s3d_background_backward_workspace_size",
                      "s3d_vm_background_backward_workspace_size", "s3d_mc_workspace_bytes",
                      "s3d_dnerf_warp_grid_workspace_size", "s3d_dnerf_basis_mid_workspace_size", "s3d_dnerf_hyper_backward_workspace_size",
-                     "s3d_sdf_mape_workspace_size"):
+                     "s3d_sdf_mape_workspace_size", "s3d_mask_positions_workspace_bytes"):
             getattr(l, name).restype = C.c_size_t
         l.s3d_vm_backward_max_bins.restype = C.c_uint32
         l.s3d_grid_level_scales.restype = None
@@ -1491,6 +1492,23 @@ class RaySampleBackend:
                "s3d_orbit_rays")
 
     @staticmethod
+    def frame_rays(pose, intrinsics, rH, rW, rays_o, rays_d):
+        """seal3d_hip.h: s3d_frame_rays.  The rays of the one camera `pose` (16 host numbers, a row-major 4 x 4 cam2world
+        matrix) for its whole rH x rW frame: rays_o, rays_d [rH*rW, 3] fp32, preallocated.  `intrinsics`: fx, fy, cx, cy of
+        the rH x rW frame (host numbers).  Pose and intrinsics travel in the launch's arguments: no staging copy."""
+        rH, rW = int(rH), int(rW)
+        for t, n in ((rays_o, "rays_o"), (rays_d, "rays_d")):
+            _need(t, torch.float32, n)
+            if t.numel() != rH * rW * 3:
+                raise RuntimeError(f"frame_rays: {n} must hold {rH * rW} x 3 values")
+        vals = [float(v) for row in pose for v in (row if hasattr(row, "__len__") else (row,))]
+        if len(vals) != 16:
+            raise RuntimeError("frame_rays: pose holds the 16 numbers of a 4 x 4 matrix")
+        mat = (C.c_float * 16)(*vals)
+        intr = (C.c_float * 4)(*[float(v) for v in intrinsics])
+        _check(lib().s3d_frame_rays(mat, intr, _u(rH), _u(rW), _p(rays_o), _p(rays_d), _stream()), "s3d_frame_rays")
+
+    @staticmethod
     def error_map_update(error_map, index, inds_coarse, image, gt, weights_sum=None, bg=None, depth=None, gt_depth=None,
                          depth_weight=1.0):
         """seal3d_hip.h: s3d_error_map_update.  bg: None, 3 floats, or a per-ray fp32 tensor [B*N, 3]"""
@@ -2151,6 +2169,81 @@ class MeshBackend:
         _check(lib().s3d_mc_emit(_p(u), _u(nx), _u(ny), _u(nz), _f(iso), _p(ws), _p(bounds), _p(vertices), _u(V), _p(triangles), _u(T), _stream()),
                "mc_emit")
         return vertices, triangles
+
+
+class PreviewBackend:
+    """The tail of an interactive preview frame (csrc/preview.hip; include/seal3d_hip.h "interactive preview")."""
+
+    @staticmethod
+    def resolve(image, depth, H, W, to_srgb=False, rays_o=None, rays_d=None, return_pos=False, buffer=None, mode="image", masks=None,
+                color=(1.0, 0.0, 0.0), alpha=1.0, spp=0):
+        """seal3d_hip.h: s3d_preview_resolve.  image [rH, rW, 3], depth [rH, rW] fp32 (the renderer's output) -> frame_image
+        [H, W, 3] (`image` itself where the two are equal: full resolution, no conversion), frame_depth [H, W] (and pos
+        [H, W, 3] with `return_pos`, which needs the frame's rays and rH == H, rW == W).
+        `buffer` [H, W, 3] fp32, the display buffer, is updated in place: `mode` image / depth, `masks` [K, H, W] uint8 painted
+        with `color` at `alpha`, accumulated onto the `spp` frames it already holds."""
+        H, W = int(H), int(W)
+        _need(image, torch.float32, "image"); _need(depth, torch.float32, "depth")
+        if image.dim() != 3 or image.shape[2] != 3 or tuple(depth.shape) != tuple(image.shape[:2]):
+            raise RuntimeError("preview resolve: image [rH, rW, 3] and depth [rH, rW]")
+        if mode not in ("image", "depth"):
+            raise RuntimeError(f"preview resolve: mode is 'image' or 'depth', got {mode!r}")
+        rH, rW = image.shape[:2]
+        dev = image.device
+        # (rendered at full resolution and not converted: the frame image IS the renderer's, handed back without a copy)
+        same = (rH, rW) == (H, W) and not to_srgb
+        frame_image = None if same else torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+        frame_depth = torch.empty(H, W, dtype=torch.float32, device=dev)
+        pos = None
+        if return_pos:
+            if rays_o is None or rays_d is None or (rH, rW) != (H, W):
+                raise RuntimeError("preview resolve: pos needs rays_o / rays_d of a frame rendered at full resolution")
+            for t, n in ((rays_o, "rays_o"), (rays_d, "rays_d")):
+                _need(t, torch.float32, n)
+                if t.numel() != H * W * 3:
+                    raise RuntimeError(f"preview resolve: {n} must hold {H * W} x 3 values")
+            pos = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+        K, col, ws = 0, None, None
+        if buffer is not None:
+            _need(buffer, torch.float32, "buffer")
+            if tuple(buffer.shape) != (H, W, 3):
+                raise RuntimeError(f"preview resolve: buffer must be [{H}, {W}, 3]")
+            if masks is not None and masks.numel():
+                _need(masks, torch.uint8, "masks")
+                if masks.dim() != 3 or tuple(masks.shape[1:]) != (H, W):
+                    raise RuntimeError(f"preview resolve: masks must be [K, {H}, {W}]")
+                K = masks.shape[0]
+                col = (C.c_float * 3)(*[float(v) for v in color])
+            if mode == "depth":
+                ws = torch.empty(1, dtype=torch.int32, device=dev)
+        _check(lib().s3d_preview_resolve(_p(image), _p(depth), _u(rH), _u(rW), _u(H), _u(W), C.c_int(int(bool(to_srgb))),
+                                         _p(rays_o if return_pos else None), _p(rays_d if return_pos else None), _p(frame_image),
+                                         _p(frame_depth), _p(pos), _p(buffer), C.c_int(int(mode == "depth")), _p(masks if K else None),
+                                         _u(K), col, C.c_double(float(alpha)), _u(spp), _p(ws), _stream()), "s3d_preview_resolve")
+        return (image if same else frame_image), frame_depth, pos
+
+    @staticmethod
+    def mask_positions(masks, pos):
+        """seal3d_hip.h: s3d_mask_positions_count / _emit.  masks [K, H, W] uint8, pos [H, W, 3] fp32 -> (rows [sum n_k, 3] fp32
+        on the device, offsets: K + 1 host ints): rows[offsets[k]:offsets[k + 1]] = pos[masks[k] > 0] in numpy's order.  The
+        offsets are read on the host between the two passes (the output's size depends on them): not capturable."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("mask_positions reads its counts on the host: it cannot be captured into a graph")
+        _need(masks, torch.uint8, "masks"); _need(pos, torch.float32, "pos")
+        if masks.dim() != 3 or masks.shape[0] == 0 or pos.dim() != 3 or tuple(pos.shape) != (masks.shape[1], masks.shape[2], 3):
+            raise RuntimeError("mask_positions: masks [K >= 1, H, W] and pos [H, W, 3]")
+        K, H, W = masks.shape
+        nbytes = lib().s3d_mask_positions_workspace_bytes(_u(K), _u(H), _u(W))
+        if nbytes == 0:
+            raise RuntimeError(f"mask_positions: {K} masks of {H} x {W} are empty or too large")
+        ws = _ws.get(nbytes, masks.device)
+        offsets = torch.empty(K + 1, dtype=torch.int64, device=masks.device)
+        _check(lib().s3d_mask_positions_count(_p(masks), _u(K), _u(H), _u(W), _p(ws), _p(offsets), _stream()), "mask_positions_count")
+        offs = [int(v) for v in offsets.cpu()]
+        rows = torch.empty(offs[-1], 3, dtype=torch.float32, device=masks.device)
+        _check(lib().s3d_mask_positions_emit(_p(masks), _u(K), _u(H), _u(W), _p(ws), _p(pos), _p(rows), _u(offs[-1]), _stream()),
+               "mask_positions_emit")
+        return rows, offs
 
 
 class DnerfBackend:

@@ -353,6 +353,30 @@ class SealSteps:
             self.freeze_mlp(False)
             self.set_lr(-1)
 
+    def _gui_train_step(self, data):
+        """a fine-tuning step of train_gui: the dataset's targets when it was proxied, else the teacher's online proxy"""
+        gt, depth = data.get("images"), data.get("depths")
+        flat = lambda t, c: None if t is None else t.reshape(-1, c) if c else t.reshape(-1)  # noqa: E731
+        return self.train_step(data["rays_o"].reshape(-1, 3), data["rays_d"].reshape(-1, 3), flat(gt, 3), flat(depth, 0),
+                               index=data.get("index"), inds_coarse=data.get("inds_coarse"))
+
+    def train_gui(self, dataset, step=16, is_pretraining=False):
+        """SealNeRF/trainer.py:647-: while pretraining, `step` epochs of the local distillation; otherwise the MLPs are
+        unfrozen, the fine-tuning lr restored, the teacher's bitfield force-filled, and `step` fine-tuning steps run as
+        nerf.trainer.Trainer.train_gui runs them"""
+        if is_pretraining:
+            total = None
+            for _ in range(step):
+                loss = self.pretrain_one_epoch().detach().float().reshape(())
+                total = loss.clone() if total is None else total + loss.to(total.device)
+            return {"loss": float(total) / step if step else 0.0, "lr": self.optimizer.param_groups[0]["lr"]}
+        self._pretraining_open = False
+        self.freeze_mlp(False)
+        self.set_lr(-1)
+        if not self.teacher.density_bitfield_hacked:
+            self.teacher.hack_bitfield()
+        return super().train_gui(dataset, step)
+
     # ------------------------------------------------------------------ global fine-tuning
     online_proxy_mode = None  # None: the teacher renders in the mode it is in (the reference); "train" / "eval": forced
 
