@@ -9,7 +9,8 @@
 // of the sin row), so one lane forms eight columns once and stores the same word twice.  The seams of the layout (63, 76; 95, 108
 // in the sin row) fall inside words, never across a store.
 #include "s3d_common.hpp"
-#include "grid_device.hpp"
+#include "grid_group.hpp"
+#include "ordered_sum.hpp"
 #include <math.h>
 
 namespace s3d {
@@ -19,8 +20,6 @@ constexpr uint32_t kDinCols = 80, kSinCols = 112, kGridCols = 32;
 constexpr uint32_t kXDeg = 10, kTDeg = 6, kXCols = 3 + 6 * kXDeg /* 63 */, kTCols = 1 + 2 * kTDeg /* 13 */;
 constexpr uint32_t kWords = kDinCols / 8;  // 16-byte words per row
 static_assert(kXCols + kTCols <= kDinCols && kGridCols + kDinCols == kSinCols, "row layouts");
-
-struct alignas(16) Half8 { _Float16 v[8]; };
 
 // column c of [freq_10(x) | freq_6(t) | 0]: k_freq_forward's expression (csrc/encoders.hip) for D = 3 and for D = 1
 __device__ __forceinline__ float din_column(uint32_t c, const float (&x)[3], float t) {
@@ -58,26 +57,11 @@ __global__ void __launch_bounds__(256) k_dnerf_encode(const float* __restrict__ 
 }
 
 // ---- warp + grid lookup ---------------------------------------------------------------------------------------------------
-// Workgroup (chunk, g) serves the four levels 4 g .. 4 g + 3 of 256 samples: a lane's features of those levels are eight
-// consecutive fp16 columns of its sin row (one 16-byte store), its Jacobian entries 24 consecutive values of dy_dx.  blockIdx.x =
-// chunk * NG + g, so a level group stays on the XCDs g, g + NG, ... (workgroups are dealt round-robin over the eight XCDs) and one
-// XCD's L2 holds four levels' tables.  Rows, weights and sums are k_grid_forward's (csrc/gridencoder.hip), expression by
-// expression, through the helpers of grid_device.hpp.
-constexpr uint32_t kWarpBlock = 256, kGroup = 4;
-
-// The fp16 sums of grid_device.hpp's Acc<__half> with the fp32 value pinned before it is rounded to binary16: "round the fp32
-// product, then round that to half" (what k_grid_forward's v_mul_f32 + v_cvt_pk_f16_f32 do) and "round the exact product to half
-// once" (v_fma_mixlo_f16, which the compiler picked for the feature sums of this kernel) differ in one value in ~10^4.  An fp32
-// value that exists in a register rounds to half the same way whatever instruction converts it.
-__device__ __forceinline__ float pinned(float v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-template <typename T>
-__device__ __forceinline__ T feat_fma(float w, T g, T acc) {
-    if constexpr (sizeof(T) == 2) return __hadd(acc, __float2half(pinned(w * __half2float(g))));
-    else return Acc<T>::fma(w, g, acc);
-}
+// Workgroup (chunk, g) serves the four levels 4 g .. 4 g + 3 of 256 samples (csrc/grid_group.hpp: the level step, the Jacobian
+// columns and the stores): a lane's features of those levels are eight consecutive fp16 columns of its sin row, its Jacobian entries
+// 24 consecutive values of dy_dx.  blockIdx.x = chunk * NG + g, so a level group stays on the XCDs g, g + NG, ... (workgroups are
+// dealt round-robin over the eight XCDs) and one XCD's L2 holds four levels' tables.
+constexpr uint32_t kWarpBlock = kSumBlock;
 
 template <typename T>
 struct WarpArgs {
@@ -96,8 +80,10 @@ struct WarpArgs {
     bool align_corners;
 };
 
+// (eight waves per SIMD asked for: the fp32 instantiation sits at the 64-register edge, where the allocator otherwise lands on either
+// side of it from one small change of the source to the next)
 template <typename T>
-__global__ void __launch_bounds__(kWarpBlock) k_dnerf_warp_grid(WarpArgs<T> a, LevelScales scales) {
+__global__ void __launch_bounds__(kWarpBlock, 8) k_dnerf_warp_grid(WarpArgs<T> a, LevelScales scales) {
     constexpr uint32_t D = 3, C = 2;
     const uint32_t NG = div_up<uint32_t>(a.L, kGroup);
     const uint32_t g = blockIdx.x % NG, chunk = blockIdx.x / NG;
@@ -120,47 +106,11 @@ __global__ void __launch_bounds__(kWarpBlock) k_dnerf_warp_grid(WarpArgs<T> a, L
                 if (a.deform) a.deform[(size_t)b * D + d] = dv[d];
             }
         }
-        if (a.reg_sum) {
-            // sum of |deform| in a fixed order: lanes by a shuffle tree, waves in order, workgroups in order by the last one to
-            // arrive (one agent-scope release per workgroup, one acquire by the last) — no float atomics, the same bits every run
-            __shared__ float part[kWarpBlock / 64 + 1];
-            float s = valid ? (fabsf(dv[0]) + fabsf(dv[1])) + fabsf(dv[2]) : 0.0f;
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) s += __shfl_down(s, o, 64);
-            if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = s;
-            __syncthreads();
-            const uint32_t nchunks = gridDim.x / NG;
-            if (threadIdx.x == 0) {
-                float v = part[0];
-                for (uint32_t w = 1; w < kWarpBlock / 64; w++) v += part[w];
-                a.partials[chunk] = v;
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                const uint32_t arrived = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const bool last = arrived == nchunks - 1;
-                if (last) {
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                }
-                part[kWarpBlock / 64] = last ? 1.0f : 0.0f;
-            }
-            __syncthreads();
-            if (part[kWarpBlock / 64] != 0.0f) {  // (workgroup-uniform)
-                float v = 0.0f;
-                for (uint32_t i = threadIdx.x; i < nchunks; i += kWarpBlock) v += a.partials[i];
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o, 64);
-                __syncthreads();
-                if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = v;
-                __syncthreads();
-                if (threadIdx.x == 0) {
-                    float r = part[0];
-                    for (uint32_t w = 1; w < kWarpBlock / 64; w++) r += part[w];
-                    *a.reg_sum = r;
-                    *a.ticket = 0u;
-                }
-            }
+        if (a.reg_sum) {  // sum of |deform| over the live rows: one row per lane, one partial per chunk (csrc/ordered_sum.hpp)
+            __shared__ SumShared sh;
+            const float s = block_sum(valid ? (fabsf(dv[0]) + fabsf(dv[1])) + fabsf(dv[2]) : 0.0f, sh);
+            float total;
+            if (ordered_sum_finish(s, a.partials, a.ticket, gridDim.x / NG, chunk, sh, total)) *a.reg_sum = total;
         }
     }
     if (!valid) return;
@@ -176,110 +126,30 @@ __global__ void __launch_bounds__(kWarpBlock) k_dnerf_warp_grid(WarpArgs<T> a, L
     }
 
     const uint32_t l0 = g * kGroup;
-    T res[kGroup][C];
-    T jac[kGroup][D][C];
+    Half8 o;  // (rows outside the box and levels past L: zeros)
+    T jac[kGroup][D * C];
 #pragma unroll
     for (uint32_t k = 0; k < kGroup; k++) {
+        o.v[k * C] = o.v[k * C + 1] = (_Float16)0.0f;
 #pragma unroll
-        for (uint32_t c = 0; c < C; c++) {
-            res[k][c] = Acc<T>::zero();
-#pragma unroll
-            for (uint32_t d = 0; d < D; d++) jac[k][d][c] = Acc<T>::zero();
-        }
+        for (uint32_t n = 0; n < D * C; n++) jac[k][n] = Acc<T>::zero();
     }
 #pragma unroll
     for (uint32_t k = 0; k < kGroup; k++) {
         const uint32_t level = l0 + k;
         if (level >= a.L || oob) continue;
-        const uint32_t off = (uint32_t)a.offsets[level];
-        const uint32_t hashmap_size = (uint32_t)a.offsets[level + 1] - off;
-        const T* table = a.grid + (size_t)off * C;
-        const float scale = scales.v[level];
-        const uint32_t resolution = (uint32_t)ceilf(scale) + 1;
+        const LevelTable<T> lt = level_table<T>(a.grid, a.offsets, level, scales.v[level]);
         float pos[D], pos_deriv[D];
-        uint32_t pos_grid[D];
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) pos_deriv[d] = (d == 0) ? 1.0f : 0.0f;  // `= {1.0f}`, gridencoder.cu:143
-        locate<D>(x01, scale, a.align_corners, a.interp, pos, pos_deriv, pos_grid);
-
         T feat[1u << D][C];
-        float wts[1u << D];
+        level_value<D, T>(lt, a.gridtype, a.align_corners, a.interp, x01, false, pos, pos_deriv, feat, o, k);
+        if (a.dy_dx) {
 #pragma unroll
-        for (uint32_t idx = 0; idx < (1u << D); idx++) {
-            float w = 1;
-            uint32_t pgl[D];
-#pragma unroll
-            for (uint32_t d = 0; d < D; d++) {
-                if ((idx & (1u << d)) == 0) { w *= 1 - pos[d]; pgl[d] = pos_grid[d]; }
-                else { w *= pos[d]; pgl[d] = pos_grid[d] + 1; }
-            }
-            wts[idx] = w;
-            const uint32_t row = grid_row<D>(a.gridtype, a.align_corners, hashmap_size, resolution, pgl);
-            load_feat<T, C>(table + (size_t)row * C, feat[idx]);
-        }
-#pragma unroll
-        for (uint32_t idx = 0; idx < (1u << D); idx++) {
-#pragma unroll
-            for (uint32_t c = 0; c < C; c++) res[k][c] = feat_fma<T>(wts[idx], feat[idx][c], res[k][c]);
-        }
-        if (a.dy_dx) {  // gridencoder.cu:198-241; the corner rows are those gathered above (corner idx = bit d of dimension d)
-#pragma unroll
-            for (uint32_t gd = 0; gd < D; gd++) {
-#pragma unroll
-                for (uint32_t idx = 0; idx < (1u << (D - 1)); idx++) {
-                    float w = scale;
-                    uint32_t corner = 0;
-#pragma unroll
-                    for (uint32_t nd = 0; nd < D - 1; nd++) {
-                        const uint32_t d = (nd >= gd) ? (nd + 1) : nd;
-                        if ((idx & (1u << nd)) == 0) { w *= 1 - pos[d]; }
-                        else { w *= pos[d]; corner |= 1u << d; }
-                    }
-#pragma unroll
-                    for (uint32_t c = 0; c < C; c++) {
-                        const float diff = Acc<T>::to_f(Acc<T>::sub(feat[corner | (1u << gd)][c], feat[corner][c]));
-                        if constexpr (sizeof(T) == 2) jac[k][gd][c] = Acc<T>::add(jac[k][gd][c], Acc<T>::from_f(pinned(w * diff * pos_deriv[gd])));
-                        else jac[k][gd][c] = Acc<T>::from_f(__builtin_fmaf(w * diff, pos_deriv[gd], Acc<T>::to_f(jac[k][gd][c])));
-                    }
-                }
-            }
+            for (uint32_t gd = 0; gd < D; gd++) jacobian_column<D, T>(gd, lt.scale, pos, pos_deriv, feat, jac[k][gd * C], jac[k][gd * C + 1]);
         }
     }
-
-    // the features as the fp16 columns 2 l, 2 l + 1 of the sin row
-    _Float16* srow = a.sin + (size_t)b * kSinCols + l0 * C;
-    Half8 o;
-#pragma unroll
-    for (uint32_t k = 0; k < kGroup; k++) {
-#pragma unroll
-        for (uint32_t c = 0; c < C; c++) {
-            if constexpr (sizeof(T) == 2) { __half h = res[k][c]; __builtin_memcpy(&o.v[k * C + c], &h, 2); }
-            else o.v[k * C + c] = (_Float16)res[k][c];
-        }
-    }
-    if (l0 + kGroup <= a.L) *reinterpret_cast<Half8*>(srow) = o;
-    else {  // (a ragged last group; every index below is a compile-time constant: the arrays stay in registers)
-#pragma unroll
-        for (uint32_t k = 0; k < kGroup; k++)
-            if (l0 + k < a.L) { srow[k * C] = o.v[k * C]; srow[k * C + 1] = o.v[k * C + 1]; }
-    }
-    if (a.dy_dx) {
-        T* j = a.dy_dx + ((size_t)b * a.L + l0) * D * C;
-        if (a.L % kGroup == 0) {  // whole 16-byte words: 48 B (fp16) / 96 B (fp32) per lane, rows of L * 12 / L * 24 bytes
-            constexpr uint32_t NW = kGroup * D * C * sizeof(T) / 16;
-            uint4 w[NW];
-            __builtin_memcpy(w, jac, sizeof(w));
-#pragma unroll
-            for (uint32_t i = 0; i < NW; i++) reinterpret_cast<uint4*>(j)[i] = w[i];
-        } else {
-#pragma unroll
-            for (uint32_t k = 0; k < kGroup; k++) {
-                if (l0 + k >= a.L) continue;
-#pragma unroll
-                for (uint32_t d = 0; d < D; d++) store_feat<T, C>(j + (k * D + d) * C, jac[k][d]);
-            }
-        }
-    }
+    // the features as the fp16 columns 2 l, 2 l + 1 of the sin row (16-byte aligned at every group), the Jacobian as [L, 3, 2]
+    store_group_features(o, a.sin + (size_t)b * kSinCols + l0 * C, a.L - l0, l0 + kGroup <= a.L);
+    if (a.dy_dx) store_group_jacobian<D * C, T>(jac, a.dy_dx + ((size_t)b * a.L + l0) * D * C, a.L, l0);
 }
 
 // columns 0 .. 2 L - 1 of the density network's input gradient [B, 112] -> level-major [L][B][2] in the table's dtype.  One lane
@@ -294,15 +164,7 @@ __global__ void __launch_bounds__(256) k_dnerf_split_grad(const _Float16* __rest
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (uint64_t)gridDim.x * 256) {
         const uint32_t q = (uint32_t)(i / Bv), b = (uint32_t)(i - (uint64_t)q * Bv);
         const Half8 w = *reinterpret_cast<const Half8*>(g_sin + (size_t)b * kSinCols + q * 2 * kGroup);  // (inside the 32 grid columns)
-#pragma unroll
-        for (uint32_t k = 0; k < kGroup; k++) {
-            const uint32_t l = q * kGroup + k;
-            if (l >= L) continue;
-            T v[2];
-            if constexpr (sizeof(T) == 2) __builtin_memcpy(v, &w.v[2 * k], 4);
-            else { v[0] = (float)w.v[2 * k]; v[1] = (float)w.v[2 * k + 1]; }
-            store_feat<T, 2>(out + ((size_t)l * B + b) * 2, v);
-        }
+        split_row_group<T>(w, q * kGroup, L, B, b, out);
     }
 }
 
@@ -350,7 +212,7 @@ S3D_EXPORT int s3d_dnerf_encode_forward(const float* x, const float* t, uint32_t
 }
 
 S3D_EXPORT size_t s3d_dnerf_warp_grid_workspace_size(uint32_t B) {
-    return 16 + sizeof(float) * (size_t)div_up<uint32_t>(B, kWarpBlock);
+    return SumWorkspace::bytes(div_up<uint32_t>(B, kWarpBlock));
 }
 
 template <typename T>
@@ -374,25 +236,20 @@ S3D_EXPORT int s3d_dnerf_warp_grid_forward(const float* x, const uint16_t* dout,
     S3D_REQUIRE(dtype == S3D_F32 || dtype == S3D_F16, "dnerf_warp_grid_forward: dtype");
     S3D_REQUIRE(gridtype <= 1 && interp <= 1, "dnerf_warp_grid_forward: gridtype / interpolation");
     S3D_REQUIRE(((uintptr_t)sin | (uintptr_t)dy_dx) % 16 == 0, "dnerf_warp_grid_forward: sin and dy_dx must be 16-byte aligned");
-    S3D_REQUIRE(!reg_sum || (workspace && workspace_bytes >= s3d_dnerf_warp_grid_workspace_size(B) && (uintptr_t)workspace % 16 == 0),
+    S3D_REQUIRE(!reg_sum || SumWorkspace::fits(workspace, workspace_bytes, div_up<uint32_t>(B, kWarpBlock)),
                 "dnerf_warp_grid_forward: reg_sum needs a workspace of s3d_dnerf_warp_grid_workspace_size(B) bytes");
     hipStream_t st = as_stream(stream);
     LevelScales sc;
     host_scales(L, S, H, sc, bound, n_valid);
-    uint32_t* ticket = nullptr;
-    float* partials = nullptr;
-    if (reg_sum) {
-        ticket = (uint32_t*)workspace;
-        partials = (float*)((char*)workspace + 16);
-        S3D_HIP(hipMemsetAsync(ticket, 0, 16, st));
-    }
+    SumWorkspace ws;
+    if (reg_sum) S3D_HIP(ws.arm(workspace, st));
     if (dtype == S3D_F16) {
         WarpArgs<__half> a{x, (const _Float16*)dout, (const __half*)embeddings, offsets, (_Float16*)sin, xw, deform, (__half*)dy_dx,
-                           reg_sum, partials, ticket, B, L, gridtype, interp, align_corners != 0};
+                           reg_sum, ws.partials, ws.ticket, B, L, gridtype, interp, align_corners != 0};
         return launch_warp_grid<__half>(a, sc, st);
     }
     WarpArgs<float> a{x, (const _Float16*)dout, (const float*)embeddings, offsets, (_Float16*)sin, xw, deform, (float*)dy_dx,
-                      reg_sum, partials, ticket, B, L, gridtype, interp, align_corners != 0};
+                      reg_sum, ws.partials, ws.ticket, B, L, gridtype, interp, align_corners != 0};
     return launch_warp_grid<float>(a, sc, st);
 }
 

@@ -9,17 +9,20 @@
 //                                                             d_sb [32] f32 = sum_b float(gh_b) float(h_bk)
 // One lane = one row; every lane reads / writes whole 16-byte pieces of its rows.  The 32-column sum of the backward runs over a
 // grid of fixed size: per-lane running sums over the row stride gridDim.x * 256, one exchange tree per wave, the waves of a
-// workgroup in index order, the workgroups' partials in index order by the last one to arrive (dnerf.hip's reg_sum pattern): no
-// float atomics, the same bits on every run for the same B.
+// workgroup in index order, the workgroups' partials in index order by the last one to arrive (the hand-over and the workspace
+// are those of csrc/ordered_sum.hpp; the 32-column fold and the striped last sum are this file's): no float atomics, the same bits
+// on every run for the same B.
 #include "s3d_common.hpp"
 #include "sh_eval.hpp"
+#include "grid_group.hpp"
+#include "ordered_sum.hpp"
 
 namespace s3d {
 namespace {
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
-constexpr uint32_t kBasis = 32, kRow = 64, kCin = 48, kBlock = 256;
+constexpr uint32_t kBasis = 32, kRow = 64, kCin = 48, kBlock = kSumBlock;
 constexpr uint32_t kMaxBlocks = 512;   // workgroups of the backward (two per CU): the partials are kMaxBlocks x 32 floats
 constexpr uint32_t kStripes = kBlock / kBasis;  // 8 lanes per column in the last workgroup's sum
 constexpr uint32_t kBatch = 16;                 // partials a lane of the last workgroup has in flight
@@ -37,16 +40,8 @@ __device__ __forceinline__ Basis load_basis(const _Float16* __restrict__ sb) {
     return s;
 }
 
-// An fp32 value pinned in a register before it is rounded to binary16 (dnerf.hip): without it the compiler folds "round the fp32
-// result, then round that to half" into one v_fma_mixlo_f16, which rounds the exact result to half once — another value in ~10^-4 of
-// the cases, and not the contract's.
-__device__ __forceinline__ float pinned(float v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-
 // pre = float(half(sum)): the fp32 chain fmaf(h_k, sb_k, acc) for k = 0..31 ascending from 0, rounded to binary16 once (what an
-// fp16 matmul with fp32 accumulation hands back)
+// fp16 matmul with fp32 accumulation hands back; `pinned`, csrc/grid_group.hpp: two roundings, not one v_fma_mixlo_f16)
 __device__ __forceinline__ float basis_pre(const h8 (&hv)[kBasis / 8], const Basis& s) {
     float acc = 0.0f;
 #pragma unroll
@@ -103,7 +98,7 @@ __global__ void __launch_bounds__(kBlock) k_basis_mid_backward(const _Float16* _
                                                                float* partials, uint32_t* ticket,
                                                                const int32_t* __restrict__ n_valid) {
     __shared__ float part[kStripes][kBasis];  // (kBlock / 64 = 4 waves' sums first, then the 8 stripes of the last workgroup)
-    __shared__ uint32_t is_last;
+    __shared__ SumShared sh;  // (the hand-over's flag)
     const uint32_t Bv = valid_rows(B, n_valid);
     const Basis s = load_basis(sb);
     float acc[kBasis];
@@ -147,28 +142,14 @@ __global__ void __launch_bounds__(kBlock) k_basis_mid_backward(const _Float16* _
     acc[0] += __shfl_xor(acc[0], 1, 64);
     if ((lane & 1u) == 0) part[wave][lane >> 1] = acc[0];
     __syncthreads();
-    if (threadIdx.x < 64) {  // (wave 0 whole: the lanes that store the partials and the lane that takes the ticket are one wave)
-        if (threadIdx.x < kBasis) {
-            float v = part[0][threadIdx.x];
-            for (uint32_t w = 1; w < kBlock / 64; w++) v += part[w][threadIdx.x];
-            __hip_atomic_store(partials + (size_t)blockIdx.x * kBasis + threadIdx.x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        // The partials are write-through (agent-scope atomic) stores, drained by the one wave that made them before its lane 0
-        // takes the ticket: no release fence, which would write back the 32 KB of grad_h rows this workgroup has just left in
-        // its XCD's L2 (profiles/dnerf_basis.md).  The last workgroup acquires and reads them past its L1.
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (threadIdx.x == 0) {
-            const uint32_t arrived = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const bool last = arrived == gridDim.x - 1;
-            if (last) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            is_last = last ? 1u : 0u;
-        }
+    if (threadIdx.x < kBasis) {  // (wave 0: the lanes that store the partials and the lane that takes the ticket are one wave)
+        float v = part[0][threadIdx.x];
+        for (uint32_t w = 1; w < kBlock / 64; w++) v += part[w][threadIdx.x];
+        __hip_atomic_store(partials + (size_t)blockIdx.x * kBasis + threadIdx.x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    __syncthreads();
-    if (!is_last) return;  // (workgroup-uniform)
+    // (write-through partials and no release fence, which would write back the 32 KB of grad_h rows this workgroup has just left
+    // in its XCD's L2: profiles/dnerf_basis.md)
+    if (!ordered_sum_arrive(ticket, gridDim.x, sh)) return;  // (workgroup-uniform)
     // column k = tid % 32, stripe j = tid / 32: the partials of workgroups j, j + 8, ... in index order, then the stripes in order
     const uint32_t k = threadIdx.x % kBasis, j = threadIdx.x / kBasis;
     float v = 0.0f;
@@ -182,7 +163,7 @@ __global__ void __launch_bounds__(kBlock) k_basis_mid_backward(const _Float16* _
 #pragma unroll
         for (uint32_t u = 0; u < kBatch; u++) v += t[u];
     }
-    part[j][k] = v;  // (every read of `part` above lies before the barrier in front of `is_last`)
+    part[j][k] = v;  // (every read of `part` above lies before the barrier of the hand-over)
     __syncthreads();
     if (threadIdx.x < kBasis) {
         float r = part[0][threadIdx.x];
@@ -213,7 +194,7 @@ S3D_EXPORT int s3d_dnerf_basis_mid_forward(const uint16_t* h, const float* dirs,
 }
 
 S3D_EXPORT size_t s3d_dnerf_basis_mid_workspace_size(uint32_t B) {
-    return 16 + sizeof(float) * (size_t)kBasis * backward_blocks(B);
+    return SumWorkspace::bytes((size_t)kBasis * backward_blocks(B));
 }
 
 S3D_EXPORT int s3d_dnerf_basis_mid_backward(const uint16_t* grad_color_in, const float* grad_sigma, const uint16_t* h,
@@ -228,17 +209,12 @@ S3D_EXPORT int s3d_dnerf_basis_mid_backward(const uint16_t* grad_color_in, const
     S3D_REQUIRE(((uintptr_t)grad_color_in | (uintptr_t)h | (uintptr_t)sigma_basis | (uintptr_t)grad_h) % 16 == 0,
                 "dnerf_basis_mid_backward: grad_color_in, h, sigma_basis and grad_h must be 16-byte aligned");
     const bool sum = grad_sigma && grad_sigma_basis;
-    S3D_REQUIRE(!sum || (workspace && workspace_bytes >= s3d_dnerf_basis_mid_workspace_size(B) && (uintptr_t)workspace % 16 == 0),
+    S3D_REQUIRE(!sum || SumWorkspace::fits(workspace, workspace_bytes, (size_t)kBasis * backward_blocks(B)),
                 "dnerf_basis_mid_backward: grad_sigma_basis needs a workspace of s3d_dnerf_basis_mid_workspace_size(B) bytes");
-    uint32_t* ticket = nullptr;
-    float* partials = nullptr;
-    if (sum) {
-        ticket = (uint32_t*)workspace;
-        partials = (float*)((char*)workspace + 16);
-        S3D_HIP(hipMemsetAsync(ticket, 0, 16, st));
-    }
+    SumWorkspace ws;
+    if (sum) S3D_HIP(ws.arm(workspace, st));
     hipLaunchKernelGGL(k_basis_mid_backward, dim3(backward_blocks(B)), dim3(kBlock), 0, st, (const _Float16*)grad_color_in, grad_sigma,
-                       (const _Float16*)h, (const _Float16*)sigma_basis, B, (_Float16*)grad_h, sum ? grad_sigma_basis : nullptr, partials,
-                       ticket, n_valid);
+                       (const _Float16*)h, (const _Float16*)sigma_basis, B, (_Float16*)grad_h, sum ? grad_sigma_basis : nullptr, ws.partials,
+                       ws.ticket, n_valid);
     return check_launch("dnerf_basis_mid_backward");
 }

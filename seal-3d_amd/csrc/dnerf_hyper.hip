@@ -7,35 +7,20 @@
 //             dtype) = the ambient column of the Jacobian, formed from the 16 corners the value has already fetched
 //   backward: grad_feat [B, 2L] f16, dy_da -> grad_levels [L][B][2] (the table's dtype, what s3d_grid_encode_backward takes),
 //             grad_ambient [1] f32 = grad_scale * sum_b sum_k float(g_bk) float(j_bk)
-// The forward is k_dnerf_warp_grid's plan (csrc/dnerf.hip) for D = 4: workgroup (chunk, g) serves four levels of 256 rows, a lane's
-// features of those levels are one 16-byte store.  Rows, weights and sums are k_grid_forward's (csrc/gridencoder.hip), expression by
-// expression, through grid_device.hpp.  The backward's sum is s3d_dnerf_basis_mid_backward's scheme for one column: per-lane
-// running sums over the row stride, an exchange tree per wave, waves in index order, write-through partials added in a fixed order
-// by the last workgroup to arrive — no float atomics, the same bits on every run.
+// The forward is the four-levels-per-workgroup lookup of csrc/grid_group.hpp for D = 4: workgroup (chunk, g) serves four levels of
+// 256 rows, a lane's features of those levels are one 16-byte store.  The backward's sum is the ordered sum of
+// csrc/ordered_sum.hpp over a grid of fixed size (per-lane running sums over the row stride gridDim.x * 256) — no float atomics,
+// the same bits on every run.
 #include "s3d_common.hpp"
-#include "grid_device.hpp"
+#include "grid_group.hpp"
+#include "ordered_sum.hpp"
 #include <math.h>
 
 namespace s3d {
 namespace {
 
-constexpr uint32_t kBlock = 256, kGroup = 4, kMaxLevelsHyper = 16;
+constexpr uint32_t kBlock = kSumBlock, kMaxLevelsHyper = 16;
 constexpr uint32_t kMaxBlocks = 512;  // workgroups of the backward (two per CU): one fp32 partial each
-
-struct alignas(16) Half8 { _Float16 v[8]; };
-
-// An fp32 value pinned in a register before it is rounded to binary16 (dnerf.hip): "round the fp32 product, then round that to
-// half" is what k_grid_forward's v_mul_f32 + v_cvt_pk_f16_f32 do; without the pin the compiler may pick v_fma_mixlo_f16, which
-// rounds the exact product to half once — another value in ~10^-4 of the cases.
-__device__ __forceinline__ float pinned(float v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-template <typename T>
-__device__ __forceinline__ T feat_fma(float w, T g, T acc) {
-    if constexpr (sizeof(T) == 2) return __hadd(acc, __float2half(pinned(w * __half2float(g))));
-    else return Acc<T>::fma(w, g, acc);
-}
 
 template <typename T>
 struct HyperArgs {
@@ -52,7 +37,7 @@ struct HyperArgs {
 
 template <typename T>
 __global__ void __launch_bounds__(kBlock) k_dnerf_hyper_grid(HyperArgs<T> a, LevelScales scales) {
-    constexpr uint32_t D = 4, C = 2, NC = 1u << D, GD = D - 1;  // GD: the ambient dimension
+    constexpr uint32_t D = 4, C = 2, GD = D - 1;  // GD: the ambient dimension
     const uint32_t NG = div_up<uint32_t>(a.L, kGroup);
     const uint32_t g = blockIdx.x % NG, chunk = blockIdx.x / NG;
     const uint32_t b = chunk * kBlock + threadIdx.x;
@@ -71,127 +56,35 @@ __global__ void __launch_bounds__(kBlock) k_dnerf_hyper_grid(HyperArgs<T> a, Lev
     }
 
     const uint32_t l0 = g * kGroup;
-    T res[kGroup][C], jac[kGroup][C];
+    Half8 o;  // (rows outside the box and levels past L: zeros)
+    T jac[kGroup][C];
 #pragma unroll
     for (uint32_t k = 0; k < kGroup; k++) {
+        o.v[k * C] = o.v[k * C + 1] = (_Float16)0.0f;
 #pragma unroll
-        for (uint32_t c = 0; c < C; c++) { res[k][c] = Acc<T>::zero(); jac[k][c] = Acc<T>::zero(); }
+        for (uint32_t n = 0; n < C; n++) jac[k][n] = Acc<T>::zero();
     }
 #pragma unroll
     for (uint32_t k = 0; k < kGroup; k++) {
         const uint32_t level = l0 + k;
         if (level >= a.L || oob) continue;
-        const uint32_t off = (uint32_t)a.offsets[level];
-        const uint32_t hashmap_size = (uint32_t)a.offsets[level + 1] - off;
-        const T* table = a.grid + (size_t)off * C;
-        const float scale = scales.v[level];
-        const uint32_t resolution = (uint32_t)ceilf(scale) + 1;
-        float pos[D], pos_deriv[D];
-        uint32_t pos_grid[D];
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) pos_deriv[d] = (d == 0) ? 1.0f : 0.0f;  // `= {1.0f}`, gridencoder.cu:143
-        locate<D>(x01, scale, a.align_corners, a.interp, pos, pos_deriv, pos_grid);
-
+        const LevelTable<T> lt = level_table<T>(a.grid, a.offsets, level, scales.v[level]);
         // Does the ambient coordinate enter this level's index?  (level-uniform)  get_grid_index stops adding coordinates once
         // stride > hashmap_size (gridencoder.cu:72); a tiled level past that point addresses the same row for both ambient corners
         // of a pair: eight gathers, each used twice — the same bits.  (A hash level whose strides overflow hashes all four.)
         uint32_t stride = 1;
 #pragma unroll
         for (uint32_t d = 0; d < GD; d++)
-            if (stride <= hashmap_size) stride *= a.align_corners ? resolution : (resolution + 1);
-        const bool shared_rows = a.gridtype == 1 && stride > hashmap_size;
-
-        T feat[NC][C];
-        float wts[NC];
-#pragma unroll
-        for (uint32_t idx = 0; idx < NC; idx++) {
-            float w = 1;
-#pragma unroll
-            for (uint32_t d = 0; d < D; d++) {
-                if ((idx & (1u << d)) == 0) w *= 1 - pos[d];
-                else w *= pos[d];
-            }
-            wts[idx] = w;
-        }
-        auto gather = [&](uint32_t idx) {
-            uint32_t pgl[D];
-#pragma unroll
-            for (uint32_t d = 0; d < D; d++) pgl[d] = pos_grid[d] + ((idx >> d) & 1u);
-            const uint32_t row = grid_row<D>(a.gridtype, a.align_corners, hashmap_size, resolution, pgl);
-            load_feat<T, C>(table + (size_t)row * C, feat[idx]);
-        };
-        if (shared_rows) {
-#pragma unroll
-            for (uint32_t idx = 0; idx < NC / 2; idx++) gather(idx);
-#pragma unroll
-            for (uint32_t idx = 0; idx < NC / 2; idx++) {
-#pragma unroll
-                for (uint32_t c = 0; c < C; c++) feat[idx + NC / 2][c] = feat[idx][c];
-            }
-        } else {
-#pragma unroll
-            for (uint32_t idx = 0; idx < NC; idx++) gather(idx);
-        }
-#pragma unroll
-        for (uint32_t idx = 0; idx < NC; idx++) {
-#pragma unroll
-            for (uint32_t c = 0; c < C; c++) res[k][c] = feat_fma<T>(wts[idx], feat[idx][c], res[k][c]);
-        }
-        if (a.dy_da) {  // gridencoder.cu:198-241 for gd = 3; corner idx = bit d of dimension d, so the pair is (corner, corner | 8)
-#pragma unroll
-            for (uint32_t idx = 0; idx < NC / 2; idx++) {
-                float w = scale;
-#pragma unroll
-                for (uint32_t d = 0; d < GD; d++) {
-                    if ((idx & (1u << d)) == 0) w *= 1 - pos[d];
-                    else w *= pos[d];
-                }
-#pragma unroll
-                for (uint32_t c = 0; c < C; c++) {
-                    const float diff = Acc<T>::to_f(Acc<T>::sub(feat[idx | (1u << GD)][c], feat[idx][c]));
-                    if constexpr (sizeof(T) == 2) jac[k][c] = Acc<T>::add(jac[k][c], Acc<T>::from_f(pinned(w * diff * pos_deriv[GD])));
-                    else jac[k][c] = Acc<T>::from_f(__builtin_fmaf(w * diff, pos_deriv[GD], Acc<T>::to_f(jac[k][c])));
-                }
-            }
-        }
+            if (stride <= lt.hashmap_size) stride *= a.align_corners ? lt.resolution : (lt.resolution + 1);
+        const bool shared_rows = a.gridtype == 1 && stride > lt.hashmap_size;
+        float pos[D], pos_deriv[D];
+        T feat[1u << D][C];
+        level_value<D, T>(lt, a.gridtype, a.align_corners, a.interp, x01, shared_rows, pos, pos_deriv, feat, o, k);
+        if (a.dy_da) jacobian_column<D, T>(GD, lt.scale, pos, pos_deriv, feat, jac[k][0], jac[k][1]);  // (the pair is (corner, corner | 8))
     }
-
-    // the features as the fp16 columns 2 l, 2 l + 1 of the row (an fp32 sum is rounded to binary16 once: pinned first)
-    _Float16* frow = a.feat + (size_t)b * a.L * C + l0 * C;
-    Half8 o;
-#pragma unroll
-    for (uint32_t k = 0; k < kGroup; k++) {
-#pragma unroll
-        for (uint32_t c = 0; c < C; c++) {
-            if constexpr (sizeof(T) == 2) { __half h = res[k][c]; __builtin_memcpy(&o.v[k * C + c], &h, 2); }
-            else o.v[k * C + c] = (_Float16)pinned(res[k][c]);
-        }
-    }
-    const bool whole = a.L % kGroup == 0;  // rows of whole 16-byte words; else (a ragged last group) rows of 4 L bytes: 4-byte stores
-    if (whole) *reinterpret_cast<Half8*>(frow) = o;
-    else {  // (every index below is a compile-time constant: the arrays stay in registers)
-#pragma unroll
-        for (uint32_t k = 0; k < kGroup; k++) {
-            if (l0 + k >= a.L) continue;
-            uint32_t word;
-            __builtin_memcpy(&word, &o.v[k * C], 4);
-            *reinterpret_cast<uint32_t*>(frow + k * C) = word;
-        }
-    }
-    if (a.dy_da) {
-        T* j = a.dy_da + ((size_t)b * a.L + l0) * C;
-        if (whole) {  // 16 B (fp16) / 32 B (fp32) per lane
-            constexpr uint32_t NW = kGroup * C * sizeof(T) / 16;
-            uint4 w[NW];
-            __builtin_memcpy(w, jac, sizeof(w));
-#pragma unroll
-            for (uint32_t i = 0; i < NW; i++) reinterpret_cast<uint4*>(j)[i] = w[i];
-        } else {
-#pragma unroll
-            for (uint32_t k = 0; k < kGroup; k++)
-                if (l0 + k < a.L) store_feat<T, C>(j + k * C, jac[k]);
-        }
-    }
+    // rows of 4 L bytes: whole 16-byte words when L % 4 == 0
+    store_group_features(o, a.feat + (size_t)b * a.L * C + l0 * C, a.L - l0, a.L % kGroup == 0);
+    if (a.dy_da) store_group_jacobian<C, T>(jac, a.dy_da + ((size_t)b * a.L + l0) * C, a.L, l0);
 }
 
 // One lane = one row: the row's 2 L gradient columns go to the L level planes (consecutive lanes are consecutive rows, so every
@@ -202,8 +95,7 @@ __global__ void __launch_bounds__(kBlock) k_dnerf_hyper_backward(const _Float16*
                                                                  float* __restrict__ grad_ambient, float* partials, uint32_t* ticket,
                                                                  const int32_t* __restrict__ n_valid) {
     constexpr uint32_t C = 2;
-    __shared__ float part[kBlock / 64];
-    __shared__ uint32_t is_last;
+    __shared__ SumShared sh;
     const uint32_t Bv = valid_rows(B, n_valid);
     const bool whole = L % kGroup == 0;  // (rows of whole 16-byte words)
     float sum = 0.0f;
@@ -222,63 +114,22 @@ __global__ void __launch_bounds__(kBlock) k_dnerf_hyper_backward(const _Float16*
                     __builtin_memcpy(&gv.v[k * C], &word, 4);
                 }
             }
+            split_row_group<T>(gv, l0, L, B, b, out);
+            if (!jrow) continue;
 #pragma unroll
             for (uint32_t k = 0; k < kGroup; k++) {
-                const uint32_t l = l0 + k;
-                if (l >= L) continue;
-                T v[C];
-                if constexpr (sizeof(T) == 2) __builtin_memcpy(v, &gv.v[k * C], 4);
-                else { v[0] = (float)gv.v[k * C]; v[1] = (float)gv.v[k * C + 1]; }
-                store_feat<T, C>(out + ((size_t)l * B + b) * C, v);
-                if (jrow) {
-                    T j[C];
-                    load_feat<T, C>(jrow + l * C, j);
+                if (l0 + k >= L) continue;
+                T j[C];
+                load_feat<T, C>(jrow + (l0 + k) * C, j);
 #pragma unroll
-                    for (uint32_t c = 0; c < C; c++) acc = __builtin_fmaf((float)gv.v[k * C + c], Acc<T>::to_f(j[c]), acc);
-                }
+                for (uint32_t c = 0; c < C; c++) acc = __builtin_fmaf((float)gv.v[k * C + c], Acc<T>::to_f(j[c]), acc);
             }
         }
         sum += acc;
     }
     if (!grad_ambient) return;  // (workgroup-uniform)
-    // lanes by an exchange tree, waves in index order, workgroups in a fixed order by the last one to arrive
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) sum += __shfl_down(sum, o, 64);
-    if (lane == 0) part[wave] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float v = part[0];
-        for (uint32_t w = 1; w < kBlock / 64; w++) v += part[w];
-        // The partial is a write-through (agent-scope atomic) store, drained by the lane that made it before it takes the ticket:
-        // no release fence, which would write back the grad_levels rows this workgroup has just left in its XCD's L2
-        // (dnerf_basis.hip).  The last workgroup acquires and reads the partials past its L1.
-        __hip_atomic_store(partials + blockIdx.x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const uint32_t arrived = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool last = arrived == gridDim.x - 1;
-        if (last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        is_last = last ? 1u : 0u;
-    }
-    __syncthreads();
-    if (!is_last) return;  // (workgroup-uniform)
-    // lane i: the partials of workgroups i, i + 256 in index order; then the tree, the waves in order
-    float v = 0.0f;
-    for (uint32_t i = threadIdx.x; i < gridDim.x; i += kBlock)
-        v += __hip_atomic_load(partials + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o, 64);
-    if (lane == 0) part[wave] = v;  // (every read of `part` above lies before the barrier in front of `is_last`)
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float r = part[0];
-        for (uint32_t w = 1; w < kBlock / 64; w++) r += part[w];
-        *grad_ambient = r * grad_scale;
-        *ticket = 0u;
-    }
+    float total;
+    if (ordered_sum_finish(block_sum(sum, sh), partials, ticket, gridDim.x, blockIdx.x, sh, total)) *grad_ambient = total * grad_scale;
 }
 
 inline uint32_t backward_blocks(uint32_t B) { return std::min<uint32_t>(kMaxBlocks, std::max<uint32_t>(1u, div_up<uint32_t>(B, kBlock))); }
@@ -320,7 +171,7 @@ S3D_EXPORT int s3d_dnerf_hyper_grid_forward(const float* x, const float* ambient
 }
 
 S3D_EXPORT size_t s3d_dnerf_hyper_backward_workspace_size(uint32_t B) {
-    return 16 + sizeof(float) * (size_t)backward_blocks(B);
+    return SumWorkspace::bytes(backward_blocks(B));
 }
 
 S3D_EXPORT int s3d_dnerf_hyper_grid_backward(const uint16_t* grad_feat, const void* dy_da, uint32_t B, uint32_t L, int dtype,
@@ -337,23 +188,18 @@ S3D_EXPORT int s3d_dnerf_hyper_grid_backward(const uint16_t* grad_feat, const vo
     S3D_REQUIRE(dtype == S3D_F32 || dtype == S3D_F16, "dnerf_hyper_grid_backward: dtype");
     S3D_REQUIRE(((uintptr_t)grad_feat | (uintptr_t)dy_da | (uintptr_t)grad_levels) % 16 == 0,
                 "dnerf_hyper_grid_backward: grad_feat, dy_da and grad_levels must be 16-byte aligned");
-    S3D_REQUIRE(!sum || (workspace && workspace_bytes >= s3d_dnerf_hyper_backward_workspace_size(B) && (uintptr_t)workspace % 16 == 0),
+    S3D_REQUIRE(!sum || SumWorkspace::fits(workspace, workspace_bytes, backward_blocks(B)),
                 "dnerf_hyper_grid_backward: grad_ambient needs a workspace of s3d_dnerf_hyper_backward_workspace_size(B) bytes");
-    uint32_t* ticket = nullptr;
-    float* partials = nullptr;
-    if (sum) {
-        ticket = (uint32_t*)workspace;
-        partials = (float*)((char*)workspace + 16);
-        S3D_HIP(hipMemsetAsync(ticket, 0, 16, st));
-    }
+    SumWorkspace ws;
+    if (sum) S3D_HIP(ws.arm(workspace, st));
     const dim3 grid(backward_blocks(B)), block(kBlock);
     if (dtype == S3D_F16)
         hipLaunchKernelGGL((k_dnerf_hyper_backward<__half>), grid, block, 0, st, (const _Float16*)grad_feat,
                            sum ? (const __half*)dy_da : nullptr, B, L, grad_scale, (__half*)grad_levels, sum ? grad_ambient : nullptr,
-                           partials, ticket, n_valid);
+                           ws.partials, ws.ticket, n_valid);
     else
         hipLaunchKernelGGL((k_dnerf_hyper_backward<float>), grid, block, 0, st, (const _Float16*)grad_feat,
                            sum ? (const float*)dy_da : nullptr, B, L, grad_scale, (float*)grad_levels, sum ? grad_ambient : nullptr,
-                           partials, ticket, n_valid);
+                           ws.partials, ws.ticket, n_valid);
     return check_launch("dnerf_hyper_grid_backward");
 }

@@ -4,6 +4,7 @@
 // csrc/sdf_pair.hpp, shared with the BVH query (csrc/sdf_bvh.hip): this file only tiles the faces and loops over them.
 #include "s3d_common.hpp"
 #include "sdf_pair.hpp"
+#include "ordered_sum.hpp"
 
 namespace s3d {
 namespace {
@@ -87,15 +88,14 @@ __global__ void __launch_bounds__(256) sdf_sample_kernel(const float* __restrict
 }
 
 // ---- MAPE with its gradient --------------------------------------------------------------------------------------------------
-constexpr uint32_t kMapeBlock = 256;
+constexpr uint32_t kMapeBlock = kSumBlock;
 constexpr uint32_t kMapeMaxBlocks = 1024;
 
 template <bool HALF>
 __global__ void __launch_bounds__(kMapeBlock) sdf_mape_kernel(const void* __restrict__ pred_, const float* __restrict__ target, uint32_t B,
                                                              float clip, float grad_scale, float* __restrict__ loss,
-                                                             void* __restrict__ grad_, float* __restrict__ partials,
-                                                             uint32_t* __restrict__ ticket) {
-    __shared__ float part[kMapeBlock / 64 + 1];
+                                                             void* __restrict__ grad_, float* partials, uint32_t* ticket) {
+    __shared__ SumShared sh;
     const float fB = (float)B;
     float s = 0.0f;
     for (uint32_t b = blockIdx.x * kMapeBlock + threadIdx.x; b < B; b += gridDim.x * kMapeBlock) {
@@ -118,42 +118,9 @@ __global__ void __launch_bounds__(kMapeBlock) sdf_mape_kernel(const void* __rest
             ((float*)grad_)[b] = g;
         }
     }
-    // fixed order: a lane's rows in index order, lanes by a shuffle tree, waves in order, workgroups in order by the last to arrive
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_down(s, o, 64);
-    if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float v = part[0];
-        for (uint32_t w = 1; w < kMapeBlock / 64; w++) v += part[w];
-        partials[blockIdx.x] = v;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const uint32_t arrived = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool last = arrived == gridDim.x - 1;
-        if (last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        part[kMapeBlock / 64] = last ? 1.0f : 0.0f;
-    }
-    __syncthreads();
-    if (part[kMapeBlock / 64] != 0.0f) {  // (workgroup-uniform)
-        float v = 0.0f;
-        for (uint32_t i = threadIdx.x; i < gridDim.x; i += kMapeBlock) v += partials[i];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o, 64);
-        __syncthreads();
-        if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = v;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float r = part[0];
-            for (uint32_t w = 1; w < kMapeBlock / 64; w++) r += part[w];
-            *loss = r / fB;
-            *ticket = 0u;
-        }
-    }
+    // a lane's rows in index order, then the fixed order of csrc/ordered_sum.hpp
+    float total;
+    if (ordered_sum_finish(block_sum(s, sh), partials, ticket, gridDim.x, blockIdx.x, sh, total)) *loss = total / fB;
 }
 
 uint32_t mape_blocks(uint32_t B) {
@@ -192,26 +159,25 @@ S3D_EXPORT int s3d_sdf_sample_points(const float* triangles, const float* cdf, u
     return check_launch("sdf_sample_points");
 }
 
-S3D_EXPORT size_t s3d_sdf_mape_workspace_size(uint32_t B) { return 16 + sizeof(float) * (size_t)mape_blocks(B); }
+S3D_EXPORT size_t s3d_sdf_mape_workspace_size(uint32_t B) { return SumWorkspace::bytes(mape_blocks(B)); }
 
 S3D_EXPORT int s3d_sdf_mape_forward_backward(const void* pred, int dtype, const float* target, uint32_t B, float clip, float grad_scale,
                                              float* loss, void* grad, void* workspace, size_t workspace_bytes, s3d_stream_t stream) {
     S3D_REQUIRE(dtype == S3D_F32 || dtype == S3D_F16, "sdf_mape: dtype must be S3D_F32 ([B,1]) or S3D_F16 ([B,16])");
     S3D_REQUIRE(B > 0, "sdf_mape: the mean of an empty batch is undefined");
     S3D_REQUIRE(pred && target && loss && grad, "sdf_mape: pred, target, loss and grad must not be NULL");
-    S3D_REQUIRE(workspace && workspace_bytes >= s3d_sdf_mape_workspace_size(B) && (uintptr_t)workspace % 16 == 0,
+    S3D_REQUIRE(SumWorkspace::fits(workspace, workspace_bytes, mape_blocks(B)),
                 "sdf_mape: needs a 16-byte aligned workspace of s3d_sdf_mape_workspace_size(B) bytes");
     S3D_REQUIRE(dtype == S3D_F32 || ((uintptr_t)grad % 16 == 0), "sdf_mape: the fp16 gradient rows must be 16-byte aligned");
     hipStream_t st = as_stream(stream);
-    uint32_t* ticket = (uint32_t*)workspace;
-    float* partials = (float*)((char*)workspace + 16);
-    S3D_HIP(hipMemsetAsync(ticket, 0, 16, st));
+    SumWorkspace ws;
+    S3D_HIP(ws.arm(workspace, st));
     const uint32_t blocks = mape_blocks(B);
     if (dtype == S3D_F16)
         hipLaunchKernelGGL(sdf_mape_kernel<true>, dim3(blocks), dim3(kMapeBlock), 0, st, pred, target, B, clip, grad_scale, loss, grad,
-                           partials, ticket);
+                           ws.partials, ws.ticket);
     else
         hipLaunchKernelGGL(sdf_mape_kernel<false>, dim3(blocks), dim3(kMapeBlock), 0, st, pred, target, B, clip, grad_scale, loss, grad,
-                           partials, ticket);
+                           ws.partials, ws.ticket);
     return check_launch("sdf_mape_forward_backward");
 }

@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+import ordered_sum_witness as ow
+
 pytestmark = pytest.mark.gpu
 
 SENT = 12345.0  # sentinel the output buffers are pre-filled with (exact in fp16)
@@ -68,7 +70,7 @@ def _encoder(gridtype, log2=14):
 
 @pytest.mark.parametrize("gridtype", ["hash", "tiled"])
 @pytest.mark.parametrize("dtype", [torch.float16, torch.float32])
-@pytest.mark.parametrize("B", [1, 129, 1500])
+@pytest.mark.parametrize("B", [1, 129, 1500, 65795])  # (65,795: 258 chunks — a second partial for lane 0 of the last sum, three rows in the last chunk)
 def test_warp_grid_forward_is_the_add_and_the_grid_encoder(hip, gridtype, dtype, B):
     enc = _encoder(gridtype)
     table = enc.embeddings.detach().to(dtype).contiguous()
@@ -109,6 +111,10 @@ def test_warp_grid_forward_is_the_add_and_the_grid_encoder(hip, gridtype, dtype,
     total = float(dout[:, :3].double().abs().sum())
     assert abs(float(regs[0]) - total) <= 1e-6 * total + 1e-12
     assert torch.equal(regs[0], regs[1])  # the same bits in two runs
+    # ... and the bits of the documented order (csrc/ordered_sum.hpp): one row per lane, one partial per chunk of 256 rows
+    d = dout[:, :3].float().abs().cpu().numpy()
+    want_reg = ow.ordered_sum((d[:, 0] + d[:, 1]) + d[:, 2], (B + 255) // 256, strided=False)
+    assert regs[0].cpu().numpy().view(np.uint32) == want_reg.view(np.uint32), (float(regs[0]), float(want_reg))
     # through the module (the table the kernels read under autocast is its fp16 cast): GridEncoder's forward at xw
     if dtype == torch.float16:
         enc.eval()

@@ -1,6 +1,8 @@
 """D-NeRF temporal-basis backbone on the GPU: the two kernels of csrc/dnerf_basis.hip against the contract of include/seal3d_hip.h
 (bit for bit where it says so, within bounds derived from the number formats elsewhere), the fused route of the model against its
 own torch routes, the renderer's slot selection with this model, a budgeted step and a training smoke."""
+import json
+import os
 import zlib
 
 import numpy as np
@@ -8,6 +10,10 @@ import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
+
+# the bits of grad_sigma_basis recorded before the hand-over of the sum moved into csrc/ordered_sum.hpp
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ordered_sum_bits.json")) as _f:
+    RECORDED = json.load(_f)["basis_grad_sigma_basis"]
 
 SENT = 12345.0  # sentinel the output buffers are pre-filled with (exact in fp16)
 SIZES = [1, 63, 64, 65, 255, 256, 257, 1000]  # wave, workgroup and ragged edges of a one-lane-per-row kernel and its reduction
@@ -105,6 +111,7 @@ def test_mid_backward(hip, B, n_valid):
     assert (err <= bound).all()
     assert live == 0 or bool(g_sb.abs().sum() > 0)
     assert torch.equal(g_sb.view(torch.int32), again[1].view(torch.int32))  # the same bits in two runs
+    assert g_sb.view(torch.int32).cpu().tolist() == RECORDED[f"B{B}-nv{n_valid}"]
     assert torch.equal(_bits(again[0]), _bits(g_h))
     # without grad_sigma: zeros in the basis columns and in the sum, the copies as before
     z_h, z_sb = _backward(hip, h, sb, g_cin, None, n_valid)

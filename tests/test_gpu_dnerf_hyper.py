@@ -3,6 +3,8 @@ bit against s3d_grid_encode_forward with D = 4 where it says so, within a bound 
 grad_ambient), that D = 4 call itself against the CPU oracle, the fused route of the model against its own torch routes under both
 interpolations, the renderer's slot selection with this model, a budgeted step, a training smoke and the armed fused Adam update
 of the 4-D table."""
+import json
+import os
 import zlib
 
 import numpy as np
@@ -12,6 +14,11 @@ import torch
 import dnerf_hyper_witness as hw
 
 pytestmark = pytest.mark.gpu
+
+# the bits of grad_ambient recorded before the sum moved into csrc/ordered_sum.hpp (whose order tests/ordered_sum_witness.py pins
+# through the kernels whose terms numpy can restate)
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ordered_sum_bits.json")) as _f:
+    RECORDED = json.load(_f)["hyper_grad_ambient"]
 
 SENT = 1024.0  # sentinel the output buffers are pre-filled with (exact in fp16)
 BOUND = 1.0
@@ -233,6 +240,7 @@ def test_grid_backward(hip, B, n_valid, L, dtype):
     assert live == 0 or float(g_amb.abs()) > 0
     assert live != 0 or float(g_amb) == 0.0
     assert torch.equal(_bits(g_amb), _bits(again[1])) and torch.equal(_bits(levels), _bits(again[0]))  # the same bits in two runs
+    assert int(_bits(g_amb)) == RECORDED[f"B{B}-nv{n_valid}-L{L}-{'f16' if dtype == torch.float16 else 'f32'}"]
     # without dy_da or without the output word: the transposition alone, nothing else written
     only, word = _backward(hip, g, None, scale, dtype, n_valid)
     assert torch.equal(_bits(only), _bits(levels)) and float(word) == SENT

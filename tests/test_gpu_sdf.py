@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import ordered_sum_witness as ow
 import sdf_witness as sw
 
 pytestmark = pytest.mark.gpu
@@ -306,7 +307,8 @@ def test_sampler_statistics(hip):
 
 
 # ---- the MAPE kernel ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("B", [1, 127, 128, 4096])
+# (262,149: the grid is capped at 1,024 workgroups — five lanes get a second row, each lane of the last workgroup adds four partials)
+@pytest.mark.parametrize("B", [1, 127, 128, 4096, 262149])
 @pytest.mark.parametrize("half", [False, True])
 @pytest.mark.parametrize("clip", [None, 0.2])
 def test_mape_kernel(hip, B, half, clip):
@@ -335,6 +337,13 @@ def test_mape_kernel(hip, B, half, clip):
     assert grad.shape == dev.shape and grad.dtype == dev.dtype
     wl, wg = sw.mape(pred.numpy().astype(np.float64), target.numpy().astype(np.float64), clip, scale)
     assert abs(float(loss) - wl) <= 1e-6 * wl
+    # the bits of the documented order (csrc/ordered_sum.hpp) on the fp32 terms: a grid of min(1024, ceil(B / 256)) workgroups
+    p32, t32 = pred.numpy()[:, 0], target.numpy()
+    if clip:
+        p32 = np.clip(p32, np.float32(-clip), np.float32(clip))
+    terms = np.abs(p32 - t32) / (np.abs(t32) + np.float32(1e-2))
+    want_loss = ow.ordered_sum(terms, min(1024, (B + 255) // 256)) / np.float32(B)
+    assert want_loss.dtype == np.float32 and loss.cpu().numpy().view(np.uint32) == want_loss.view(np.uint32), (float(loss), float(want_loss))
     g = grad.float().cpu().numpy()
     if half:
         assert not g[:, 1:].any()
