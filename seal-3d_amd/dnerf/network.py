@@ -17,7 +17,7 @@ import s3d_hip
 from activation import trunc_exp
 from encoding import get_encoder
 from ffmlp.ffmlp import ffmlp_forward
-from gridencoder.grid import _table_backward, _table_for_kernels
+from gridencoder.grid import _table_backward, _table_for_kernels, note_table_use
 from nerf.network import _Background, _mlp, _run_mlp
 from nerf.network_ff import _NgpMid, _NgpRgb
 
@@ -193,6 +193,7 @@ class NeRFNetwork(NeRFRenderer):
             dout = ffmlp_forward(rows.din, self._pack_deform(), DIN, 16, 128, 4, 0, 6, infer, False, None, None, 0, None)
         else:
             dout = F.pad(_run_mlp(self.deform_net, rows.din[:, :self.in_dim_deform + self.in_dim_time]).to(torch.float16), (0, 13))
+        note_table_use(self.encoder.embeddings)
         sin, deform, reg = _WarpGrid.apply(x, dout.contiguous(), self.encoder.embeddings, self.encoder, float(self.bound), rows, want_reg)
         if self._sigma_fusable():
             h = ffmlp_forward(sin, self._pack_sigma(), SIN, 16, 64, 2, 0, 6, infer, sin.requires_grad, None, None, 0, None)

@@ -23,7 +23,7 @@ import s3d_hip
 from activation import trunc_exp
 from encoding import get_encoder
 from ffmlp.ffmlp import ffmlp_forward
-from gridencoder.grid import _table_backward, _table_for_kernels
+from gridencoder.grid import _table_backward, _table_for_kernels, note_table_use
 from nerf.network import _Background, _mlp, _run_mlp
 
 from .network_basis import BASIS, CIN, ROW, _BasisMid
@@ -156,6 +156,7 @@ class NeRFNetwork(NeRFRenderer):
         if Bp != B:
             x = torch.cat([x, x.new_zeros(Bp - B, 3)], dim=0)
         ambient = self._ambient(t).float()  # float(half(tanh(.)) * bound): what the reference's cat promotes; stays on the device
+        note_table_use(self.encoder.embeddings)
         feat = _HyperGrid.apply(x, ambient, self.encoder.embeddings, self.encoder, float(self.bound))
         hidden = F.relu(self.sigma_net[0](feat), inplace=True)
         return F.linear(hidden, self._head_weight()).to(torch.float16).contiguous(), Bp

@@ -111,7 +111,10 @@ class _GridEncode(Function):
         return grad_inputs, grad_embeddings, None, None, None, None, None, None, None, None, None, None, None, None
 
 
-grid_encode = _GridEncode.apply
+def grid_encode(inputs, embeddings, *args):
+    """`_GridEncode.apply` (the reference's `grid_encode`), the table's use counted for the optimizer's hand-over"""
+    note_table_use(embeddings)
+    return _GridEncode.apply(inputs, embeddings, *args)
 
 
 def _table_for_kernels(param, cache_half):
@@ -123,6 +126,18 @@ def _table_for_kernels(param, cache_half):
         if emb is None:
             emb = _half_table(param, cache_half)
     return emb.contiguous()
+
+
+def note_table_use(param):
+    """Called in front of the `apply` of every Function whose backward goes through `_table_backward`: an adopted table
+    (`param._s3d`) keeps count of the autograd nodes that will still scatter into it.  `_table_backward` counts them out again,
+    and an armed in-backward update waits for the last one.  (Asked out here, not in the Function's forward: grad mode is off in
+    there, and `ctx.needs_input_grad` says what requires a gradient also where no graph is recorded.)  A use whose backward
+    never reaches the table (a graph that is dropped) stays counted until the optimizer's next zero_grad() or step() starts the
+    count over: until then nothing is applied in a backward."""
+    h = getattr(param, "_s3d", None)
+    if h is not None and param.requires_grad and torch.is_grad_enabled():
+        h.pending += 1
 
 
 def _kernel_keywords(bound, n_valid, live):
@@ -160,7 +175,16 @@ def _table_backward(param, table, grad, inputs, offsets, geometry, extra, dy_dx=
     # kernel applies the update itself and no gradient is written
     armed = None
     if h is not None:
+        h.pending = max(h.pending - 1, 0)  # (this node has run: note_table_use counted it in)
         armed, h.arm = h.arm, None
+        # ... but only as the LAST table backward of the pass.  The kernel takes the step's skip decision from the flag as it
+        # stands when it starts; a table scatter that runs later — another table's, or this table's second node — may still
+        # raise it, and then a table has moved in a step that is skipped.  And the kernel updates from this call's row sums
+        # alone: gradient that another node of the same table adds to the hand-over buffer would be lost.  So: no forward use
+        # of any adopted table (`peers`) is left without its backward — this table's other uses included.  Every earlier
+        # scatter has raised the flag by now (same stream); whoever is not last takes the separate update in step().
+        if armed is not None and any(q.pending for q in armed.pop("peers", ())):
+            armed = None  # (a step tail attached to the arm stays with it: the trainer's close() issues what it holds)
     # ... and, with a step tail attached to the arm (s3d_hip.StepTail), the step's small closing launches as well.  (Where no
     # tail may ride, one attached to the arm stays there: the trainer's close() flushes it.)
     tail = armed.pop("tail", None) if (armed is not None and tail_may_ride) else None
@@ -221,6 +245,9 @@ class _GridEncodePair(Function):
         outs = []
         for k, (grad, table, param) in enumerate(((ga, ta, ctx.params[0]), (gb, tb, ctx.params[1]))):
             if grad is None or not ctx.needs_input_grad[1 + k]:  # (a frozen table of the pair: no scatter, no hand-over mark)
+                h = getattr(param, "_s3d", None)
+                if h is not None and ctx.needs_input_grad[1 + k]:
+                    h.pending = max(h.pending - 1, 0)  # (an output nobody used: the use the forward counted is over)
                 outs.append(None)
                 continue
             # in-backward update (nerf/optim.py: arm_fused_tables) for the LAST table of the pair only: its kernel takes the step's
@@ -249,6 +276,8 @@ def grid_encode_pair(enc_a, enc_b, inputs, bound=1, n_valid=None, live=None):
     halfed = torch.is_autocast_enabled("cuda") and C % 2 == 0
     if not same or (C * (2 if halfed else enc_a.embeddings.element_size())) % 4:  # (the lane-pair kernel: whole 32-bit feature words)
         return None
+    note_table_use(enc_a.embeddings)
+    note_table_use(enc_b.embeddings)
     return _GridEncodePair.apply(inputs, enc_a.embeddings, enc_b.embeddings, enc_a.offsets, enc_a.per_level_scale,
                                  enc_a.base_resolution, enc_a.gridtype_id, enc_a.align_corners, enc_a.interp_id,
                                  not enc_a.training, float(bound), n_valid, live)

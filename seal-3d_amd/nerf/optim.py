@@ -96,13 +96,23 @@ class NativeAdam(torch.optim.Optimizer):
         other gradient of the step checked where it is produced): each adopted fp16 C = 2 table is armed — its backward
         (gridencoder/grid.py) hands this state to s3d_grid_encode_backward_adam, the accumulate kernel applies the update where
         the row sums are, and `step()` leaves the table alone.  A table whose backward does not run, or falls back to the plain
-        kernels, is updated by `step()` as always.  Returns the number of tables armed."""
+        kernels, is updated by `step()` as always.  Returns the number of tables armed.
+        A step updates every parameter or none, so of the armed tables only the one whose backward runs LAST in the pass applies
+        its update there — its kernel starts behind every other table's scatter and sees the flag they raised; the others, and a
+        table that feeds more than one node of the pass, keep the separate update (`peers`: gridencoder.grid._table_backward)."""
         n = 0
         if not self.fuse_table_updates or self.flat_half is None:
             return 0
         lr_of = {}
         if self._lr_captured is not None:
+            # the kernel reads the schedule factor step() would write — after this backward: bring it up to date here, as step()
+            # does (under capture the replaying trainer does it before each replay)
+            if not torch.cuda.is_current_stream_capturing() and not self.follow_lr_schedule():
+                self.capture_lr()  # groups moved apart: rebase now, step() finds nothing left to do
             lr_of = {id(g): lr for g, lr in zip(self.param_groups, self._lr_captured)}
+        # every adopted table whose gradient arrives through a table backward: one that is still to run may raise the flag
+        peers = [q._s3d for g in self.param_groups for q in g["params"]
+                 if getattr(q, "_s3d", None) is not None and getattr(q, "_s3d_stash_ok", False) and q.requires_grad]
         for group in self.param_groups:
             for p in group["params"]:
                 h = getattr(p, "_s3d", None)
@@ -114,7 +124,7 @@ class NativeAdam(torch.optim.Optimizer):
                 b1, b2 = group["betas"]
                 h.arm = dict(param=p.data, exp_avg=st["exp_avg"], exp_avg_sq=st["exp_avg_sq"], param_half=half,
                              lr=lr_of.get(id(group), group["lr"]), betas=(b1, b2), eps=group["eps"], step=self.step_count,
-                             grad_scale=grad_scale, lr_scale=self.lr_scale)
+                             grad_scale=grad_scale, lr_scale=self.lr_scale, peers=peers)
                 n += 1
         return n
 
@@ -211,6 +221,9 @@ class NativeAdam(torch.optim.Optimizer):
                 h = getattr(p, "_s3d", None)
                 if h is not None:
                     h.touched = h.consumed = h.unchecked = False
+                    # (the step's forward passes start here: a use counted earlier whose backward never ran is not one this
+                    #  step's backward has to wait for)
+                    h.pending = 0
                 p.__dict__.pop("_s3d_grad_checked", None)  # (a producer's "checked at the source" mark never outlives its step)
                 if p.grad is not None:
                     if set_to_none:
@@ -355,7 +368,7 @@ class NativeAdam(torch.optim.Optimizer):
         if advance:
             _backend.adam_advance(self.step_count, found_inf)
         for _, h in self._records():  # (the marks of this step's in-backward updates; an arm nobody consumed goes with them)
-            h.fused_done, h.arm = False, None
+            h.fused_done, h.arm, h.pending = False, None, 0
 
 
 class NativeGradScaler:

@@ -260,14 +260,17 @@ class Handover:
       touched, consumed         written since the last clear / read (and cleared) by a step since: host-side flags
       unchecked                 a torch op wrote `grad`: the scaler checks the buffer itself
       found_inf                 the attached scaler's flag, raised by the kernels that write `grad` (NativeGradScaler.attach)
-      arm, fused_done           arguments of the update a table's backward applies itself (arm_fused_tables) / it did so"""
+      arm, fused_done           arguments of the update a table's backward applies itself (arm_fused_tables) / it did so
+      pending                   forward passes that took this table into an autograd graph and whose backward has not run yet
+                                (gridencoder.grid: note_table_use / _table_backward; the optimizer's zero_grad() and step() start it over)"""
     __slots__ = ("grad", "flat", "flat_range", "half", "half_version", "touched", "consumed", "unchecked", "found_inf", "arm",
-                 "fused_done")
+                 "fused_done", "pending")
 
     def __init__(self, grad=None, flat=None, flat_range=None, half=None, half_version=None):
         self.grad, self.flat, self.flat_range, self.half, self.half_version = grad, flat, flat_range, half, half_version
         self.touched = self.consumed = self.unchecked = self.fused_done = False
         self.found_inf = self.arm = None
+        self.pending = 0
 
     def fresh_half(self, p):
         """the fp16 copy while it is p's current value, else None (somebody wrote the parameter through torch)"""
